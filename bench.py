@@ -28,6 +28,17 @@ through ONE all-gather of the 144-byte result records, reduced on the device
 at the same N (cfg4: K = 262,144; cfg5: K = 65,536 with CEM x4) and cfg3
 weak-scaled.  Rank 0 prints ONE JSON line; its ``summary`` key (last) holds
 every line's value / p50 / roofline fraction.
+
+A plain run (``--gpus N --steps S --warmup W``) measures the headline alone:
+set up, prewarm + W warmup steps, exactly S timed steps, the JSON line
+(``ms_per_step`` = the timed wall time / S).  ``--full`` adds every other
+line -- the CPU baseline, ``dropin_parity_p50_ms``, the small-K, cfg2,
+ns_shard / cfg4_shard / cfg5, f16 and ``scale`` lines, the library
+communicator's line at N > 1 -- each still switched off by its ``--no-*``
+option.  ``--dump-outputs DIR`` writes what the last timed step returned
+(best cost, best index, first action) and its per-candidate costs as
+``DIR/<name>.npy``; the inputs are seeded, so the same arguments give the same
+problem on every run.
 """
 from __future__ import annotations
 
@@ -816,24 +827,41 @@ class RankCtx:
 def timed_loop(ctx, step, steps, warmup, kernel_ms=None):
     """W untimed steps, then EXACTLY ``steps`` steps bracketed by a barrier + device synchronisation on
     both sides; the wall time is the max over ranks.  ``kernel_ms``: read after each step (HIP events of
-    the rollout launch on its stream)."""
+    the rollout launch on its stream).  Also returns what the last timed step returned to its caller."""
     import torch
     for i in range(warmup):
         step(i)
     ctx.barrier()
     torch.cuda.synchronize(ctx.dev)
-    ts, ks = [], []
+    ts, ks, last = [], [], None
     t0 = time.perf_counter()
     for i in range(steps):
         t1 = time.perf_counter()
-        step(warmup + i)
+        last = step(warmup + i)
         ts.append(time.perf_counter() - t1)
         if kernel_ms is not None:
             ks.append(kernel_ms())
     torch.cuda.synchronize(ctx.dev)
     ctx.barrier()
     elapsed = ctx.allreduce(time.perf_counter() - t0, "max")
-    return elapsed, ts, ks
+    return elapsed, ts, ks, last
+
+
+def dump_outputs(path, last, costs=None):
+    """``--dump-outputs``: what the last timed step handed its caller -- (best cost, best index, first action) --
+    as ``best_cost.npy``, ``best_index.npy`` and ``first_action.npy``, and, where the line has them, that step's
+    per-candidate costs as ``candidate_costs.npy``; all float64 (a few hundred KB at K = 65,536).  The inputs
+    are seeded (synthetic_problem, the steps' Philox seeds), so two builds run with the same arguments are
+    compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    cost, index, first = last
+    arrays = {"best_cost": np.asarray(cost, dtype=np.float64), "best_index": np.asarray(index, dtype=np.float64),
+              "first_action": np.asarray(first, dtype=np.float64).reshape(-1)[:A_DIM]}
+    if costs is not None:
+        arrays["candidate_costs"] = np.asarray(costs, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def rollout_stepper(ctx, eng, state, lo, maximize, lib_comm=None):
@@ -935,7 +963,7 @@ def scale_line(ctx, name, K_global, steps, warmup, precision="auto", scaling="st
         step, carrier = rollout_stepper(ctx, eng, prob["state"], lo, prob["reward"])
         kms = lambda: eng.last_kernel_ms()[0]          # noqa: E731
     pre = prewarm(step, ctx)
-    el, ts, ks = timed_loop(ctx, step, steps, warmup, kms)
+    el, ts, ks, _ = timed_loop(ctx, step, steps, warmup, kms)
     H = wl["H"]
     fpcs = flop_per_cand_step(wl["hidden"], wl["L"])
     # (multi-rank CEM: the HIP events see one pass at a time; the per-rank device share is the step's wall)
@@ -1103,7 +1131,18 @@ def main():
                          "that every N measures over all its ranks")
     ap.add_argument("--no-small-k", action="store_true",
                     help="skip the small-K get_action lines (ppo_defaults, runsh_recipe, cfg1: team vs slab kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else this bench reports: the CPU baseline, the "
+                         "drop-in controller's p50, the small-K, cfg2, ns_shard / cfg4_shard / cfg5, f16 and `scale` "
+                         "lines and (N > 1) the library communicator's line; the --no-* options above trim it.  "
+                         "Without --full none of them runs: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (best_cost, "
+                         "best_index, first_action) and that step's per-candidate costs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if not args.full:                                  # the plain run: the headline alone
+        args.no_cpu_baseline = args.no_cfg2 = args.no_extra = args.no_scale = args.no_small_k = args.no_f16 = True
+        args.dropin_calls = 0
 
     plan = launch_plan(args.gpus, os.environ)
     if plan == "spawn":                                # before any GPU call: N ranks in a child launcher
@@ -1186,7 +1225,21 @@ def main():
 
     kms = (lambda: eng.last_kernel_ms()[0]) if not (cem and world > 1) else None
     pre = prewarm(step, ctx)                           # (untimed: the GPU's clock ramp after idle, see prewarm)
-    elapsed, step_s, kern_ms = timed_loop(ctx, step, args.steps, args.warmup, kms)
+    elapsed, step_s, kern_ms, last = timed_loop(ctx, step, args.steps, args.warmup, kms)
+
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        costs = None
+        if cem:                                        # (a CEM call keeps no single cost vector)
+            pass
+        elif args.actions == "hbm":                    # the cost vector the last timed launch wrote
+            costs = d_costs.cpu().numpy()
+        elif world == 1:
+            # the last timed step again (same state, seed and offset) with the cost vector requested: the
+            # timed call itself returns the winner only
+            costs = eng.get_action(state, None, seed=0xB0B + args.warmup + args.steps - 1, cand_offset=lo,
+                                   return_costs=True).costs
+        dumped = dump_outputs(args.dump_outputs, last, costs)
 
     scale = None
     if not args.no_scale and args.workload == "cfg3" and args.scaling == "strong":
@@ -1198,7 +1251,7 @@ def main():
                               "= the headline (N=1)")
 
     lib_line = None
-    if world > 1 and lib_comm is None and not cem and args.actions == "device":
+    if args.full and world > 1 and lib_comm is None and not cem and args.actions == "device":
         lib_line = library_comm_line(eng, state, lo, K, H, args.steps, args.warmup, world, local, backend)
 
     dropin = None
@@ -1250,7 +1303,7 @@ def main():
                    "collective": carrier},
         "p50_ms": float(np.percentile(step_s, 50) * 1e3),
         "dropin_parity_p50_ms": dropin["p50_ms"] if dropin else None,
-        "dropin_parity": dropin if dropin else "n/a (MPCcontroller drop-in is timed for the plain delta-net "
+        "dropin_parity": dropin if dropin else "n/a (MPCcontroller drop-in is timed with --full, for the plain delta-net "
                                                 "workloads; policy / reward / CEM controllers: tools/bench_dropin.py)",
         "p90_ms": float(np.percentile(step_s, 90) * 1e3),
         "kernel_ms_avg": kern_avg_s * 1e3,
@@ -1273,6 +1326,8 @@ def main():
         "prewarm": dict(pre, note="untimed control steps of the same workload before the W warmup steps: the GPU's "
                                   "clocks ramp over the first ~40 ms of work after idle (profiles/r06_cold_ramp.txt)"),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if scale is not None:
         out["scale"] = scale
     if lib_line is not None:

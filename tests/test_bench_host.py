@@ -134,6 +134,22 @@ def test_summary_key_is_compact_and_covers_every_line():
     assert list(s)[0] == "headline" and "ns_shard" in s and "cfg2" in s
 
 
+def test_dump_outputs_writes_float64_npy_files(tmp_path):
+    # a step's (cost, index, first action) as the exchange returns it: the action padded to MAX_ACTION
+    first = np.arange(16, dtype=np.float32) / 16
+    out = str(tmp_path / "a" / "b")                                   # (created on demand)
+    assert bench.dump_outputs(out, (1.5, 7, first)) == ["best_cost", "best_index", "first_action"]
+    assert sorted(os.listdir(out)) == ["best_cost.npy", "best_index.npy", "first_action.npy"]
+    fa = np.load(os.path.join(out, "first_action.npy"))
+    assert fa.dtype == np.float64 and np.array_equal(fa, first[:bench.A_DIM])
+    assert float(np.load(os.path.join(out, "best_cost.npy"))) == 1.5
+    assert float(np.load(os.path.join(out, "best_index.npy"))) == 7.0
+    costs = np.linspace(-1, 1, 33, dtype=np.float32)
+    assert "candidate_costs" in bench.dump_outputs(out, (1.5, 7, first), costs)
+    cc = np.load(os.path.join(out, "candidate_costs.npy"))
+    assert cc.dtype == np.float64 and np.array_equal(cc, costs)
+
+
 def test_ns_shard_is_the_north_star_per_gpu_shard():
     base = json.load(open(os.path.join(REPO, "BASELINE.json")))
     assert "K=65536" in base["north_star"] and "8" in base["north_star"]

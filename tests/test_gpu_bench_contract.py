@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -29,8 +30,18 @@ def _bench(*args, env=None):
     return json.loads(lines[0])
 
 
-def test_headline_line_contract():
-    d = _bench("--steps", "5", "--warmup", "2", *LEAN)
+def _load(path):
+    return {n[:-4]: np.load(os.path.join(path, n)) for n in sorted(os.listdir(path)) if n.endswith(".npy")}
+
+
+@pytest.fixture(scope="module")
+def headline(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("headline") / "dump")
+    return _bench("--steps", "5", "--warmup", "2", *LEAN, "--dump-outputs", out), _load(out)
+
+
+def test_headline_line_contract(headline):
+    d = headline[0]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -50,6 +61,31 @@ def test_headline_line_contract():
     assert r["flop_per_launch"] / (r["achieved"] * 1e12) * 1e3 <= d["ms_per_step"] * 1.02
 
 
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(headline, tmp_path):
+    """Without ``--full`` (and without any ``--no-*`` option) the bench measures the headline only: exactly
+    ``--steps`` timed steps, none of the other lines.  ``--dump-outputs`` writes what the last timed step
+    returned and its candidate costs as float64 ``.npy`` files; the inputs are seeded, so a second run with the
+    same arguments (the ``headline`` fixture's: the same steps and warmup) writes the same arrays."""
+    out = str(tmp_path / "dump")
+    d = _bench("--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", out)
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(65536 * 20 / (d["ms_per_step"] / 1e3), rel=1e-6)
+    assert d["cpu_baseline"] is None and d["small_k"] is None and d["dropin_parity_p50_ms"] is None
+    for k in ("scale", "cfg2", "ns_shard", "cfg4_shard", "cfg5", "f16_single_pass", "library_comm"):
+        assert k not in d, k
+    assert list(d["summary"]) == ["headline"]
+    a = _load(out)
+    assert sorted(a) == ["best_cost", "best_index", "candidate_costs", "first_action"] == d["dumped_outputs"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["first_action"].shape == (6,) and a["candidate_costs"].shape == (65536,)
+    assert np.all(np.abs(a["first_action"]) <= 1.0) and np.all(np.isfinite(a["candidate_costs"]))
+    # the winner the timed step returned is the cost vector's first minimum (np.argmin's rule)
+    assert int(a["best_index"]) == int(np.argmin(a["candidate_costs"]))
+    assert float(a["best_cost"]) == a["candidate_costs"].min()
+    b = headline[1]
+    assert sorted(b) == sorted(a) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_cem_line_contract():
     d = _bench("--workload", "cfg5", "--steps", "1", "--warmup", "1", *LEAN)
     K, H = d["config"]["K_per_gpu"], d["config"]["horizon"]
@@ -63,7 +99,7 @@ def test_self_launched_two_ranks_split_the_global_k():
     """``bench.py --gpus 2`` with no WORLD_SIZE starts the two ranks itself (gloo, both on this card): the
     north_star's K = 65,536 is split 32,768 per rank, the record exchange ran over 2 ranks, and the scale
     line's cfg4 is K_global = 262,144 over the same 2 ranks."""
-    d = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", *[a for a in LEAN if a != "--no-scale"],
+    d = _bench("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", *[a for a in LEAN if a != "--no-scale"],
                env={"BCMPC_DIST_BACKEND": "gloo", "BCMPC_BENCH_DEVICE": "0"})
     assert d["n_gpus"] == 2 and d["config"]["ranks"] == 2 and d["scaling"] == "strong"
     assert d["config"]["K_global"] == 65536 and d["config"]["K_per_gpu"] == 32768

@@ -10,7 +10,7 @@ WL=$1; N=$2; shift 2
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in "$@"; do
     if [ "$lib" = tree ]; then unset BCMPC_LIB; else export BCMPC_LIB=$PWD/$lib; fi
-    env ${KERNEL:+BCMPC_KERNEL=$KERNEL} timeout -k 10 200 python bench.py --workload "$WL" --steps "$N" --warmup 10 \
+    env ${KERNEL:+BCMPC_KERNEL=$KERNEL} timeout -k 10 200 python bench.py ${AB_SMALLK:+--full} --workload "$WL" --steps "$N" --warmup 10 \
         --no-cpu-baseline $([ -n "${AB_SMALLK:-}" ] || echo --no-small-k) --no-cfg2 --no-f16 --no-extra --dropin-calls 0 ${AB_ARGS:-} > gpurun_out/ab_libs.log 2>&1 \
         || { echo "$lib failed"; tail -5 gpurun_out/ab_libs.log; exit 1; }
     python - "$lib" gpurun_out/ab_libs.log <<'PY'

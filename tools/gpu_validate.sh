@@ -3,7 +3,7 @@
 #   STEPS  (space-separated, run in this order; any failure ends the script)
 #     tests    pytest -m gpu over $TESTS (default: the whole suite)
 #     smoke    __graft_entry__.smoke()
-#     bench    python bench.py $BENCH_ARGS                       -> $OUT/bench.json
+#     bench    python bench.py --full $BENCH_ARGS                -> $OUT/bench.json
 #     trace    rocprofv3 --kernel-trace --stats of the same bench   -> $OUT/trace/
 #     timed    kernel trace of the headline's timed launches only   -> $OUT/trace_timed/
 #     traffic  PMC FETCH_SIZE / WRITE_SIZE passes per workload      -> $OUT/traffic_*/
@@ -45,11 +45,11 @@ for step in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || stop smoke $?
       cat "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 600 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || stop bench $?
+      timeout -k 10 600 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || stop bench $?
       echo "bench: $(head -c 300 "$OUT/bench.json")" ;;
     trace)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-          python3 bench.py $BENCH_ARGS > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err" || stop trace $? ;;
+          python3 bench.py --full $BENCH_ARGS > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err" || stop trace $? ;;
     timed)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_timed" -o run -- \
           python3 bench.py --steps 50 --warmup 5 $LITE $BENCH_ARGS > "$OUT/trace_timed.json" 2>&1 || stop timed $? ;;
@@ -74,7 +74,7 @@ for step in $STEPS; do
       python3 "$R/tools/pmc_issue.py" "$OUT" "$PMC_KERNEL" ${PMC_CANDSTEPS:-1310720} > "$OUT/pmc_summary.txt" 2>&1 || true
       cat "$OUT/pmc_summary.txt" ;;
     rehearse)
-      BCMPC_DIST_BACKEND=gloo BCMPC_BENCH_DEVICE=0 timeout -k 10 400 python bench.py --gpus ${RANKS:-2} --steps 5 \
+      BCMPC_DIST_BACKEND=gloo BCMPC_BENCH_DEVICE=0 timeout -k 10 400 python bench.py --full --gpus ${RANKS:-2} --steps 5 \
           --warmup 1 --no-cpu-baseline $BENCH_ARGS > "$OUT/rehearsal.json" 2> "$OUT/rehearsal.err" || stop rehearse $?
       tail -c 600 "$OUT/rehearsal.json" ;;
     ab)
