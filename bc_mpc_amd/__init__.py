@@ -11,10 +11,10 @@ from .controllers import (Controller, MCTScontrollerPolicyNetReward, MPCcontroll
                           MPCcontrollerPolicyNetReward, MPCcontrollerReward, RandomController)
 from .cem import CEMcontroller
 from .cost_functions import cheetah_cost_fn, trajectory_cost_fn
-from .engine import MLPSpec, PolicySpec, RolloutEngine, StepResult
+from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
-           "trajectory_cost_fn", "MLPSpec", "RolloutEngine", "StepResult"]
+           "trajectory_cost_fn", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

@@ -25,7 +25,7 @@ MAX_LAYERS = 8
 MAX_STATE = 32
 MAX_ACTION = 16
 COMM_ID_BYTES = 128
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE, ERR_EMPTY = range(6)
 ACT_TANH, ACT_RELU = 0, 1
@@ -149,6 +149,11 @@ SIGNATURES = [
     ("bcmpc_set_action_bounds", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("bcmpc_get_action", ctypes.c_int,
      [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
+    ("bcmpc_get_actions_batch", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
+    ("bcmpc_rollout_batch_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_get_action_mt19937", ctypes.c_int,
      [ctypes.c_void_p, _DP, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), _DP, _DP,
       ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.POINTER(Result), _DP]),

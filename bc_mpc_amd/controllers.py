@@ -128,6 +128,23 @@ def _minloc(ctrl, eng, valid, cost, index, first, A):
     return _dist.allgather_minloc(valid, cost, index, first, A, ctrl._group, device=_comm_device(ctrl))
 
 
+def _batch_rng_check(rng: str) -> None:
+    """get_actions draws in the kernel only: the host-stream modes promise ONE draw per get_action call
+    in the reference's order, and a batch of environments in one launch cannot keep that order."""
+    if rng != "device":
+        raise ValueError(f"get_actions needs rng='device': rng={rng!r} promises one host-stream draw per "
+                         "get_action call in the reference's order, which a batched step cannot keep")
+
+
+def _batch_states(states, S: int, group) -> np.ndarray:
+    states = np.ascontiguousarray(states, dtype=np.float64)
+    if states.ndim != 2 or states.shape[1] != S or states.shape[0] < 1:
+        raise ValueError(f"states shape {states.shape} != (B, S) = (B >= 1, {S})")
+    if _dist.world(group)[1] != 1:
+        raise ValueError("get_actions runs on a single rank (candidate sharding is not batched yet)")
+    return states
+
+
 class MPCcontroller(Controller):
     """Random-shooting MPC (controllers.py:26-88) on the MI355X rollout engine."""
 
@@ -282,6 +299,45 @@ class MPCcontroller(Controller):
             opt_action_path = action_paths[:, index, :]     # controllers.py:84-85
             return opt_action_path[0].copy()
         return first_g
+
+    def get_actions(self, states):
+        """Batched control step (not in the reference): ``states`` is ``[B, S]``, one independent
+        random-shooting answer per row with ``num_simulated_paths`` candidates each, all rolled out in one
+        launch chain (``RolloutEngine.get_actions``).  Returns ``[B, A]`` float64.  Row ``b`` is what
+        ``get_action(states[b])`` returns on the Philox candidates ``b*K .. (b+1)*K`` of the call's seed
+        (one seed is drawn per call, as ``get_action`` draws one).  ``rng="device"`` on one rank with the
+        fused cheetah cost only."""
+        _batch_rng_check(self.rng)
+        S, A = self._dims()
+        K = int(self.num_simulated_paths)
+        if self.horizon < 1:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        states = _batch_states(states, S, self._group)
+        spec, norm, version = _weights.extract(self.dyn_model)
+        if spec.model != "delta":
+            raise TypeError("MPCcontroller needs an NNDynamicsModel; use MPCcontrollerReward")
+        if not is_cheetah_cost(self.cost_fn, S, A):
+            raise ValueError("get_actions needs the fused cheetah cost_fn")
+        seed = self._next_seed()
+        if K == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        dev = _default_device() if self._device is None else self._device
+        key = (S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
+               states.shape[0] * K, dev)
+        eng = getattr(self, "_batch_engine", None)
+        if eng is None or self._batch_key != key:
+            if eng is not None:
+                eng.close()
+            eng = self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation,
+                                                     spec.layer_norm, int(self.horizon), states.shape[0] * K,
+                                                     device=dev, cost="cheetah")
+            eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
+                                  np.asarray(self.env.action_space.high, dtype=np.float64))
+            self._batch_key = key
+        eng.set_weights(spec, norm, version)
+        res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
+        self.last_costs, self.last_cost, self.last_index = res.costs, res.best_cost, res.best_index
+        return res.first_action
 
     def _trajectory_costs(self, eng: RolloutEngine, state, local_actions) -> np.ndarray:
         """Non-fused cost_fn: the engine returns states_paths_all (controllers.py:65-74)
@@ -601,6 +657,44 @@ class MPCcontrollerReward(Controller):
         if action_paths is not None:
             return copy.copy(action_paths[:, index, :][0])    # controllers.py:154-156
         return first_g
+
+    def get_actions(self, states):
+        """Batched control step (not in the reference): ``states`` ``[B, S]`` -> ``[B, A]`` float64, row ``b``
+        the ARGMAX answer for ``states[b]`` on the Philox candidates ``b*K .. (b+1)*K`` of the call's seed
+        (one seed per call), all environments in one launch chain (``RolloutEngine.get_actions``).
+        ``rng="device"`` on one rank only."""
+        _batch_rng_check(self.rng)
+        S = int(math.prod(self.env.observation_space.shape))
+        A = len(self.env.action_space.high)
+        K = int(self.num_simulated_paths)
+        if self.horizon < 1:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        states = _batch_states(states, S, self._group)
+        spec, norm, version = _weights.extract(self.dyn_model)
+        _check_model(spec, "reward", type(self).__name__)
+        seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
+        if K == 0:
+            raise ValueError("attempt to get argmax of an empty sequence")
+        dev = _default_device() if self._device is None else self._device
+        key = (S, A, spec.hidden, spec.layer_norm, int(self.horizon), states.shape[0] * K, dev)
+        eng = getattr(self, "_batch_engine", None)
+        if eng is None or self._batch_key != key:
+            if eng is not None:
+                eng.close()
+            eng = self._batch_engine = RolloutEngine(S, A, spec.hidden, 2, "tanh", spec.layer_norm,
+                                                     int(self.horizon), states.shape[0] * K, device=dev,
+                                                     cost="reward", model="reward")
+            eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
+                                  np.asarray(self.env.action_space.high, dtype=np.float64))
+            self._batch_key = key
+            self._batch_gamma = None
+        if self._batch_gamma != float(self.gamma):
+            eng.set_discount(float(self.gamma))
+            self._batch_gamma = float(self.gamma)
+        eng.set_weights(spec, norm, version)
+        res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
+        self.last_rewards, self.last_reward, self.last_index = res.costs, res.best_cost, res.best_index
+        return res.first_action
 
 
 class MPCcontrollerPolicyNetReward(MPCcontrollerPolicyNet):

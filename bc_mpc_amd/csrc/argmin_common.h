@@ -6,6 +6,26 @@
 
 namespace bcmpc {
 
+// One block's best record from every thread's own (sc / si: one LDS slot per wave); better() is a total
+// order, so the grouping cannot change the answer.  Shared by the argmin launches (rollout.hip) and the
+// batched step's per-environment argmin (batch.hip).
+__device__ __forceinline__ Best block_best(Best best, double* sc, int64_t* si) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        Best o{__shfl_xor(best.c, off), __shfl_xor(best.i, off)};
+        if (better(o, best)) best = o;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { sc[wave] = best.c; si[wave] = best.i; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+            const Best o{sc[w], si[w]};
+            if (better(o, best)) best = o;
+        }
+    return best;                                   // valid in thread 0
+}
+
 // Writes out->{best_index, best_cost, first_action} for the winning (cost, index) record
 // (maximize: the record holds -cost).  CEM merge: np.argmin over the iteration-major
 // concatenation keeps the earlier best on ties.

@@ -221,6 +221,12 @@ struct bcmpc_engine {
     int64_t* d_amin_i = nullptr;
     size_t amin_cap = 0;                // records the scratch holds
     unsigned* d_amin_ticket = nullptr;  // fused argmin (split kernel): last-workgroup ticket
+    // batched control step (bcmpc_get_actions_batch / bcmpc_rollout_batch_async), allocated on first use
+    double* d_tiled = nullptr;          // [num_paths][S] the environments' states expanded to the candidates
+    double* d_bstates = nullptr;        // [batch_cap][S] the environments' states (synchronous call)
+    bcmpc_result* d_bresults = nullptr; // [batch_cap] records
+    bcmpc_result* h_bresults = nullptr; // pinned mirror
+    int32_t batch_cap = 0;              // environments d_bstates / d_bresults / h_bresults hold
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;
     int team_kind = 0;                  // 0 plain delta net, 1 + policy, 2 reward net (+ policy)
@@ -687,8 +693,10 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_first, (void*)e->d_gpow, (void*)e->d_mu, (void*)e->d_sigma, (void*)e->d_elite,
                     (void*)e->d_count, (void*)e->d_amin_c, (void*)e->d_amin_i,
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
-                    (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part})
+                    (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
+                    (void*)e->d_bstates, (void*)e->d_bresults})
         if (p) (void)hipFree(p);
+    if (e->h_bresults) (void)hipHostFree(e->h_bresults);
     if (e->h_result) (void)hipHostFree(e->h_result);
     if (e->h_result_map) (void)hipHostFree(e->h_result_map);
     if (e->h_team_err) (void)hipHostFree(e->h_team_err);
@@ -1639,6 +1647,110 @@ int bcmpc_get_action(bcmpc_engine* e, const double* state, const double* actions
         return bcmpc_get_action(re, state, actions, seed, cand_offset, out, costs_out);
     }
     *out = lean ? *e->h_result_map : *e->h_result;
+    return BCMPC_OK;
+}
+
+// ---- batched control step: n_envs environments x K candidates per launch chain --------------
+// Column c = b * K + j of the engine's num_paths candidates belongs to environment b.  The states are
+// expanded to the candidates by a kernel of their own (batch.hip tile_states), so that the rollout
+// kernels run exactly as for bcmpc_rollout_async with per-candidate states; argmin_segments then
+// reduces each environment's K costs to its record.
+static int batch_check(const bcmpc_engine* e, int32_t n_envs) {
+    const bcmpc_config& c = e->cfg;
+    if (c.cost == BCMPC_COST_NONE)
+        return fail(BCMPC_ERR_ARG, "the batched step needs a fused objective (cheetah cost or learned reward)");
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (c.num_paths % n_envs != 0)
+        return fail(BCMPC_ERR_ARG, "num_paths (" + std::to_string(c.num_paths) + ") is not a multiple of n_envs (" +
+                                       std::to_string(n_envs) + ")");
+    if (e->PL > 0) return fail(BCMPC_ERR_UNSUPPORTED, "the batched step does not cover engines with a fused policy yet");
+    if (e->comm)
+        return fail(BCMPC_ERR_UNSUPPORTED, "the batched step does not cover engines with a communicator attached yet");
+    if (!e->has_weights) return fail(BCMPC_ERR_STATE, "bcmpc_set_weights has not been called");
+    if (c.num_paths == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    return BCMPC_OK;
+}
+
+// tile_states -> rollout (per-candidate states, no argmin) -> argmin_segments, all on st
+static int batch_impl(bcmpc_engine* e, const double* d_states, int32_t n_envs, const double* d_actions,
+                      uint64_t seed, int64_t cand_offset, double* d_costs, bcmpc_result* d_results,
+                      hipStream_t st) {
+    const bcmpc_config& c = e->cfg;
+    if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
+    const int64_t K = c.num_paths / n_envs;
+    const bool timing = e->timing;
+    if (timing) HIP_TRY(hipEventRecord(e->ev[0], st));
+    TileStatesArgs t{};
+    t.states = d_states; t.out = e->d_tiled; t.K = K; t.Ktot = c.num_paths; t.S = c.state_dim;
+    HIP_TRY(launch_tile_states(t, st));
+    if (const int rc = rollout_impl(e, e->d_tiled, c.state_dim, d_actions, seed, cand_offset, d_costs, nullptr,
+                                    nullptr, st, nullptr, false))
+        return rc;
+    if (timing) HIP_TRY(hipEventRecord(e->ev[1], st));
+    SegmentArgminArgs m{};
+    m.costs = d_costs; m.actions = d_actions; m.consts = e->d_consts; m.out = d_results;
+    m.seed = seed; m.cand_offset = cand_offset; m.K = K; m.n_envs = n_envs; m.A = c.action_dim;
+    m.maximize = c.cost == BCMPC_COST_REWARD;
+    HIP_TRY(launch_argmin_segments(m, st));
+    if (timing) HIP_TRY(hipEventRecord(e->ev[2], st));
+    e->timed = timing;                                 // (bcmpc_last_kernel_ms: tile + rollout | argmin)
+    return BCMPC_OK;
+}
+
+int bcmpc_rollout_batch_async(bcmpc_engine* e, const double* d_states, int32_t n_envs, const double* d_actions,
+                              uint64_t seed, int64_t cand_offset, double* d_costs, bcmpc_result* d_results,
+                              void* stream) {
+    if (!e || !d_states || !d_costs || !d_results) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return batch_impl(e, d_states, n_envs, d_actions, seed, cand_offset, d_costs, d_results, (hipStream_t)stream);
+}
+
+int bcmpc_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const double* actions,
+                            uint64_t seed, int64_t cand_offset, bcmpc_result* out, double* costs_out) {
+    if (!e || !states || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    const bcmpc_config& c = e->cfg;
+    HIP_TRY(hipSetDevice(c.device));
+    const SyncCall sync_guard(e);
+    if (n_envs > e->batch_cap) {
+        for (void* p : {(void*)e->d_bstates, (void*)e->d_bresults})
+            if (p) (void)hipFree(p);
+        if (e->h_bresults) (void)hipHostFree(e->h_bresults);
+        e->d_bstates = nullptr; e->d_bresults = nullptr; e->h_bresults = nullptr;
+        e->batch_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_bstates, (size_t)n_envs * c.state_dim * sizeof(double)));
+        HIP_TRY(hipMalloc(&e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result)));
+        HIP_TRY(hipHostMalloc(&e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipHostMallocDefault));
+        e->batch_cap = n_envs;
+    }
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
+    const double* d_act = nullptr;
+    if (actions) {
+        const size_t n = (size_t)c.horizon * (size_t)c.num_paths * (size_t)c.action_dim;
+        if (n > e->actions_cap) {
+            if (e->d_actions) (void)hipFree(e->d_actions);
+            e->d_actions = nullptr;
+            e->actions_cap = 0;
+            HIP_TRY(hipMalloc(&e->d_actions, n * sizeof(double)));
+            e->actions_cap = n;
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_actions, actions, n * sizeof(double), hipMemcpyHostToDevice, st));
+        d_act = e->d_actions;
+    }
+    if (const int rc = batch_impl(e, e->d_bstates, n_envs, d_act, seed, cand_offset, e->d_costs, e->d_bresults, st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->h_bresults, e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
+    if (costs_out)
+        HIP_TRY(hipMemcpyAsync(costs_out, e->d_costs, sizeof(double) * c.num_paths, hipMemcpyDeviceToHost, st));
+    if (const int sr = sync_step(e, st)) return sr;
+    if (step_failed(e)) {                              // the team gave up: the whole batch on the fallback engine
+        bcmpc_engine* re = nullptr;
+        if (const int fr = rerun_engine(e, &re)) return fr;
+        return bcmpc_get_actions_batch(re, states, n_envs, actions, seed, cand_offset, out, costs_out);
+    }
+    std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
     return BCMPC_OK;
 }
 

@@ -206,4 +206,26 @@ hipError_t launch_argmin(const ArgminArgs& a, hipStream_t st);
 hipError_t launch_select(const SelectArgs& a, hipStream_t st);
 hipError_t launch_refit(const RefitArgs& a, hipStream_t st);
 
+// ---- batched control step (batch.hip): n_envs environments x K candidates per launch chain; candidate
+// column c = b * K + j belongs to environment b ----
+struct TileStatesArgs {                      // out[c][:] = states[c / K][:]
+    const double* states;                    // [n_envs][S]
+    double* out;                             // [Ktot][S]
+    int64_t K, Ktot;
+    int32_t S;
+};
+struct SegmentArgminArgs {                   // one np.argmin record per environment
+    const double* costs;                     // [n_envs * K]
+    const double* actions;                   // [H][n_envs * K][A] or nullptr => Philox
+    const double* consts;
+    bcmpc_result* out;                       // [n_envs]
+    uint64_t seed;
+    int64_t cand_offset;                     // Philox / global index of column 0
+    int64_t K;                               // candidates per environment
+    int32_t n_envs, A;
+    int32_t maximize;                        // np.argmax (learned reward)
+};
+hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);
+hipError_t launch_argmin_segments(const SegmentArgminArgs& a, hipStream_t st);
+
 }  // namespace bcmpc

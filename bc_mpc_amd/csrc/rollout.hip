@@ -317,24 +317,7 @@ __global__ __launch_bounds__(256) void rollout_fp32(const RolloutArgs a) {
 // contiguous chunks of the cost vector to one (cost, index) record per block,
 // argmin_final reduces the records and writes the result (index, cost, first
 // action).  better() is a total order (NaN first, then value, then lower index),
-// so the grouping cannot change the answer.
-__device__ __forceinline__ Best block_best(Best best, double* sc, int64_t* si) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Best o{__shfl_xor(best.c, off), __shfl_xor(best.i, off)};
-        if (better(o, best)) best = o;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { sc[wave] = best.c; si[wave] = best.i; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-            const Best o{sc[w], si[w]};
-            if (better(o, best)) best = o;
-        }
-    return best;                                   // valid in thread 0
-}
-
+// so the grouping cannot change the answer (block_best: argmin_common.h).
 __global__ __launch_bounds__(256) void argmin_partial(const ArgminArgs a) {
     __shared__ double sc[4];
     __shared__ int64_t si[4];

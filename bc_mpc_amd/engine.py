@@ -74,6 +74,15 @@ class StepResult:
     costs: Optional[np.ndarray] = None
 
 
+@dataclass
+class BatchResult:
+    """RolloutEngine.get_actions: one record per environment (B environments, K candidates each)."""
+    best_index: np.ndarray     # [B] int64, global candidate indices (cand_offset + b*K + j*)
+    best_cost: np.ndarray      # [B] f64
+    first_action: np.ndarray   # [B, A] f64
+    costs: Optional[np.ndarray] = None   # [B, K] f64
+
+
 def _f32(a) -> np.ndarray:
     if hasattr(a, "detach"):
         a = a.detach().cpu().numpy()
@@ -355,6 +364,59 @@ class RolloutEngine:
             ctypes.byref(res), _dp(costs) if costs is not None else None))
         return StepResult(int(res.best_index), float(res.best_cost),
                           np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
+
+    def _n_envs(self, n_envs: int) -> int:
+        n_envs = int(n_envs)
+        if n_envs < 1:
+            raise ValueError("the batched step needs at least one environment")
+        if self.num_paths % n_envs != 0:
+            raise ValueError(f"num_paths = {self.num_paths} is not a multiple of the {n_envs} environments")
+        return n_envs
+
+    def get_actions(self, states, actions: Optional[np.ndarray] = None, seed: int = 0,
+                    cand_offset: int = 0, return_costs: bool = False) -> BatchResult:
+        """Synchronous batched control step (bcmpc_get_actions_batch): ``states`` is ``[B, S]``, the
+        engine's ``num_paths`` candidates are split into B runs of ``K = num_paths // B``; candidate column
+        ``c = b*K + j`` belongs to environment ``b``, starts from ``states[b]`` and has the Philox index
+        ``cand_offset + c``.  Record ``b`` equals ``get_action(states[b], seed=seed, cand_offset=cand_offset
+        + b*K)`` of a K-candidate engine of the same kernel layout.  ``actions``: ``[H, num_paths, A]``
+        (the kernels' layout, columns as above) or None (device Philox)."""
+        st = _f64(states)
+        if st.ndim != 2 or st.shape[1] != self.state_dim:
+            raise ValueError(f"states shape {st.shape} != (B, S) = (B, {self.state_dim})")
+        B = self._n_envs(st.shape[0])
+        act_p = None
+        if actions is not None:
+            actions = _f64(actions)
+            if actions.shape != (self.horizon, self.num_paths, self.action_dim):
+                raise ValueError(f"actions shape {actions.shape} != (H, B*K, A) = "
+                                 f"{(self.horizon, self.num_paths, self.action_dim)}")
+            act_p = _dp(actions)
+        res = (_lib.Result * B)()
+        costs = np.empty(self.num_paths, dtype=np.float64) if return_costs else None
+        _lib.check(self._lib.bcmpc_get_actions_batch(
+            self._h, _dp(st), ctypes.c_int32(B), act_p, ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(cand_offset), res, _dp(costs) if costs is not None else None))
+        rec = np.frombuffer(res, dtype=np.float64).reshape(B, 2 + _lib.MAX_ACTION)
+        return BatchResult(rec[:, 0].copy().view(np.int64), rec[:, 1].copy(),
+                           rec[:, 2:2 + self.action_dim].copy(),
+                           costs.reshape(B, -1) if costs is not None else None)
+
+    def rollout_batch_async(self, d_states: int, n_envs: int, d_actions: Optional[int], seed: int,
+                            cand_offset: int, d_costs: int, d_results: int, stream: Optional[int] = None) -> None:
+        """Device-pointer form of get_actions (bcmpc_rollout_batch_async); no host synchronisation.
+        ``d_states`` ``[n_envs, S]`` f64, ``d_actions`` ``[H, num_paths, A]`` f64 or None, ``d_costs``
+        ``[num_paths]`` f64 (required), ``d_results`` ``n_envs`` result records; ``stream`` as rollout_async."""
+        n_envs = self._n_envs(n_envs)
+        if not d_states or not d_costs or not d_results:
+            raise ValueError("d_states, d_costs and d_results are required")
+        if stream is None:
+            stream = self.stream
+        _lib.check(self._lib.bcmpc_rollout_batch_async(
+            self._h, ctypes.c_void_p(d_states), ctypes.c_int32(n_envs),
+            ctypes.c_void_p(d_actions) if d_actions else None, ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(cand_offset), ctypes.c_void_p(d_costs), ctypes.c_void_p(d_results),
+            ctypes.c_void_p(stream)))
 
     def _numpy_bounds(self, low, high):
         """Per-action f64 bounds with a finite range (np.random.uniform would not raise), else None

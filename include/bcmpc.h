@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BCMPC_ABI_VERSION 4
+#define BCMPC_ABI_VERSION 5
 #define BCMPC_MAX_LAYERS 8      /* hidden layers supported (dynamics.py:66 n_layers) */
 #define BCMPC_MAX_STATE 32      /* S: observation dim (HalfCheetah: 20, cheetah_env.py:21-27) */
 #define BCMPC_MAX_INPUT 32      /* S + A (dynamics.py:26 concat) */
@@ -300,6 +300,39 @@ int bcmpc_rollout_async(bcmpc_engine* eng, const double* d_state, int64_t state_
                         const double* d_actions, uint64_t seed, int64_t cand_offset,
                         double* d_costs, double* d_traj, bcmpc_result* d_result, void* stream);
 
+/* Batched control step (ABI 5): n_envs environments per launch chain, K = num_paths / n_envs
+ * candidates each (num_paths % n_envs must be 0).  Candidate column c = b * K + j (0 <= j < K) belongs
+ * to environment b and starts from states[b]; its Philox index is cand_offset + c.  For every b,
+ *   out[b] == bcmpc_get_action(states[b], seed, cand_offset + b * K)
+ * of a K-candidate engine of the same kernel layout: best_index is global (cand_offset + b * K + j*,
+ * j* by np.argmin over the environment's K costs, np.argmax for BCMPC_COST_REWARD), best_cost that
+ * candidate's cost, first_action its step-0 action.
+ *   states    : host [n_envs][S] doubles
+ *   actions   : host [H][num_paths][A] doubles (column c as above), or NULL => device Philox
+ *   out       : host [n_envs] records
+ *   costs_out : optional host [num_paths] doubles (environment b's costs at [b * K, (b + 1) * K))
+ * One chain on the engine's stream: the states expanded to the candidates (tile_states), the rollout
+ * on per-candidate states, one argmin workgroup per environment (argmin_segments); the records come
+ * back in one device-to-host copy, one stream synchronisation.  A team-kernel engine whose team gave
+ * up reruns the call on its fallback engine, as bcmpc_get_action does.
+ * BCMPC_ERR_ARG: null pointers, n_envs < 1, num_paths % n_envs != 0, cost == BCMPC_COST_NONE.
+ * BCMPC_ERR_UNSUPPORTED (not batched yet): engines with a fused policy, engines with a communicator
+ * attached.  CEM has no batched form. */
+int bcmpc_get_actions_batch(bcmpc_engine* eng, const double* states, int32_t n_envs, const double* actions,
+                            uint64_t seed, int64_t cand_offset, bcmpc_result* out, double* costs_out);
+
+/* The same chain on device memory, stream-ordered, no host synchronisation:
+ *   d_states  : device [n_envs][S] doubles
+ *   d_actions : device [H][num_paths][A] doubles or NULL => device Philox
+ *   d_costs   : device [num_paths] doubles (required)
+ *   d_results : device [n_envs] records
+ *   stream    : as bcmpc_rollout_async
+ * Team-kernel engines: bcmpc_engine_status once the stream has completed, as for every
+ * stream-ordered launch. */
+int bcmpc_rollout_batch_async(bcmpc_engine* eng, const double* d_states, int32_t n_envs, const double* d_actions,
+                              uint64_t seed, int64_t cand_offset, double* d_costs, bcmpc_result* d_results,
+                              void* stream);
+
 /* MPCcontrollerPolicyNet engines: bcmpc_rollout_async plus the actions actually rolled out at
  * EVERY step -- d_actions_out [H, K, A] f64, the reference's action_paths (controllers.py:208-213:
  * the policy mean mixed with the exploration draw, or mean + exp(logstd) * N(0,1) when self_exp)
@@ -419,7 +452,7 @@ void* bcmpc_stream(bcmpc_engine* eng);
  * process or kernel holding CUs) gives up and flags it; the synchronous entry points then rerun the
  * call on a fallback engine of the same net (the split slab kernel, else the fp32 group kernel;
  * not with a communicator attached: BCMPC_ERR_HIP).  Stream-ordered callers (bcmpc_rollout_async,
- * bcmpc_rollout_policy_async, bcmpc_cem_rollout_async) call bcmpc_engine_status once their stream has
+ * bcmpc_rollout_batch_async, bcmpc_rollout_policy_async, bcmpc_cem_rollout_async) call bcmpc_engine_status once their stream has
  * completed: BCMPC_ERR_HIP when a launch of this engine since the last check gave up (its outputs
  * are not valid), BCMPC_OK otherwise; reading clears the flag.  Team launches of one process on
  * different streams of a device are serialised (stream-ordered) by the library. */
@@ -433,7 +466,8 @@ int bcmpc_engine_team_reruns(const bcmpc_engine* eng, uint64_t* reruns);
 int bcmpc_engine_set_timing(bcmpc_engine* eng, int32_t on);
 /* Timing of the last rollout kernel launched through bcmpc_get_action /
  * bcmpc_rollout_async / bcmpc_cem_get_action, in milliseconds (HIP events on the launch
- * stream); requires timing on for that launch (else BCMPC_ERR_ARG) and waits for it. */
+ * stream); requires timing on for that launch (else BCMPC_ERR_ARG) and waits for it.  After a
+ * batched call: rollout_ms = the state expansion + the rollout, argmin_ms = the per-environment argmin. */
 int bcmpc_last_kernel_ms(bcmpc_engine* eng, float* rollout_ms, float* argmin_ms);
 
 /* Static shape facts for tests: padded hidden size and packed weight bytes. */
