@@ -10,11 +10,12 @@ from . import _lib
 from .controllers import (Controller, MCTScontrollerPolicyNetReward, MPCcontroller, MPCcontrollerPolicyNet,
                           MPCcontrollerPolicyNetReward, MPCcontrollerReward, RandomController)
 from .cem import CEMcontroller
+from .mppi import MPPIcontroller
 from .cost_functions import cheetah_cost_fn, trajectory_cost_fn
 from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
-           "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
+           "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
            "trajectory_cost_fn", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

@@ -108,6 +108,24 @@ class Elite(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_double), ("index", ctypes.c_int64)]
 
 
+class Mppi(ctypes.Structure):
+    _fields_ = [
+        ("iterations", ctypes.c_int32),
+        ("lambda_", ctypes.c_double),          # bcmpc_mppi.lambda (the temperature)
+        ("k_global", ctypes.c_int64),
+    ]
+
+
+class MppiStats(ctypes.Structure):
+    """One MPPI update's statistics (bcmpc_mppi_stats); no valid candidate: 0, 0, NaN, 0."""
+    _fields_ = [
+        ("weight_sum", ctypes.c_double),
+        ("ess", ctypes.c_double),
+        ("min_cost", ctypes.c_double),
+        ("n_valid", ctypes.c_int64),
+    ]
+
+
 class Result(ctypes.Structure):
     _fields_ = [
         ("best_index", ctypes.c_int64),
@@ -181,6 +199,12 @@ SIGNATURES = [
     ("bcmpc_cem_refit_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_double,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_mppi_get_action", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result),
+      ctypes.POINTER(MppiStats)]),
+    ("bcmpc_mppi_update_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
+      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_stream", ctypes.c_void_p, [ctypes.c_void_p]),
     ("bcmpc_engine_status", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_engine_team_reruns", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),

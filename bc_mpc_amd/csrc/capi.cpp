@@ -263,6 +263,10 @@ struct bcmpc_engine {
     double* d_sigma = nullptr;
     bcmpc_elite* d_elite = nullptr; int32_t elite_cap = 0;
     int32_t* d_count = nullptr;
+    // MPPI (bcmpc_mppi_get_action / bcmpc_mppi_update_async): the update's scratch -- [256] minima,
+    // [256] counts, [H * A + 2][partials] -- grown on demand, and the synchronous call's statistics
+    double* d_mppi = nullptr; size_t mppi_cap = 0;
+    bcmpc_mppi_stats* d_mppi_stats = nullptr;
     double explore = 0.0;
     uint64_t pol_version = 0;
     bool has_policy = false;
@@ -691,7 +695,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
     for (void* p : {(void*)e->d_w, (void*)e->d_b, (void*)e->d_ln, (void*)e->d_consts, (void*)e->d_state,
                     (void*)e->d_actions, (void*)e->d_costs, (void*)e->d_result, (void*)e->d_pw, (void*)e->d_pb,
                     (void*)e->d_first, (void*)e->d_gpow, (void*)e->d_mu, (void*)e->d_sigma, (void*)e->d_elite,
-                    (void*)e->d_count, (void*)e->d_amin_c, (void*)e->d_amin_i,
+                    (void*)e->d_count, (void*)e->d_mppi, (void*)e->d_mppi_stats, (void*)e->d_amin_c, (void*)e->d_amin_i,
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults})
@@ -1578,6 +1582,42 @@ static int refit_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t
     r.elite = d_elite; r.count = d_count; r.mu = d_mu; r.sigma = d_sigma; r.consts = e->d_consts;
     r.seed = seed; r.iter = iter; r.H = e->cfg.horizon; r.A = e->cfg.action_dim; r.alpha = alpha;
     HIP_TRY(launch_refit(r, st));
+    return BCMPC_OK;
+}
+
+// one MPPI update on st (mppi.hip): the scratch is grown like cem_buffers grows the elite buffer
+static int mppi_update_impl(bcmpc_engine* e, const double* d_costs, int64_t m, int64_t cand_offset, uint64_t seed,
+                            int32_t iter, double lambda, double* d_mu, const double* d_sigma,
+                            bcmpc_mppi_stats* d_stats, hipStream_t st) {
+    if (!d_costs || !d_mu || !d_sigma || !d_stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (m < 1) return fail(BCMPC_ERR_ARG, "m must be >= 1");
+    if (iter < 0 || iter >= (1 << 22)) return fail(BCMPC_ERR_ARG, "iteration must be in [0, 2^22)");
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    // (the action bounds reach the device with the weights or with bcmpc_set_action_bounds)
+    if (!e->has_weights) return fail(BCMPC_ERR_STATE, "bcmpc_set_weights has not been called");
+    const int64_t parts = mppi_parts(m);
+    if (parts > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "m is too large for one update");
+    const size_t ha = (size_t)e->cfg.horizon * e->cfg.action_dim;
+    const size_t need = 2 * (size_t)kMppiMinParts + (ha + 2) * (size_t)parts;
+    if (need > e->mppi_cap) {
+        if (e->d_mppi) (void)hipFree(e->d_mppi);
+        e->d_mppi = nullptr;
+        e->mppi_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_mppi, need * sizeof(double)));
+        e->mppi_cap = need;
+    }
+    MppiArgs a{};
+    a.costs = d_costs; a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts;
+    a.pmin = e->d_mppi;
+    a.pcnt = reinterpret_cast<int64_t*>(e->d_mppi + kMppiMinParts);
+    a.part = e->d_mppi + 2 * kMppiMinParts;
+    a.stats = d_stats;
+    a.seed = seed; a.m = m; a.cand_offset = cand_offset; a.nparts = parts;
+    a.iter = iter; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.cpl = mppi_cpl(m); a.nmin = mppi_min_blocks(m);
+    a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    a.lambda = lambda;
+    HIP_TRY(launch_mppi_update(a, st));
     return BCMPC_OK;
 }
 
@@ -2622,6 +2662,70 @@ int bcmpc_cem_refit_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int
     if (!e) return fail(BCMPC_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(e->cfg.device));
     return refit_impl(e, d_elite, d_count, seed, iteration, alpha, d_mu, d_sigma, (hipStream_t)stream);
+}
+
+int bcmpc_mppi_get_action(bcmpc_engine* e, const double* state, const bcmpc_mppi* p, uint64_t seed, double* mu,
+                          const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    if (!e || !state || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    const bcmpc_config& c = e->cfg;
+    if (p->iterations < 1 || p->iterations > (1 << 22)) return fail(BCMPC_ERR_ARG, "iterations must be in [1, 2^22]");
+    if (!(std::isfinite(p->lambda) && p->lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (c.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "MPPI needs a fused objective");
+    if (p->k_global != 0 && p->k_global != c.num_paths)
+        return fail(BCMPC_ERR_ARG, "single-device MPPI: k_global must be 0 or num_paths");
+    if (c.num_paths == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    if (e->comm)
+        return fail(BCMPC_ERR_UNSUPPORTED, "MPPI with a communicator attached is not supported (the ranks' "
+                                           "(v_min, W, N) partials are not combined yet)");
+    if (e->PL > 0) return fail(BCMPC_ERR_UNSUPPORTED, "MPPI runs on engines without a fused policy");
+    HIP_TRY(hipSetDevice(c.device));
+    const SyncCall sync_guard(e);
+    int rc = cem_buffers(e, 0);                        // d_mu, d_sigma
+    if (rc != BCMPC_OK) return rc;
+    if (!e->d_mppi_stats) HIP_TRY(hipMalloc(&e->d_mppi_stats, sizeof(bcmpc_mppi_stats)));
+    const size_t ha = (size_t)c.horizon * c.action_dim;
+    hipStream_t st = e->stream;
+    std::vector<double> mu0;                           // (team engines: the input, for a rerun)
+    if (e->kernel == BCMPC_KERNEL_TEAM) mu0.assign(mu, mu + ha);
+    HIP_TRY(hipMemcpyAsync(e->d_state, state, sizeof(double) * c.state_dim, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_mu, mu, ha * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_sigma, sigma, ha * sizeof(double), hipMemcpyHostToDevice, st));
+    if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
+    for (int it = 0; it < p->iterations; ++it) {
+        const CemLaunch cl{e->d_mu, e->d_sigma, it, it > 0, (int64_t)it * c.num_paths};
+        rc = rollout_impl(e, e->d_state, 0, nullptr, seed, 0, e->d_costs, nullptr, e->d_result, st, &cl, false);
+        if (rc != BCMPC_OK) return rc;
+        rc = mppi_update_impl(e, e->d_costs, c.num_paths, 0, seed, it, p->lambda, e->d_mu, e->d_sigma,
+                              e->d_mppi_stats, st);
+        if (rc != BCMPC_OK) return rc;
+    }
+    if (e->timing) {
+        HIP_TRY(hipEventRecord(e->ev[1], st));
+        HIP_TRY(hipEventRecord(e->ev[2], st));
+    }
+    e->timed = e->timing;
+    HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mu, e->d_mu, ha * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stats, e->d_mppi_stats, sizeof(*stats), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (team_failed(e)) {
+        if (const int fr = team_fallback(e)) return fr;
+        std::memcpy(mu, mu0.data(), ha * sizeof(double));
+        return bcmpc_mppi_get_action(e->fb, state, p, seed, mu, sigma, out, stats);
+    }
+    *out = *e->h_result;
+    return BCMPC_OK;
+}
+
+int bcmpc_mppi_update_async(bcmpc_engine* e, const double* d_costs, int64_t m, int64_t cand_offset, uint64_t seed,
+                            int32_t iteration, double lambda, double* d_mu, const double* d_sigma,
+                            bcmpc_mppi_stats* d_stats, void* stream) {
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    // (arguments first: a bad call is answered before any HIP call)
+    if (!d_costs || !d_mu || !d_sigma || !d_stats) return fail(BCMPC_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return mppi_update_impl(e, d_costs, m, cand_offset, seed, iteration, lambda, d_mu, d_sigma, d_stats,
+                            (hipStream_t)stream);
 }
 
 int bcmpc_engine_set_comm(bcmpc_engine* e, bcmpc_comm* comm) {

@@ -127,6 +127,31 @@ struct RefitArgs {                           // per-(h, j) elite mean / std, smo
     int32_t iter, H, A;
     double alpha;
 };
+// ---- MPPI plan update (mppi.hip): softmin weights over all m candidates, weighted mean of their actions ----
+constexpr int kMppiWaves = 16;               // waves per stage-1 workgroup (they split the (h, j) pairs)
+constexpr int kMppiMaxCpl = 4;               // candidates per lane of a stage-1 workgroup: 1, or this beyond
+constexpr int64_t kMppiSmall = 16384;        //   kMppiSmall candidates (64 / 256 candidates per workgroup)
+constexpr int kMppiMinParts = 256;           // workgroups of the min reduction, at most
+struct MppiArgs {
+    const double* costs;                     // [m]
+    double* mu;                              // [H][A], in / out
+    const double* sigma;                     // [H][A]
+    const double* consts;                    // action bounds (rows 6, 7)
+    double* pmin;                            // [nmin] per-workgroup minimum of the finite scores (+inf: none)
+    int64_t* pcnt;                           // [nmin] ... and their count
+    double* part;                            // [H * A + 2][nparts]: N[h][j], then W, then sum w^2
+    bcmpc_mppi_stats* stats;
+    uint64_t seed;
+    int64_t m, cand_offset, nparts;
+    int32_t iter, H, A, cpl, nmin;
+    int32_t maximize;                        // learned reward: the score is -cost
+    double lambda;
+};
+int mppi_cpl(int64_t m);                     // candidates per lane stage 1 uses for m candidates
+int64_t mppi_parts(int64_t m);               // stage-1 workgroups (partials per value)
+int mppi_min_blocks(int64_t m);
+hipError_t launch_mppi_update(const MppiArgs& a, hipStream_t st);
+
 // ---- NumPy's legacy MT19937 stream drawn on the device (mt_device.hip) ----
 // One chunk = a contiguous range of the draw's generator words [s, s + n) (both even: whole
 // random_sample doubles), drawn by one workgroup starting from the 624-word window of stream block

@@ -612,6 +612,40 @@ class RolloutEngine:
             self._h, ctypes.c_void_p(d_elite), ctypes.c_void_p(d_count), ctypes.c_uint64(seed & (2**64 - 1)),
             int(iteration), float(alpha), ctypes.c_void_p(d_mu), ctypes.c_void_p(d_sigma), ctypes.c_void_p(stream)))
 
+    # ------------------------------------------------------------------ MPPI
+    def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
+                        seed: int) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
+        """``iterations`` rounds of CEM-style rollout + MPPI update on this device
+        (bcmpc_mppi_get_action; DESIGN.md "MPPI").  ``mu``/``sigma`` are ``[H, A]``; returns (the best
+        single candidate over all rounds, best_index = iteration*K + candidate; the updated plan mu',
+        whose row 0 is the action to apply; the last round's statistics).  sigma is not modified."""
+        st = _f64(state).reshape(-1)
+        if st.shape[0] != self.state_dim:
+            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
+        shape = (self.horizon, self.action_dim)
+        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
+        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
+        p = _lib.Mppi(int(iterations), float(temperature), 0)
+        res, stats = _lib.Result(), _lib.MppiStats()
+        _lib.check(self._lib.bcmpc_mppi_get_action(self._h, _dp(st), ctypes.byref(p),
+                                                   ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
+                                                   ctypes.byref(res), ctypes.byref(stats)))
+        return (StepResult(int(res.best_index), float(res.best_cost),
+                           np.array(res.first_action[: self.action_dim], dtype=np.float64)), m, stats)
+
+    def mppi_update_async(self, d_costs: int, m: int, cand_offset: int, seed: int, iteration: int,
+                          temperature: float, d_mu: int, d_sigma: int, d_stats: int,
+                          stream: Optional[int] = None) -> None:
+        """The MPPI update alone on device pointers (bcmpc_mppi_update_async): ``d_costs`` ``[m]`` f64 are
+        the costs of candidates ``cand_offset + [0, m)`` sampled at ``iteration`` from (``d_mu``,
+        ``d_sigma``) ``[H, A]``; ``d_mu`` is replaced by the weighted mean, ``d_stats`` receives one
+        ``_lib.MppiStats`` record.  ``m`` need not equal ``num_paths``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_update_async(
+            self._h, vp(d_costs), int(m), int(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)), int(iteration),
+            float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), ctypes.c_void_p(stream)))
+
     def set_comm(self, comm) -> None:
         """Attach a ``distributed.LibraryComm`` (None detaches): every get_action of this engine then
         exchanges the ranks' result records over RCCL inside the library and returns the GLOBAL best

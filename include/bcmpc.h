@@ -190,6 +190,25 @@ typedef struct bcmpc_elite {   /* one (cost, global candidate index) record; ind
     int64_t index;
 } bcmpc_elite;
 
+/* MPPI outer loop (model-predictive path integral control; not in the reference, semantics in
+ * DESIGN.md "MPPI").  An iteration samples and scores the candidates exactly like a CEM iteration,
+ * then replaces mu by the softmin-weighted mean of ALL candidates' actions: score v = cost (-cost
+ * for the learned reward), a candidate is valid iff v is finite, w = exp(-(v - v_min) / lambda)
+ * (0 when invalid), mu'[h][j] = sum w a[h][j] / sum w.  sigma is not modified.  Additive to ABI 5:
+ * callers detect it by the symbol bcmpc_mppi_get_action. */
+typedef struct bcmpc_mppi {
+    int32_t iterations;   /* rollout + update rounds (>= 1)                            */
+    double lambda;        /* temperature, finite and > 0                               */
+    int64_t k_global;     /* 0 or num_paths (single device)                            */
+} bcmpc_mppi;
+
+typedef struct bcmpc_mppi_stats {   /* of one update; no valid candidate: 0, 0, NaN, 0 */
+    double weight_sum;    /* W = sum w (>= 1: the best candidate has w = 1)            */
+    double ess;           /* effective sample size W^2 / sum w^2, in [1, n_valid]      */
+    double min_cost;      /* best valid cost (largest reward sum for the learned reward) */
+    int64_t n_valid;      /* candidates with a finite score                            */
+} bcmpc_mppi_stats;
+
 typedef struct bcmpc_engine bcmpc_engine;
 
 int bcmpc_abi_version(void);
@@ -365,6 +384,31 @@ int bcmpc_select_async(bcmpc_engine* eng, const bcmpc_elite* d_pairs, const doub
                        int64_t index_base, int32_t n_elite, bcmpc_elite* d_out, int32_t* d_count, void* stream);
 int bcmpc_cem_refit_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const int32_t* d_count, uint64_t seed,
                           int32_t iteration, double alpha, double* d_mu, double* d_sigma, void* stream);
+
+/* MPPI, single device, synchronous: `iterations` rounds of CEM-style rollout + update on the
+ * engine's stream, one host synchronisation.
+ *   mu    : host [H][A] doubles, in: the sampling mean, out: the updated plan (the action to apply is
+ *           mu[0] of the output)
+ *   sigma : host [H][A] doubles, the sampling std (read only)
+ *   out   : the best single candidate over all rounds (best_index = iteration * K + candidate), as CEM
+ *   stats : the last round's update statistics
+ * Engines as for bcmpc_cem_get_action; a team-kernel engine whose team gave up reruns the call on its
+ * fallback engine.  BCMPC_ERR_ARG: null pointers, iterations outside [1, 2^22], lambda not finite or
+ * <= 0, cost == BCMPC_COST_NONE, k_global not 0 / num_paths.  BCMPC_ERR_EMPTY: num_paths == 0.
+ * BCMPC_ERR_UNSUPPORTED: engines with a communicator attached, engines with a fused policy. */
+int bcmpc_mppi_get_action(bcmpc_engine* eng, const double* state, const bcmpc_mppi* params, uint64_t seed,
+                          double* mu, const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats);
+
+/* The update alone (device pointers, stream-ordered; next to bcmpc_cem_rollout_async, which leaves
+ * d_costs): d_costs [m] are the costs of candidates cand_offset + [0, m) sampled at `iteration` from
+ * (d_mu, d_sigma); d_mu [H][A] is replaced by the weighted mean (left alone when no cost is finite),
+ * d_stats receives the statistics.  m need not equal num_paths: the update uses the engine's H, A,
+ * action bounds and objective direction only.  The engine's scratch serves one update at a time:
+ * updates of one engine on different streams must be ordered by the caller.
+ * BCMPC_ERR_ARG: null pointers, m < 1, iteration outside [0, 2^22), lambda not finite or <= 0. */
+int bcmpc_mppi_update_async(bcmpc_engine* eng, const double* d_costs, int64_t m, int64_t cand_offset,
+                            uint64_t seed, int32_t iteration, double lambda, double* d_mu,
+                            const double* d_sigma, bcmpc_mppi_stats* d_stats, void* stream);
 
 /* ------------------------------------------------------------------------
  * NNDynamicsModel.fit (dynamics.py:81-104) on the GPU:
