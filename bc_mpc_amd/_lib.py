@@ -205,6 +205,29 @@ SIGNATURES = [
     ("bcmpc_mppi_update_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
       ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_cem_get_actions_batch", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Cem), ctypes.c_uint64, ctypes.c_int64, _DP, _DP,
+      ctypes.POINTER(Result), _DP]),
+    ("bcmpc_mppi_get_actions_batch", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Mppi), ctypes.c_uint64, ctypes.c_int64, _DP, _DP,
+      ctypes.POINTER(Result), ctypes.POINTER(MppiStats), _DP]),
+    ("bcmpc_plan_sample_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_plan_argmin_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_select_batch_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_cem_refit_batch_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+      ctypes.c_int64, ctypes.c_void_p]),
+    ("bcmpc_mppi_update_batch_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p]),
     ("bcmpc_stream", ctypes.c_void_p, [ctypes.c_void_p]),
     ("bcmpc_engine_status", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_engine_team_reruns", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),

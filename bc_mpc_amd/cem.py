@@ -20,6 +20,10 @@ all-gather their local top-E (cost, index) records (E x 16 bytes each), every
 rank selects the same global top-E from the gathered records and refits the
 same mu / sigma by regenerating the elites' actions from Philox -- no second
 collective.  One final all-gather min-loc picks the answer.
+
+Many environments per call (one rank): ``get_actions(states[B, S])`` runs B independent CEM
+problems, one warm-start plan per environment, in one ``bcmpc_cem_get_actions_batch`` call
+(DESIGN.md 9e).
 """
 from __future__ import annotations
 
@@ -33,14 +37,14 @@ import numpy as np
 from . import _lib
 from . import distributed as _dist
 from . import weights as _weights
-from .controllers import Controller, _check_model, _default_device
+from .controllers import Controller, _BatchPlans, _check_model, _default_device
 from .cost_functions import is_cheetah_cost
 from .engine import RolloutEngine
 
 _ELITE_BYTES = ctypes.sizeof(_lib.Elite)
 
 
-class CEMcontroller(Controller):
+class CEMcontroller(_BatchPlans, Controller):
     """Cross-entropy-method MPC on the MI355X engine (BASELINE cfg5 CEM outer loop)."""
 
     def __init__(self,
@@ -91,9 +95,12 @@ class CEMcontroller(Controller):
             return int(self._n_elite)
         return max(1, int(round(self.elite_frac * int(self.num_simulated_paths))))
 
-    def reset(self) -> None:
-        """Forget the warm-start mean (call at episode boundaries)."""
-        self._mu = None
+    def reset(self, env_ids=None) -> None:
+        """Forget the warm-start mean (call at episode boundaries).  ``env_ids``: forget only those
+        environments' plans of ``get_actions`` (an episode boundary in one simulator of a batch)."""
+        if env_ids is None:
+            self._mu = None
+        self._reset_plans(env_ids)
 
     def _bounds(self):
         return (np.asarray(self.env.action_space.low, dtype=np.float64),
@@ -166,6 +173,37 @@ class CEMcontroller(Controller):
         self.last_mu, self.last_sigma = mu, sd
         self.last_cost, self.last_position = cost, pos
         return first
+
+    def get_actions(self, states):
+        """Batched control step: ``states`` is ``[B, S]``, one independent CEM answer per row with
+        ``num_simulated_paths`` candidates and ``n_elite`` elites each, all environments in one launch
+        chain (``RolloutEngine.cem_get_actions``).  Every environment keeps its own warm-start plan (see
+        ``reset``); one seed is drawn per call.  Returns ``[B, A]`` float64: each environment's best
+        sample's first action.  ``last_mu`` / ``last_sigma`` (``[B, H, A]``), ``last_cost`` /
+        ``last_position`` (``[B]``) describe the call.  One rank only."""
+        S = int(math.prod(self.env.observation_space.shape))
+        A = len(self.env.action_space.high)
+        K = int(self.num_simulated_paths)
+        if self.horizon < 1:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        states = self._plan_states(states, S)
+        if K == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        spec, norm, version = _weights.extract(self.dyn_model)
+        if spec.model != "reward":
+            _check_model(spec, "delta", type(self).__name__)
+            if not is_cheetah_cost(self.cost_fn, S, A):
+                raise ValueError("CEMcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
+        B = states.shape[0]
+        mu0, sd0 = self.batch_initial_distribution(B)
+        seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
+        eng = self._batch_engine_for(spec, S, A, B * K)
+        eng.set_weights(spec, norm, version)
+        res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        self._store_plans(mu)
+        self.last_mu, self.last_sigma = mu, sd
+        self.last_cost, self.last_position = res.best_cost, res.best_index
+        return res.first_action
 
 
 class _EngineShard:

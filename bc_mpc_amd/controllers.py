@@ -145,6 +145,70 @@ def _batch_states(states, S: int, group) -> np.ndarray:
     return states
 
 
+class _BatchPlans:
+    """The batched planners' host state (CEMcontroller / MPPIcontroller ``get_actions``): one warm-start
+    plan per environment and the B*K-candidate engine, kept next to ``get_action``'s own plan and engine.
+    The host class provides ``env``, ``horizon``, ``gamma``, ``init_std``, ``warm_start``, ``_device``,
+    ``_group`` and ``_bounds()``."""
+    _bmu = None             # [B, H, A]: the last batched call's plans
+    _bkeep = None           # [B] bool: plan b is shifted and reused (False after reset([b]))
+    _batch_engine = None
+    _batch_key = None
+    _batch_gamma = None
+
+    def _reset_plans(self, env_ids) -> None:
+        if env_ids is None:
+            self._bmu = self._bkeep = None
+        elif self._bmu is not None:
+            self._bkeep[np.asarray(env_ids, dtype=np.int64).reshape(-1)] = False
+
+    def batch_initial_distribution(self, n_envs: int):
+        """``initial_distribution()`` per environment, ``[B, H, A]`` each: plan b of the last batched call
+        shifted by one step with the box centre appended, or the box centre in every step where there is
+        none (first call, after ``reset``, B changed, ``warm_start=False``)."""
+        low, high = self._bounds()
+        H, B = int(self.horizon), int(n_envs)
+        mid = (low + high) / 2.0
+        sd = np.full_like(low, self.init_std) if self.init_std is not None else (high - low) / 4.0
+        mu = np.tile(mid, (B, H, 1))
+        if self.warm_start and self._bmu is not None and self._bmu.shape == mu.shape:
+            mu[self._bkeep, :-1] = self._bmu[self._bkeep, 1:]
+        return mu, np.tile(sd, (B, H, 1))
+
+    def _store_plans(self, mu: np.ndarray) -> None:
+        self._bmu = mu
+        self._bkeep = np.ones(mu.shape[0], dtype=bool)
+
+    def _plan_states(self, states, S: int) -> np.ndarray:
+        _, ws = _dist.world(self._group)
+        if ws > 1:
+            raise NotImplementedError(f"{type(self).__name__}.get_actions runs on one rank (world size {ws}): "
+                                      "the batched planners do not shard their candidates")
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != S or states.shape[0] < 1:
+            raise ValueError(f"states shape {states.shape} != (B, S) = (B >= 1, {S})")
+        return states
+
+    def _batch_engine_for(self, spec, S: int, A: int, k_total: int) -> RolloutEngine:
+        dev = _default_device() if self._device is None else self._device
+        key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
+               int(k_total), dev)
+        if self._batch_engine is None or self._batch_key != key:
+            if self._batch_engine is not None:
+                self._batch_engine.close()
+            reward = spec.model == "reward"
+            self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
+                                               int(self.horizon), int(k_total), device=dev,
+                                               cost="reward" if reward else "cheetah", model=spec.model)
+            self._batch_engine.set_action_bounds(*self._bounds())
+            self._batch_key = key
+            self._batch_gamma = None
+        if spec.model == "reward" and self._batch_gamma != float(self.gamma):
+            self._batch_engine.set_discount(float(self.gamma))
+            self._batch_gamma = float(self.gamma)
+        return self._batch_engine
+
+
 class MPCcontroller(Controller):
     """Random-shooting MPC (controllers.py:26-88) on the MI355X rollout engine."""
 

@@ -227,6 +227,13 @@ struct bcmpc_engine {
     bcmpc_result* d_bresults = nullptr; // [batch_cap] records
     bcmpc_result* h_bresults = nullptr; // pinned mirror
     int32_t batch_cap = 0;              // environments d_bstates / d_bresults / h_bresults hold
+    // batched CEM / MPPI (bcmpc_cem_get_actions_batch / bcmpc_mppi_get_actions_batch, plan_batch.hip)
+    double* d_bmu = nullptr;            // [plan_cap][H][A] the environments' plans
+    double* d_bsigma = nullptr;
+    int32_t* d_bcount = nullptr;        // [plan_cap] elites selected
+    bcmpc_mppi_stats* d_bstats = nullptr;   // [plan_cap]
+    int32_t plan_cap = 0;
+    bcmpc_elite* d_belite = nullptr; size_t belite_cap = 0;   // [n_envs][n_elite] records
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;
     int team_kind = 0;                  // 0 plain delta net, 1 + policy, 2 reward net (+ policy)
@@ -698,7 +705,8 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_count, (void*)e->d_mppi, (void*)e->d_mppi_stats, (void*)e->d_amin_c, (void*)e->d_amin_i,
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
-                    (void*)e->d_bstates, (void*)e->d_bresults})
+                    (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
+                    (void*)e->d_bstats, (void*)e->d_belite})
         if (p) (void)hipFree(p);
     if (e->h_bresults) (void)hipHostFree(e->h_bresults);
     if (e->h_result) (void)hipHostFree(e->h_result);
@@ -1711,6 +1719,32 @@ static int batch_check(const bcmpc_engine* e, int32_t n_envs) {
     return BCMPC_OK;
 }
 
+// the synchronous batched calls' buffers, grown on demand: the environments' states and records ...
+static int batch_buffers(bcmpc_engine* e, int32_t n_envs) {
+    if (n_envs <= e->batch_cap) return BCMPC_OK;
+    for (void* p : {(void*)e->d_bstates, (void*)e->d_bresults})
+        if (p) (void)hipFree(p);
+    if (e->h_bresults) (void)hipHostFree(e->h_bresults);
+    e->d_bstates = nullptr; e->d_bresults = nullptr; e->h_bresults = nullptr;
+    e->batch_cap = 0;
+    HIP_TRY(hipMalloc(&e->d_bstates, (size_t)n_envs * e->cfg.state_dim * sizeof(double)));
+    HIP_TRY(hipMalloc(&e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result)));
+    HIP_TRY(hipHostMalloc(&e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipHostMallocDefault));
+    e->batch_cap = n_envs;
+    return BCMPC_OK;
+}
+
+// ... and the explicit action array d_actions, n doubles
+static int actions_buffer(bcmpc_engine* e, size_t n) {
+    if (n <= e->actions_cap) return BCMPC_OK;
+    if (e->d_actions) (void)hipFree(e->d_actions);
+    e->d_actions = nullptr;
+    e->actions_cap = 0;
+    HIP_TRY(hipMalloc(&e->d_actions, n * sizeof(double)));
+    e->actions_cap = n;
+    return BCMPC_OK;
+}
+
 // tile_states -> rollout (per-candidate states, no argmin) -> argmin_segments, all on st
 static int batch_impl(bcmpc_engine* e, const double* d_states, int32_t n_envs, const double* d_actions,
                       uint64_t seed, int64_t cand_offset, double* d_costs, bcmpc_result* d_results,
@@ -1753,29 +1787,13 @@ int bcmpc_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_env
     const bcmpc_config& c = e->cfg;
     HIP_TRY(hipSetDevice(c.device));
     const SyncCall sync_guard(e);
-    if (n_envs > e->batch_cap) {
-        for (void* p : {(void*)e->d_bstates, (void*)e->d_bresults})
-            if (p) (void)hipFree(p);
-        if (e->h_bresults) (void)hipHostFree(e->h_bresults);
-        e->d_bstates = nullptr; e->d_bresults = nullptr; e->h_bresults = nullptr;
-        e->batch_cap = 0;
-        HIP_TRY(hipMalloc(&e->d_bstates, (size_t)n_envs * c.state_dim * sizeof(double)));
-        HIP_TRY(hipMalloc(&e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result)));
-        HIP_TRY(hipHostMalloc(&e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipHostMallocDefault));
-        e->batch_cap = n_envs;
-    }
+    if (const int rc = batch_buffers(e, n_envs)) return rc;
     hipStream_t st = e->stream;
     HIP_TRY(hipMemcpyAsync(e->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
     const double* d_act = nullptr;
     if (actions) {
         const size_t n = (size_t)c.horizon * (size_t)c.num_paths * (size_t)c.action_dim;
-        if (n > e->actions_cap) {
-            if (e->d_actions) (void)hipFree(e->d_actions);
-            e->d_actions = nullptr;
-            e->actions_cap = 0;
-            HIP_TRY(hipMalloc(&e->d_actions, n * sizeof(double)));
-            e->actions_cap = n;
-        }
+        if (const int rc = actions_buffer(e, n)) return rc;
         HIP_TRY(hipMemcpyAsync(e->d_actions, actions, n * sizeof(double), hipMemcpyHostToDevice, st));
         d_act = e->d_actions;
     }
@@ -2726,6 +2744,286 @@ int bcmpc_mppi_update_async(bcmpc_engine* e, const double* d_costs, int64_t m, i
     HIP_TRY(hipSetDevice(e->cfg.device));
     return mppi_update_impl(e, d_costs, m, cand_offset, seed, iteration, lambda, d_mu, d_sigma, d_stats,
                             (hipStream_t)stream);
+}
+
+// ---- batched CEM / MPPI: n_envs plans per launch chain (plan_batch.hip) ----------------------
+// The rollout kernels take one sampling distribution per launch, so the iteration's actions are
+// materialised from the n_envs plans (plan_sample) and rolled out as an explicit action array by the
+// batched chain; the outer-loop kernels run once per iteration with the environment as a grid index.
+static int plan_block_check(const bcmpc_engine* e, int32_t n_envs, int64_t K, int32_t iteration) {
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (K < 1) return fail(BCMPC_ERR_ARG, "K (candidates per environment) must be >= 1");
+    if (iteration < 0 || iteration >= (1 << 22)) return fail(BCMPC_ERR_ARG, "iteration must be in [0, 2^22)");
+    // (the action bounds reach the device with the weights or with bcmpc_set_action_bounds)
+    if (!e->has_weights) return fail(BCMPC_ERR_STATE, "bcmpc_set_weights has not been called");
+    return BCMPC_OK;
+}
+
+static int plan_sample_impl(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                            uint64_t seed, int32_t iteration, int64_t cand_offset, double* d_actions, hipStream_t st) {
+    PlanSampleArgs a{};
+    a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts; a.out = d_actions;
+    a.seed = seed; a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
+    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    HIP_TRY(launch_plan_sample(a, st));
+    return BCMPC_OK;
+}
+
+static int plan_argmin_impl(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs, int64_t K,
+                            int32_t iteration, int32_t merge, bcmpc_result* d_results, hipStream_t st) {
+    PlanArgminArgs a{};
+    a.costs = d_costs; a.actions = d_actions; a.consts = e->d_consts; a.out = d_results;
+    a.K = K; a.n_envs = n_envs; a.A = e->cfg.action_dim; a.iter = iteration; a.merge = merge != 0;
+    a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    HIP_TRY(launch_plan_argmin(a, st));
+    return BCMPC_OK;
+}
+
+static int select_batch_impl(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K, int64_t index_base,
+                             int32_t n_elite, bcmpc_elite* d_out, int32_t* d_count, hipStream_t st) {
+    SelectBatchArgs a{};
+    a.one.costs = d_costs; a.one.m = K; a.one.index_base = index_base; a.one.n_elite = n_elite;
+    a.one.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    a.one.out = d_out; a.one.count = d_count;
+    a.n_envs = n_envs;
+    HIP_TRY(launch_select_batch(a, st));
+    return BCMPC_OK;
+}
+
+// d_actions (optional): the iteration's stored actions [H][n_envs * K][A], column 0 = candidate cand_offset
+static int refit_batch_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, int32_t n_envs,
+                            int32_t n_elite, uint64_t seed, int32_t iteration, double alpha, double* d_mu,
+                            double* d_sigma, const double* d_actions, int64_t K, int64_t cand_offset, hipStream_t st) {
+    RefitBatchArgs a{};
+    a.one.elite = d_elite; a.one.count = d_count; a.one.mu = d_mu; a.one.sigma = d_sigma; a.one.consts = e->d_consts;
+    a.one.seed = seed; a.one.iter = iteration; a.one.H = e->cfg.horizon; a.one.A = e->cfg.action_dim;
+    a.one.alpha = alpha;
+    a.one.actions = d_actions; a.one.act_cols = d_actions ? K * n_envs : 0; a.one.act_g0 = cand_offset;
+    a.n_envs = n_envs; a.n_elite = n_elite;
+    HIP_TRY(launch_refit_batch(a, st));
+    return BCMPC_OK;
+}
+
+static int mppi_update_batch_impl(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K,
+                                  int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda, double* d_mu,
+                                  const double* d_sigma, bcmpc_mppi_stats* d_stats, const double* d_actions,
+                                  hipStream_t st) {
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    const int64_t parts = mppi_parts(K);
+    if (parts * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one update");
+    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+    const size_t need = mppi_batch_scratch(K, n_envs, ha);
+    if (need > e->mppi_cap) {
+        if (e->d_mppi) (void)hipFree(e->d_mppi);
+        e->d_mppi = nullptr;
+        e->mppi_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_mppi, need * sizeof(double)));
+        e->mppi_cap = need;
+    }
+    MppiBatchArgs b{};
+    MppiArgs& a = b.one;
+    a.costs = d_costs; a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts;
+    a.pmin = e->d_mppi;
+    a.pcnt = reinterpret_cast<int64_t*>(e->d_mppi + (size_t)n_envs * kMppiMinParts);
+    a.part = e->d_mppi + 2 * (size_t)n_envs * kMppiMinParts;
+    a.stats = d_stats;
+    a.seed = seed; a.m = K; a.cand_offset = cand_offset; a.nparts = parts;
+    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.cpl = mppi_cpl(K); a.nmin = mppi_min_blocks(K);          // (the workgroup size rule follows K, not n_envs * K)
+    a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    a.lambda = lambda;
+    a.actions = d_actions; a.act_cols = d_actions ? K * n_envs : 0; a.act_g0 = cand_offset;
+    b.n_envs = n_envs;
+    HIP_TRY(launch_mppi_update_batch(b, st));
+    return BCMPC_OK;
+}
+
+int bcmpc_plan_sample_async(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                            uint64_t seed, int32_t iteration, int64_t cand_offset, double* d_actions, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_mu || !d_sigma || !d_actions) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_sample_impl(e, d_mu, d_sigma, n_envs, K, seed, iteration, cand_offset, d_actions, (hipStream_t)stream);
+}
+
+int bcmpc_plan_argmin_async(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs, int64_t K,
+                            int32_t iteration, int32_t merge, bcmpc_result* d_results, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_actions || !d_results) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    if (e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "argmin needs the fused cost");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_argmin_impl(e, d_costs, d_actions, n_envs, K, iteration, merge, d_results, (hipStream_t)stream);
+}
+
+int bcmpc_select_batch_async(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K, int64_t index_base,
+                             int32_t n_elite, bcmpc_elite* d_out, int32_t* d_count, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_out || !d_count) return fail(BCMPC_ERR_ARG, "null argument");
+    if (n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return select_batch_impl(e, d_costs, n_envs, K, index_base, n_elite, d_out, d_count, (hipStream_t)stream);
+}
+
+int bcmpc_cem_refit_batch_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, int32_t n_envs,
+                                int32_t n_elite, uint64_t seed, int32_t iteration, double alpha, double* d_mu,
+                                double* d_sigma, const double* d_actions, int64_t K, int64_t cand_offset,
+                                void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_elite || !d_count || !d_mu || !d_sigma) return fail(BCMPC_ERR_ARG, "null argument");
+    if (n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, d_actions ? K : 1, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return refit_batch_impl(e, d_elite, d_count, n_envs, n_elite, seed, iteration, alpha, d_mu, d_sigma, d_actions, K,
+                            cand_offset, (hipStream_t)stream);
+}
+
+int bcmpc_mppi_update_batch_async(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K,
+                                  int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda, double* d_mu,
+                                  const double* d_sigma, bcmpc_mppi_stats* d_stats, const double* d_actions,
+                                  void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_mu || !d_sigma || !d_stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return mppi_update_batch_impl(e, d_costs, n_envs, K, cand_offset, seed, iteration, lambda, d_mu, d_sigma, d_stats,
+                                  d_actions, (hipStream_t)stream);
+}
+
+// the synchronous calls' device buffers: plans, counts and statistics per environment, the elite records
+static int plan_buffers(bcmpc_engine* e, int32_t n_envs, size_t n_elite_total) {
+    const size_t ha = (size_t)e->cfg.horizon * e->cfg.action_dim;
+    if (n_envs > e->plan_cap) {
+        for (void* p : {(void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount, (void*)e->d_bstats})
+            if (p) (void)hipFree(p);
+        e->d_bmu = e->d_bsigma = nullptr; e->d_bcount = nullptr; e->d_bstats = nullptr;
+        e->plan_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_bmu, (size_t)n_envs * ha * sizeof(double)));
+        HIP_TRY(hipMalloc(&e->d_bsigma, (size_t)n_envs * ha * sizeof(double)));
+        HIP_TRY(hipMalloc(&e->d_bcount, (size_t)n_envs * sizeof(int32_t)));
+        HIP_TRY(hipMalloc(&e->d_bstats, (size_t)n_envs * sizeof(bcmpc_mppi_stats)));
+        e->plan_cap = n_envs;
+    }
+    if (n_elite_total > e->belite_cap) {
+        if (e->d_belite) (void)hipFree(e->d_belite);
+        e->d_belite = nullptr;
+        e->belite_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_belite, n_elite_total * sizeof(bcmpc_elite)));
+        e->belite_cap = n_elite_total;
+    }
+    return BCMPC_OK;
+}
+
+// The synchronous batched planner: states and plans up, tile_states once, then per iteration plan_sample ->
+// rollout (explicit actions, per-candidate states) -> plan_argmin -> the planner's update; records and
+// plans down, one stream synchronisation.  cem != nullptr: CEM, else MPPI (mp).
+static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* cem,
+                            const bcmpc_mppi* mp, uint64_t seed, int64_t cand_offset, double* mu, double* sigma_io,
+                            const double* sigma_in, bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out) {
+    const bcmpc_config& c = e->cfg;
+    const int32_t iterations = cem ? cem->iterations : mp->iterations;
+    const int64_t K = c.num_paths / n_envs;
+    HIP_TRY(hipSetDevice(c.device));
+    const SyncCall sync_guard(e);
+    const size_t ha = (size_t)c.horizon * c.action_dim, nplan = (size_t)n_envs * ha;
+    if (const int rc = batch_buffers(e, n_envs)) return rc;
+    if (const int rc = plan_buffers(e, n_envs, cem ? (size_t)n_envs * cem->n_elite : 0)) return rc;
+    if (const int rc = actions_buffer(e, (size_t)c.horizon * (size_t)c.num_paths * (size_t)c.action_dim)) return rc;
+    if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
+    const double* sigma = cem ? sigma_io : sigma_in;
+    std::vector<double> mu0, sigma0;                   // (team engines: the inputs, for a rerun)
+    if (e->kernel == BCMPC_KERNEL_TEAM) {
+        mu0.assign(mu, mu + nplan);
+        if (cem) sigma0.assign(sigma, sigma + nplan);
+    }
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_bmu, mu, nplan * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_bsigma, sigma, nplan * sizeof(double), hipMemcpyHostToDevice, st));
+    if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
+    TileStatesArgs t{};
+    t.states = e->d_bstates; t.out = e->d_tiled; t.K = K; t.Ktot = c.num_paths; t.S = c.state_dim;
+    HIP_TRY(launch_tile_states(t, st));
+    for (int it = 0; it < iterations; ++it) {
+        int rc = plan_sample_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset, e->d_actions, st);
+        if (rc != BCMPC_OK) return rc;
+        rc = rollout_impl(e, e->d_tiled, c.state_dim, e->d_actions, seed, cand_offset, e->d_costs, nullptr, nullptr, st,
+                          nullptr, false);
+        if (rc != BCMPC_OK) return rc;
+        if (costs_out)
+            HIP_TRY(hipMemcpyAsync(costs_out + (size_t)it * c.num_paths, e->d_costs, sizeof(double) * c.num_paths,
+                                   hipMemcpyDeviceToHost, st));
+        // the record before the update, and before the next plan_sample overwrites the array it reads
+        rc = plan_argmin_impl(e, e->d_costs, e->d_actions, n_envs, K, it, it > 0, e->d_bresults, st);
+        if (rc != BCMPC_OK) return rc;
+        if (cem) {
+            rc = select_batch_impl(e, e->d_costs, n_envs, K, cand_offset, cem->n_elite, e->d_belite, e->d_bcount, st);
+            if (rc != BCMPC_OK) return rc;
+            rc = refit_batch_impl(e, e->d_belite, e->d_bcount, n_envs, cem->n_elite, seed, it, cem->alpha, e->d_bmu,
+                                  e->d_bsigma, e->d_actions, K, cand_offset, st);
+        } else {
+            rc = mppi_update_batch_impl(e, e->d_costs, n_envs, K, cand_offset, seed, it, mp->lambda, e->d_bmu,
+                                        e->d_bsigma, e->d_bstats, e->d_actions, st);
+        }
+        if (rc != BCMPC_OK) return rc;
+    }
+    if (e->timing) {
+        HIP_TRY(hipEventRecord(e->ev[1], st));
+        HIP_TRY(hipEventRecord(e->ev[2], st));
+    }
+    e->timed = e->timing;
+    HIP_TRY(hipMemcpyAsync(e->h_bresults, e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mu, e->d_bmu, nplan * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (cem) HIP_TRY(hipMemcpyAsync(sigma_io, e->d_bsigma, nplan * sizeof(double), hipMemcpyDeviceToHost, st));
+    else HIP_TRY(hipMemcpyAsync(stats, e->d_bstats, (size_t)n_envs * sizeof(bcmpc_mppi_stats), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (team_failed(e)) {                              // the whole call again, from the original plans
+        if (const int fr = team_fallback(e)) return fr;
+        std::memcpy(mu, mu0.data(), nplan * sizeof(double));
+        if (cem) std::memcpy(sigma_io, sigma0.data(), nplan * sizeof(double));
+        return plan_get_actions(e->fb, states, n_envs, cem, mp, seed, cand_offset, mu, sigma_io, sigma_in, out, stats,
+                                costs_out);
+    }
+    std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
+    return BCMPC_OK;
+}
+
+int bcmpc_cem_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                                uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                double* costs_out) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (p->iterations < 1 || p->iterations > (1 << 22)) return fail(BCMPC_ERR_ARG, "iterations must be in [1, 2^22]");
+    if (p->n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    if (p->k_global != 0 && p->k_global != e->cfg.num_paths / n_envs)
+        return fail(BCMPC_ERR_ARG, "batched CEM: k_global must be 0 or num_paths / n_envs");
+    return plan_get_actions(e, states, n_envs, p, nullptr, seed, cand_offset, mu, sigma, nullptr, out, nullptr,
+                            costs_out);
+}
+
+int bcmpc_mppi_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                                 uint64_t seed, int64_t cand_offset, double* mu, const double* sigma, bcmpc_result* out,
+                                 bcmpc_mppi_stats* stats, double* costs_out) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (p->iterations < 1 || p->iterations > (1 << 22)) return fail(BCMPC_ERR_ARG, "iterations must be in [1, 2^22]");
+    if (!(std::isfinite(p->lambda) && p->lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    if (p->k_global != 0 && p->k_global != e->cfg.num_paths / n_envs)
+        return fail(BCMPC_ERR_ARG, "batched MPPI: k_global must be 0 or num_paths / n_envs");
+    return plan_get_actions(e, states, n_envs, nullptr, p, seed, cand_offset, mu, nullptr, sigma, out, stats,
+                            costs_out);
 }
 
 int bcmpc_engine_set_comm(bcmpc_engine* e, bcmpc_comm* comm) {

@@ -126,6 +126,10 @@ struct RefitArgs {                           // per-(h, j) elite mean / std, smo
     uint64_t seed;
     int32_t iter, H, A;
     double alpha;
+    // (plan_batch.hip) the iteration's materialised actions [H][act_cols][A], column = index - act_g0, read
+    // instead of regenerating them; nullptr / outside the array: Philox (the same bits either way)
+    const double* actions;
+    int64_t act_cols, act_g0;
 };
 // ---- MPPI plan update (mppi.hip): softmin weights over all m candidates, weighted mean of their actions ----
 constexpr int kMppiWaves = 16;               // waves per stage-1 workgroup (they split the (h, j) pairs)
@@ -146,6 +150,8 @@ struct MppiArgs {
     int32_t iter, H, A, cpl, nmin;
     int32_t maximize;                        // learned reward: the score is -cost
     double lambda;
+    const double* actions;                   // (plan_batch.hip) as RefitArgs::actions: column = candidate - act_g0
+    int64_t act_cols, act_g0;
 };
 int mppi_cpl(int64_t m);                     // candidates per lane stage 1 uses for m candidates
 int64_t mppi_parts(int64_t m);               // stage-1 workgroups (partials per value)
@@ -252,5 +258,45 @@ struct SegmentArgminArgs {                   // one np.argmin record per environ
 };
 hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);
 hipError_t launch_argmin_segments(const SegmentArgminArgs& a, hipStream_t st);
+
+// ---- batched CEM / MPPI (plan_batch.hip): one plan, elite set and weighted mean per environment; the
+// columns are laid out as above, environment b's arrays follow environment b - 1's ----
+struct PlanSampleArgs {                      // out[h][c][j] = cem_action(seed, cand_offset + c, h, j, iter,
+    const double* mu;                        //                           mu[c / K][h][j], sigma[c / K][h][j], ..)
+    const double* sigma;                     // [n_envs][H][A] each
+    const double* consts;
+    double* out;                             // [H][Ktot][A]
+    uint64_t seed;
+    int64_t cand_offset, K, Ktot;
+    int32_t iter, H, A;
+};
+struct PlanArgminArgs {                      // the running best of every environment (ArgminArgs::merge's rule)
+    const double* costs;                     // [n_envs * K] this iteration's costs
+    const double* actions;                   // [H][n_envs * K][A] this iteration's actions (step 0 is read)
+    const double* consts;
+    bcmpc_result* out;                       // [n_envs]: best_index = iter * K + j, environment-local
+    int64_t K;
+    int32_t n_envs, A, iter;
+    int32_t merge;                           // keep out[b] unless this iteration's best is strictly better
+    int32_t maximize;
+};
+struct SelectBatchArgs {                     // environment b: SelectArgs{costs + b K, m = K, index_base + b K,
+    SelectArgs one;                          //                out + b n_elite, count + b} (one: environment 0's)
+    int32_t n_envs;
+};
+struct RefitBatchArgs {                      // environment b: elite + b n_elite, count + b, mu / sigma + b H A
+    RefitArgs one;
+    int32_t n_envs, n_elite;
+};
+struct MppiBatchArgs {                       // environment b: costs + b K, mu / sigma + b H A, stats + b,
+    MppiArgs one;                            // cand_offset + b K, pmin / pcnt + b kMppiMinParts,
+    int32_t n_envs;                          // part + b (H A + 2) nparts; m = K sets cpl, nparts, nmin
+};
+size_t mppi_batch_scratch(int64_t K, int32_t n_envs, int32_t HA);   // doubles: [B][256] [B][256] [B][HA + 2][parts]
+hipError_t launch_plan_sample(const PlanSampleArgs& a, hipStream_t st);
+hipError_t launch_plan_argmin(const PlanArgminArgs& a, hipStream_t st);
+hipError_t launch_select_batch(const SelectBatchArgs& a, hipStream_t st);
+hipError_t launch_refit_batch(const RefitBatchArgs& a, hipStream_t st);
+hipError_t launch_mppi_update_batch(const MppiBatchArgs& a, hipStream_t st);
 
 }  // namespace bcmpc

@@ -80,7 +80,11 @@ class BatchResult:
     best_index: np.ndarray     # [B] int64, global candidate indices (cand_offset + b*K + j*)
     best_cost: np.ndarray      # [B] f64
     first_action: np.ndarray   # [B, A] f64
-    costs: Optional[np.ndarray] = None   # [B, K] f64
+    costs: Optional[np.ndarray] = None   # [B, K] f64 (cem_get_actions / mppi_get_actions: [iterations, B, K])
+
+
+# bcmpc_mppi_stats as a NumPy record (mppi_get_actions returns one per environment)
+MPPI_STATS = np.dtype([("weight_sum", "<f8"), ("ess", "<f8"), ("min_cost", "<f8"), ("n_valid", "<i8")])
 
 
 def _f32(a) -> np.ndarray:
@@ -645,6 +649,111 @@ class RolloutEngine:
         _lib.check(self._lib.bcmpc_mppi_update_async(
             self._h, vp(d_costs), int(m), int(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)), int(iteration),
             float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), ctypes.c_void_p(stream)))
+
+    # ------------------------------------------------------------------ batched CEM / MPPI
+    def _plan_batch_args(self, states, mu, sigma, copy_sigma: bool):
+        st = _f64(states)
+        if st.ndim != 2 or st.shape[1] != self.state_dim:
+            raise ValueError(f"states shape {st.shape} != (B, S) = (B, {self.state_dim})")
+        B = self._n_envs(st.shape[0])
+        shape = (B, self.horizon, self.action_dim)
+        if np.shape(mu) != shape or np.shape(sigma) != shape:
+            raise ValueError(f"mu / sigma shapes {np.shape(mu)} / {np.shape(sigma)} != (B, H, A) = {shape}")
+        m = np.array(mu, dtype=np.float64, copy=True, order="C")
+        s = (np.array(sigma, dtype=np.float64, copy=True, order="C") if copy_sigma
+             else np.ascontiguousarray(sigma, dtype=np.float64))
+        return st, B, m, s
+
+    def _batch_result(self, res, B: int, costs, iterations: int) -> BatchResult:
+        rec = np.frombuffer(res, dtype=np.float64).reshape(B, 2 + _lib.MAX_ACTION)
+        return BatchResult(rec[:, 0].copy().view(np.int64), rec[:, 1].copy(), rec[:, 2:2 + self.action_dim].copy(),
+                           costs.reshape(iterations, B, -1) if costs is not None else None)
+
+    def cem_get_actions(self, states, mu, sigma, iterations: int, n_elite: int, alpha: float, seed: int,
+                        cand_offset: int = 0, return_costs: bool = False
+                        ) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+        """Batched CEM (bcmpc_cem_get_actions_batch): ``states`` ``[B, S]``, ``mu`` / ``sigma``
+        ``[B, H, A]``, ``K = num_paths // B`` candidates and ``n_elite`` elites per environment, columns
+        as for get_actions.  Returns (records with ``best_index = iteration*K + candidate`` per
+        environment and ``costs`` ``[iterations, B, K]`` when asked for, mu' ``[B, H, A]``, sigma')."""
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, True)
+        p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
+        res = (_lib.Result * B)()
+        costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
+        _lib.check(self._lib.bcmpc_cem_get_actions_batch(
+            self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, _dp(costs) if costs is not None else None))
+        return self._batch_result(res, B, costs, int(iterations)), m, s
+
+    def mppi_get_actions(self, states, mu, sigma, iterations: int, temperature: float, seed: int,
+                         cand_offset: int = 0, return_costs: bool = False
+                         ) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+        """Batched MPPI (bcmpc_mppi_get_actions_batch): as cem_get_actions, with the softmin update of
+        mppi_get_action per environment.  Returns (records, mu' ``[B, H, A]`` whose rows ``[b, 0]`` are the
+        actions to apply, the last round's statistics as a ``[B]`` array of MPPI_STATS).  sigma is not
+        modified."""
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, False)
+        p = _lib.Mppi(int(iterations), float(temperature), 0)
+        res = (_lib.Result * B)()
+        stats = np.zeros(B, dtype=MPPI_STATS)
+        costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
+        _lib.check(self._lib.bcmpc_mppi_get_actions_batch(
+            self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(cand_offset), _dp(m), _dp(s), res,
+            stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None))
+        return self._batch_result(res, B, costs, int(iterations)), m, stats
+
+    def plan_sample_async(self, d_mu: int, d_sigma: int, n_envs: int, K: int, seed: int, iteration: int,
+                          cand_offset: int, d_actions: int, stream: Optional[int] = None) -> None:
+        """bcmpc_plan_sample_async: ``d_actions`` ``[H, n_envs*K, A]`` f64 from the plans ``d_mu`` /
+        ``d_sigma`` ``[n_envs, H, A]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_sample_async(
+            self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), int(cand_offset), vp(d_actions), ctypes.c_void_p(stream)))
+
+    def plan_argmin_async(self, d_costs: int, d_actions: int, n_envs: int, K: int, iteration: int, merge: bool,
+                          d_results: int, stream: Optional[int] = None) -> None:
+        """bcmpc_plan_argmin_async: every environment's running best into ``d_results`` (n_envs records)."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_argmin_async(
+            self._h, vp(d_costs), vp(d_actions), int(n_envs), int(K), int(iteration), int(bool(merge)),
+            vp(d_results), ctypes.c_void_p(stream)))
+
+    def select_batch_async(self, d_costs: int, n_envs: int, K: int, index_base: int, n_elite: int, d_out: int,
+                           d_count: int, stream: Optional[int] = None) -> None:
+        """bcmpc_select_batch_async: ``d_out`` ``[n_envs, n_elite]`` elite records, ``d_count`` ``[n_envs]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_select_batch_async(
+            self._h, vp(d_costs), int(n_envs), int(K), int(index_base), int(n_elite), vp(d_out), vp(d_count),
+            ctypes.c_void_p(stream)))
+
+    def cem_refit_batch_async(self, d_elite: int, d_count: int, n_envs: int, n_elite: int, seed: int, iteration: int,
+                              alpha: float, d_mu: int, d_sigma: int, d_actions: Optional[int] = None, K: int = 0,
+                              cand_offset: int = 0, stream: Optional[int] = None) -> None:
+        """bcmpc_cem_refit_batch_async; ``d_actions`` (with ``K``, ``cand_offset``): read the iteration's
+        stored samples instead of regenerating them."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_cem_refit_batch_async(
+            self._h, vp(d_elite), vp(d_count), int(n_envs), int(n_elite), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), float(alpha), vp(d_mu), vp(d_sigma), vp(d_actions), int(K), int(cand_offset),
+            ctypes.c_void_p(stream)))
+
+    def mppi_update_batch_async(self, d_costs: int, n_envs: int, K: int, cand_offset: int, seed: int, iteration: int,
+                                temperature: float, d_mu: int, d_sigma: int, d_stats: int,
+                                d_actions: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_update_batch_async: mppi_update_async per environment at ``m = K``; ``d_stats`` holds
+        ``n_envs`` MPPI_STATS records."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_update_batch_async(
+            self._h, vp(d_costs), int(n_envs), int(K), int(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), vp(d_actions),
+            ctypes.c_void_p(stream)))
 
     def set_comm(self, comm) -> None:
         """Attach a ``distributed.LibraryComm`` (None detaches): every get_action of this engine then

@@ -19,6 +19,9 @@ Not included: MPPI's control-cost term ``lambda * u^T Sigma^-1 eps`` and a sigma
 Single GPU only: one ``bcmpc_mppi_get_action`` call (all rounds stream-ordered on the device,
 one host sync).  With more than one rank the per-rank ``(v_min, W, N)`` partials would have to be
 combined; that is not built yet and ``get_action`` raises NotImplementedError.
+
+Many environments per call: ``get_actions(states[B, S])`` runs B independent MPPI problems, one
+warm-start plan per environment, in one ``bcmpc_mppi_get_actions_batch`` call.
 """
 from __future__ import annotations
 
@@ -29,12 +32,12 @@ import numpy as np
 
 from . import distributed as _dist
 from . import weights as _weights
-from .controllers import Controller, _check_model, _default_device
+from .controllers import Controller, _BatchPlans, _check_model, _default_device
 from .cost_functions import is_cheetah_cost
 from .engine import RolloutEngine
 
 
-class MPPIcontroller(Controller):
+class MPPIcontroller(_BatchPlans, Controller):
     """MPPI on the MI355X engine: softmin-weighted plan update over all sampled candidates."""
 
     def __init__(self,
@@ -79,9 +82,12 @@ class MPPIcontroller(Controller):
         self.last_ess = None
         self.last_stats = None
 
-    def reset(self) -> None:
-        """Forget the warm-start plan (call at episode boundaries)."""
-        self._mu = None
+    def reset(self, env_ids=None) -> None:
+        """Forget the warm-start plan (call at episode boundaries).  ``env_ids``: forget only those
+        environments' plans of ``get_actions`` (an episode boundary in one simulator of a batch)."""
+        if env_ids is None:
+            self._mu = None
+        self._reset_plans(env_ids)
 
     def _bounds(self):
         return (np.asarray(self.env.action_space.low, dtype=np.float64),
@@ -148,3 +154,35 @@ class MPPIcontroller(Controller):
         self.last_cost, self.last_position = res.best_cost, res.best_index
         self.last_ess, self.last_stats = float(stats.ess), stats
         return mu[0].copy()
+
+    def get_actions(self, states):
+        """Batched control step: ``states`` is ``[B, S]``, one independent MPPI answer per row with
+        ``num_simulated_paths`` candidates each, all environments in one launch chain
+        (``RolloutEngine.mppi_get_actions``).  Every environment keeps its own warm-start plan (see
+        ``reset``); one seed is drawn per call.  Returns ``[B, A]`` float64: ``mu'[b, 0]``.  ``last_mu``
+        (``[B, H, A]``), ``last_ess`` / ``last_cost`` / ``last_position`` (``[B]``) and ``last_stats`` (a
+        ``[B]`` record array) describe the call.  One rank only."""
+        S = int(math.prod(self.env.observation_space.shape))
+        A = len(self.env.action_space.high)
+        K = int(self.num_simulated_paths)
+        if self.horizon < 1:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        states = self._plan_states(states, S)
+        if K == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        spec, norm, version = _weights.extract(self.dyn_model)
+        if spec.model != "reward":
+            _check_model(spec, "delta", type(self).__name__)
+            if not is_cheetah_cost(self.cost_fn, S, A):
+                raise ValueError("MPPIcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
+        B = states.shape[0]
+        mu0, sd0 = self.batch_initial_distribution(B)
+        seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
+        eng = self._batch_engine_for(spec, S, A, B * K)
+        eng.set_weights(spec, norm, version)
+        res, mu, stats = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed)
+        self._store_plans(mu)
+        self.last_mu = mu
+        self.last_cost, self.last_position = res.best_cost, res.best_index
+        self.last_ess, self.last_stats = stats["ess"].copy(), stats
+        return mu[:, 0].copy()

@@ -336,7 +336,7 @@ int bcmpc_rollout_async(bcmpc_engine* eng, const double* d_state, int64_t state_
  * up reruns the call on its fallback engine, as bcmpc_get_action does.
  * BCMPC_ERR_ARG: null pointers, n_envs < 1, num_paths % n_envs != 0, cost == BCMPC_COST_NONE.
  * BCMPC_ERR_UNSUPPORTED (not batched yet): engines with a fused policy, engines with a communicator
- * attached.  CEM has no batched form. */
+ * attached.  CEM and MPPI: bcmpc_cem_get_actions_batch / bcmpc_mppi_get_actions_batch below. */
 int bcmpc_get_actions_batch(bcmpc_engine* eng, const double* states, int32_t n_envs, const double* actions,
                             uint64_t seed, int64_t cand_offset, bcmpc_result* out, double* costs_out);
 
@@ -409,6 +409,77 @@ int bcmpc_mppi_get_action(bcmpc_engine* eng, const double* state, const bcmpc_mp
 int bcmpc_mppi_update_async(bcmpc_engine* eng, const double* d_costs, int64_t m, int64_t cand_offset,
                             uint64_t seed, int32_t iteration, double lambda, double* d_mu,
                             const double* d_sigma, bcmpc_mppi_stats* d_stats, void* stream);
+
+/* Batched CEM and MPPI (additive to ABI 5; callers detect them by the symbol
+ * bcmpc_cem_get_actions_batch): n_envs environments per launch chain, K = num_paths / n_envs candidates
+ * each, columns as for bcmpc_get_actions_batch (column c = b * K + j belongs to environment b, starts
+ * from states[b], Philox index cand_offset + c).  Environment b samples from its own plan mu[b],
+ * sigma[b] and gets its own elite set or softmin weights, updated plan, record and statistics.  With
+ * off_b = cand_offset + b * K, for every b and iteration `it`:
+ *   costs   == bcmpc_cem_rollout_async(states[b], mu_b, sigma_b, seed, it, off_b, ..) of a K-candidate
+ *              engine of the same kernel layout, bit for bit
+ *   elites  == bcmpc_select_async(costs_b, K, index_base = off_b, n_elite)
+ *   CEM     mu_b', sigma_b' == bcmpc_cem_refit_async on those elites
+ *   MPPI    mu_b', stats[b] == bcmpc_mppi_update_async(costs_b, K, off_b, seed, it, lambda, ..)
+ *   out[b]  np.argmin (np.argmax for BCMPC_COST_REWARD) over environment b's iteration-major
+ *           concatenated costs: best_index = it * K + j (environment-local, as the single calls report
+ *           it), best_cost, first_action that sample's step-0 action
+ * and with n_envs == 1, cand_offset == 0 the call equals bcmpc_cem_get_action / bcmpc_mppi_get_action.
+ * The rollout kernels are not told about the plans: each iteration's actions [H][num_paths][A] are
+ * written by a sampling kernel (the values the rollout kernels would draw) and rolled out as an
+ * explicit action array, so the solo layout works here too.
+ *   states    : host [n_envs][S]
+ *   mu, sigma : host [n_envs][H][A]; mu in/out; sigma in/out (CEM) or in (MPPI)
+ *   params    : n_elite is per environment; k_global is 0 or K
+ *   out       : host [n_envs] records;  stats: host [n_envs], the last iteration's
+ *   costs_out : optional host [iterations][num_paths]
+ * BCMPC_ERR_ARG: null pointers, n_envs < 1, num_paths % n_envs != 0, iterations outside [1, 2^22],
+ * n_elite < 1, lambda not finite or <= 0, k_global, cost == BCMPC_COST_NONE.  BCMPC_ERR_UNSUPPORTED:
+ * engines with a fused policy, engines with a communicator attached.  BCMPC_ERR_EMPTY: num_paths == 0.
+ * A team-kernel engine whose team gave up reruns the whole call on its fallback engine from the
+ * original mu / sigma. */
+int bcmpc_cem_get_actions_batch(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_cem* params,
+                                uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                double* costs_out);
+int bcmpc_mppi_get_actions_batch(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_mppi* params,
+                                 uint64_t seed, int64_t cand_offset, double* mu, const double* sigma,
+                                 bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out);
+
+/* The batched planners' building blocks (device pointers, stream-ordered, no host synchronisation).
+ * n_envs and K are explicit: only plan_sample's output has to fit a rollout; the others use the
+ * engine's H, A, action bounds and objective direction only, so n_envs * K need not be num_paths.
+ *   plan_sample  d_actions[h][c][j] (f64 [H][n_envs * K][A]) = the CEM sample of candidate
+ *                cand_offset + c at `iteration` from d_mu / d_sigma [n_envs][H][A], plan c / K; roll it
+ *                out with bcmpc_rollout_batch_async or bcmpc_rollout_async (state_stride == S)
+ *   plan_argmin  environment b's best of d_costs[b * K .. (b + 1) * K) into d_results[b] (best_index =
+ *                iteration * K + j, first_action read from d_actions' step 0), merged (merge != 0) with
+ *                the running best already there; before the next plan_sample overwrites d_actions
+ *   select_batch bcmpc_select_async per environment on costs (index = index_base + b * K + j):
+ *                d_out [n_envs][n_elite] in ascending index, padded with index -1; d_count [n_envs]
+ *   cem_refit_batch   bcmpc_cem_refit_async per environment: d_elite [n_envs][n_elite], d_count
+ *                [n_envs], d_mu / d_sigma [n_envs][H][A] in place
+ *   mppi_update_batch bcmpc_mppi_update_async per environment at m = K (its workgroup size rule and
+ *                summation order follow K, not n_envs * K): d_costs [n_envs * K], d_mu [n_envs][H][A]
+ *                in place, d_sigma read, d_stats [n_envs]; the engine's scratch serves one update at a time
+ * d_actions of the refit and the update is optional: the array plan_sample wrote for this iteration
+ * ([H][n_envs * K][A], column 0 = candidate cand_offset) is then read instead of regenerating the
+ * samples from Philox -- the same bits (NULL: regenerate; K and cand_offset of the refit are then unused).
+ * BCMPC_ERR_ARG: null pointers, n_envs < 1, K < 1, n_elite < 1, iteration outside [0, 2^22), lambda.
+ * Team-kernel engines: bcmpc_engine_status after the rollout's stream has completed, as always. */
+int bcmpc_plan_sample_async(bcmpc_engine* eng, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                            uint64_t seed, int32_t iteration, int64_t cand_offset, double* d_actions, void* stream);
+int bcmpc_plan_argmin_async(bcmpc_engine* eng, const double* d_costs, const double* d_actions, int32_t n_envs,
+                            int64_t K, int32_t iteration, int32_t merge, bcmpc_result* d_results, void* stream);
+int bcmpc_select_batch_async(bcmpc_engine* eng, const double* d_costs, int32_t n_envs, int64_t K, int64_t index_base,
+                             int32_t n_elite, bcmpc_elite* d_out, int32_t* d_count, void* stream);
+int bcmpc_cem_refit_batch_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const int32_t* d_count, int32_t n_envs,
+                                int32_t n_elite, uint64_t seed, int32_t iteration, double alpha, double* d_mu,
+                                double* d_sigma, const double* d_actions, int64_t K, int64_t cand_offset,
+                                void* stream);
+int bcmpc_mppi_update_batch_async(bcmpc_engine* eng, const double* d_costs, int32_t n_envs, int64_t K,
+                                  int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda, double* d_mu,
+                                  const double* d_sigma, bcmpc_mppi_stats* d_stats, const double* d_actions,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------
  * NNDynamicsModel.fit (dynamics.py:81-104) on the GPU:
