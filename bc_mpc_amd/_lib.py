@@ -238,6 +238,7 @@ SIGNATURES = [
      [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     ("bcmpc_fit_create", ctypes.c_int, [ctypes.POINTER(FitConfig), ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_fit_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_fit_is_fused", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_fit_set_params", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Weights)]),
     ("bcmpc_fit_get_params", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(_FP), ctypes.POINTER(_FP), ctypes.POINTER(_FP), ctypes.POINTER(_FP)]),

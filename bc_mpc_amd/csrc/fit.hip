@@ -942,7 +942,8 @@ struct bcmpc_fitter {
     float* d_bp = nullptr;                        // [beta1_power, beta2_power] (device)
     float* d_cpart = nullptr;                     // column-sum chunk partials [kColChunks][2][max width]
     unsigned* d_tickets = nullptr;                // column-sum completion tickets (one per 64 columns)
-    // one captured graph of a whole uniform-batch run, reused while its shape and buffers match
+    // one captured graph of a whole uniform-batch run, reused while its shape and buffers match (index and
+    // loss buffers: the reuse key; the data / reward buffers: fit_drop_graph where they are reallocated)
     hipGraphExec_t graph = nullptr;
     int32_t graph_iters = 0, graph_b = 0;
     const void* graph_idx = nullptr;
@@ -966,9 +967,19 @@ struct bcmpc_fitter {
     int32_t last_iters = 0;                       // iterations of the last run (its reward losses in d_loss2)
 };
 
+// The captured graph holds the data buffers' addresses in its kernel arguments (fit_gather,
+// fit_gather_reward, FusedArgs.st/ac/de): a buffer that moves ends the graph's life.  (No run is in
+// flight here: bcmpc_fit_run synchronises the stream before it returns.)
+static void fit_drop_graph(bcmpc_fitter* f) {
+    if (f->graph) (void)hipGraphExecDestroy(f->graph);
+    f->graph = nullptr;
+}
+
 extern "C" {
 
 const char* bcmpc_fit_last_error(void) { return g_fit_error.c_str(); }
+
+int bcmpc_fit_is_fused(const bcmpc_fitter* f) { return f && f->fused ? 1 : 0; }
 
 int bcmpc_fit_create(const bcmpc_fit_config* c, bcmpc_fitter** out) {
     if (!c || !out) return ffail(BCMPC_ERR_ARG, "null argument");
@@ -1168,6 +1179,7 @@ int bcmpc_fit_set_data(bcmpc_fitter* f, const double* states, const double* acti
     if (!f || (n > 0 && (!states || !actions || !deltas)) || n < 0) return ffail(BCMPC_ERR_ARG, "bad argument");
     if (hipSetDevice(f->cfg.device) != hipSuccess) return ffail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > f->data_cap) {
+        fit_drop_graph(f);
         for (double** p : {&f->d_st, &f->d_ac, &f->d_de})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         f->data_cap = 0;
@@ -1472,6 +1484,7 @@ int bcmpc_fit_set_rewards(bcmpc_fitter* f, const double* rewards, int64_t n) {
     if (n != f->n_data) return ffail(BCMPC_ERR_ARG, "rewards: one per row of bcmpc_fit_set_data");
     if (hipSetDevice(f->cfg.device) != hipSuccess) return ffail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > f->rw_cap) {
+        fit_drop_graph(f);
         if (f->d_rwd) (void)hipFree(f->d_rwd);
         f->d_rwd = nullptr;
         f->rw_cap = 0;

@@ -58,6 +58,11 @@ class GPUFitter:
         self.layer_norm = bool(layer_norm)
         self.batch_size = batch_size
 
+    @property
+    def fused(self) -> bool:
+        """True: the fused two-launch step; False: the per-op kernels (bcmpc_fit_is_fused)."""
+        return bool(self._lib.bcmpc_fit_is_fused(self._h))
+
     def set_params(self, spec: MLPSpec, normalization: Sequence) -> None:
         ks = [_f32(k) for k in spec.kernels]
         bs = [_f32(b) for b in spec.biases]

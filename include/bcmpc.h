@@ -509,6 +509,9 @@ typedef struct bcmpc_fitter bcmpc_fitter;
 
 int bcmpc_fit_create(const bcmpc_fit_config* cfg, bcmpc_fitter** out);
 int bcmpc_fit_destroy(bcmpc_fitter* f);
+/* 1: the fused two-launch step (fit_rows_kernel + fit_params_kernel); 0: the per-op kernels (the reward
+ * model, BCMPC_FIT_FUSED=0, or a net whose row block does not fit the LDS).  Additive to ABI 5. */
+int bcmpc_fit_is_fused(const bcmpc_fitter* f);
 /* parameters (TF layout [in, out] kernels, biases, LN gamma/beta) + the normalization stats */
 int bcmpc_fit_set_params(bcmpc_fitter* f, const bcmpc_weights* w);
 int bcmpc_fit_get_params(bcmpc_fitter* f, float* const* kernels, float* const* biases, float* const* ln_gamma,

@@ -798,9 +798,11 @@ class AdamState:
     beta2_power: np.float32
 
     @classmethod
-    def zeros_like(cls, params: Sequence[np.ndarray], beta1=0.9, beta2=0.999) -> "AdamState":
-        return cls([np.zeros_like(p, dtype=np.float32) for p in params],
-                   [np.zeros_like(p, dtype=np.float32) for p in params], np.float32(beta1), np.float32(beta2))
+    def zeros_like(cls, params: Sequence[np.ndarray], beta1=0.9, beta2=0.999, dtype=np.float32) -> "AdamState":
+        """``dtype`` float64: the slots and beta powers of the f64 reference trajectory (fit's ``dtype``)."""
+        return cls([np.zeros_like(p, dtype=dtype) for p in params],
+                   [np.zeros_like(p, dtype=dtype) for p in params], dtype(np.float32(beta1)),
+                   dtype(np.float32(beta2)))
 
 
 def fit_params(w: MLPWeights) -> List[np.ndarray]:
@@ -834,15 +836,21 @@ def fit_batch(normalization, states, actions, deltas):
 
 
 def fit_grads(ps: Sequence[np.ndarray], L: int, act: str, ln: bool, x0: np.ndarray, t: np.ndarray,
-              dtype=np.float32):
+              dtype=np.float32, bwd_kernels=None, trace=None):
     """Loss and d(loss)/d(params) for one batch (f32 throughout, TF op semantics; ``dtype``
-    float64 only for the finite-difference check of the restated derivatives)."""
+    float64 for the finite-difference check of the restated derivatives and for the f64 reference
+    trajectory).  ``bwd_kernels``: the kernels the data gradients dH_l = dZ_{l+1} W_{l+1}^T read (default:
+    the forward's; the fused GPU step reads a transposed copy, whose staleness a test must be able to
+    model).  ``trace``: a list that receives every layer's pre-activation Z_l."""
     f32 = dtype
     ks, bs, gs, bes = _split_params(ps, L, ln)
+    kb = ks if bwd_kernels is None else bwd_kernels
     hs, As, means, rss = [x0], [], [], []
     h = x0
     for l in range(L):
         z = h @ ks[l] + bs[l]
+        if trace is not None:
+            trace.append(z)
         a = (np.tanh(z) if act == "tanh" else np.maximum(z, f32(0))).astype(f32)
         As.append(a)
         if ln:
@@ -867,7 +875,7 @@ def fit_grads(ps: Sequence[np.ndarray], L: int, act: str, ln: bool, x0: np.ndarr
     gbe = [None] * L if ln else None
     gk[L] = hs[L].T @ dp
     gb[L] = np.sum(dp, axis=0, dtype=f32)
-    dh = dp @ ks[L].T
+    dh = dp @ kb[L].T
     for l in range(L - 1, -1, -1):
         a = As[l]
         if ln:
@@ -888,7 +896,7 @@ def fit_grads(ps: Sequence[np.ndarray], L: int, act: str, ln: bool, x0: np.ndarr
         gk[l] = hs[l].T @ dz
         gb[l] = np.sum(dz, axis=0, dtype=f32)
         if l > 0:
-            dh = dz @ ks[l].T
+            dh = dz @ kb[l].T
     grads = []
     for l in range(L + 1):
         grads += [gk[l].astype(f32), gb[l].astype(f32)]
@@ -899,11 +907,13 @@ def fit_grads(ps: Sequence[np.ndarray], L: int, act: str, ln: bool, x0: np.ndarr
 
 
 def adam_apply(ps: List[np.ndarray], grads: Sequence[np.ndarray], st: AdamState, lr: float,
-               beta1=0.9, beta2=0.999, eps=1e-8) -> None:
+               beta1=0.9, beta2=0.999, eps=1e-8, dtype=np.float32) -> None:
     """TF1 ApplyAdam (training_ops.cc): lr_t = lr*sqrt(1-b2^t)/(1-b1^t) from the f32 beta
     powers; m += (g-m)(1-b1); v += (g^2-v)(1-b2); w -= (m lr_t)/(sqrt(v)+eps); then the
-    powers are multiplied by beta (AdamOptimizer._finish)."""
-    f32 = np.float32
+    powers are multiplied by beta (AdamOptimizer._finish).  ``dtype`` float64: the same step on
+    f64 parameters, slots and beta powers (the hyperparameters still the f32-rounded ones)."""
+    f32 = dtype
+    beta1, beta2, lr, eps = (np.float32(x) for x in (beta1, beta2, lr, eps))
     b1, b2 = f32(beta1), f32(beta2)
     lr_t = f32(lr) * np.sqrt(f32(1) - st.beta2_power) / (f32(1) - st.beta1_power)
     for i, g in enumerate(grads):
@@ -915,13 +925,17 @@ def adam_apply(ps: List[np.ndarray], grads: Sequence[np.ndarray], st: AdamState,
 
 
 def fit(ps: List[np.ndarray], st: AdamState, L: int, act: str, ln: bool, normalization, data_states,
-        data_actions, data_deltas, batches: Sequence[np.ndarray], lr: float):
-    """dynamics.py:81-104 over explicit batch index lists; returns the per-step losses."""
+        data_actions, data_deltas, batches: Sequence[np.ndarray], lr: float, beta1=0.9, beta2=0.999, eps=1e-8,
+        dtype=np.float32, trace=None):
+    """dynamics.py:81-104 over explicit batch index lists; returns the per-step losses.
+    ``dtype`` float64 (with f64 ``ps`` and ``AdamState.zeros_like(.., dtype=np.float64)``): the
+    high-precision reference trajectory -- the same steps on the same f32-rounded batches (fit_batch),
+    widened, with f64 parameters, Adam slots and beta powers.  ``trace``: see fit_grads."""
     losses = []
     for idx in batches:
         x0, t = fit_batch(normalization, data_states[idx], data_actions[idx], data_deltas[idx])
-        loss, grads = fit_grads(ps, L, act, ln, x0, t)
-        adam_apply(ps, grads, st, lr)
+        loss, grads = fit_grads(ps, L, act, ln, x0.astype(dtype), t.astype(dtype), dtype=dtype, trace=trace)
+        adam_apply(ps, grads, st, lr, beta1, beta2, eps, dtype=dtype)
         losses.append(loss)
     return losses
 
@@ -1034,13 +1048,15 @@ def fit_reward_grads(ps: Sequence[np.ndarray], ln: bool, x0: np.ndarray, t: np.n
 
 
 def fit_reward(ps: List[np.ndarray], st: AdamState, ln: bool, normalization, data_states, data_actions,
-               data_rewards, data_deltas, batches: Sequence[np.ndarray], lr: float):
-    """dynamics.py:195-219 over explicit batch index lists; returns the per-step (model_loss, reward_loss)."""
+               data_rewards, data_deltas, batches: Sequence[np.ndarray], lr: float, beta1=0.9, beta2=0.999,
+               eps=1e-8, dtype=np.float32):
+    """dynamics.py:195-219 over explicit batch index lists; returns the per-step (model_loss, reward_loss).
+    ``dtype`` float64: the f64 reference trajectory, as fit's."""
     out = []
     for idx in batches:
         x0, t, r = fit_reward_batch(normalization, data_states[idx], data_actions[idx], data_rewards[idx],
                                     data_deltas[idx])
-        ld, lr_, grads = fit_reward_grads(ps, ln, x0, t, r)
-        adam_apply(ps, grads, st, lr)
+        ld, lr_, grads = fit_reward_grads(ps, ln, x0.astype(dtype), t.astype(dtype), r.astype(dtype), dtype=dtype)
+        adam_apply(ps, grads, st, lr, beta1, beta2, eps, dtype=dtype)
         out.append((ld, lr_))
     return out

@@ -24,11 +24,13 @@ def _data(n, S=20, A=6, seed=5):
 
 
 @pytest.mark.parametrize("hidden,L,act,ln,B", [(64, 2, "tanh", False, 128), (256, 2, "relu", True, 512),
-                                              (500, 2, "tanh", False, 512), (96, 3, "tanh", True, 77)])
+                                              (500, 2, "tanh", False, 512), (96, 3, "tanh", True, 77),
+                                              (428, 2, "tanh", True, 512)])
 @pytest.mark.parametrize("fused", ["1", "0"])
 def test_fit_matches_oracle(hidden, L, act, ln, B, fused, monkeypatch):
-    """fused: the two-launch iteration (fit_rows_kernel + fit_params_kernel, the default);
-    "0": the per-op kernels (BCMPC_FIT_FUSED=0)."""
+    """fused: the two-launch iteration (fit_rows_kernel + fit_params_kernel, the default) where the row
+    kernel's LDS fits -- up to 2 x 428, the widest case here; 2 x 500 (run.sh's model) does not fit and
+    runs the per-op kernels under either setting; "0": the per-op kernels (BCMPC_FIT_FUSED=0)."""
     monkeypatch.setenv("BCMPC_FIT_FUSED", fused)
     from bc_mpc_amd.engine import MLPSpec
     from bc_mpc_amd.fit import GPUFitter
@@ -38,6 +40,8 @@ def test_fit_matches_oracle(hidden, L, act, ln, B, fused, monkeypatch):
     rs = np.random.RandomState(9)
     batches = [rs.choice(2000, B, replace=False) for _ in range(iters)]
     f = GPUFitter(20, 6, hidden, L, act, ln, B, lr, device=0)
+    from test_fit_oracle import fused_fits
+    assert f.fused == (fused == "1" and hidden != 500) == (fused == "1" and fused_fits(hidden, L))
     f.set_params(MLPSpec(w.kernels, w.biases, act, w.ln_gamma, w.ln_beta), norm)
     f.set_data(states, actions, deltas)
     got = f.run(batches)
