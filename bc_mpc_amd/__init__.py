@@ -11,11 +11,11 @@ from .controllers import (Controller, MCTScontrollerPolicyNetReward, MPCcontroll
                           MPCcontrollerPolicyNetReward, MPCcontrollerReward, RandomController)
 from .cem import CEMcontroller
 from .mppi import MPPIcontroller
-from .cost_functions import cheetah_cost_fn, trajectory_cost_fn
+from .cost_functions import TermCost, cheetah_cost_fn, cheetah_terms, trajectory_cost_fn
 from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
-           "trajectory_cost_fn", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult"]
+           "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

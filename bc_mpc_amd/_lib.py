@@ -29,7 +29,11 @@ ABI_VERSION = 5
 
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE, ERR_EMPTY = range(6)
 ACT_TANH, ACT_RELU = 0, 1
-COST_CHEETAH, COST_NONE, COST_REWARD = 0, 1, 2
+COST_CHEETAH, COST_NONE, COST_REWARD, COST_TERMS = 0, 1, 2, 3
+MAX_COST_TERMS = 32
+TERM_THRESHOLD, TERM_DIFF, TERM_LINEAR, TERM_QUADRATIC = range(4)
+SRC_STATE, SRC_NEXT_STATE, SRC_ACTION = range(3)
+CMP_GE, CMP_GT, CMP_LE, CMP_LT = range(4)
 MODEL_DELTA, MODEL_REWARD = 0, 1
 PREC_FP32, PREC_SPLIT_F16, PREC_F16 = 0, 1, 2
 # "f16": single-pass f16 MFMA (BASELINE cfg3's bf16-class GEMM), not the fp32 tolerance
@@ -104,6 +108,18 @@ class Cem(ctypes.Structure):
     ]
 
 
+class CostTerm(ctypes.Structure):
+    """bcmpc_cost_term (32 bytes): one term of a declarative cost (cost_functions.TermCost)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("source", ctypes.c_int32),
+        ("index", ctypes.c_int32),
+        ("cmp", ctypes.c_int32),
+        ("weight", ctypes.c_double),
+        ("param", ctypes.c_double),
+    ]
+
+
 class Elite(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_double), ("index", ctypes.c_int64)]
 
@@ -165,6 +181,10 @@ SIGNATURES = [
     ("bcmpc_first_actions", ctypes.c_int, [ctypes.c_void_p, _DP]),
     ("bcmpc_set_discount", ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     ("bcmpc_set_action_bounds", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
+    ("bcmpc_set_cost_terms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CostTerm), ctypes.c_int32]),
+    ("bcmpc_trajectory_cost_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_get_action", ctypes.c_int,
      [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
     ("bcmpc_get_actions_batch", ctypes.c_int,

@@ -8,7 +8,8 @@ reference's constructor and ``get_action(state)`` contract, keyword extras only:
   ``clip(mu + sigma * z, low, high)`` with z = Irwin-Hall(12) - 6 drawn in the
   rollout kernel (Philox keyed by seed, global candidate, h, j, i);
 * the candidates are scored exactly like ``MPCcontroller.get_action`` (fused
-  cheetah cost, argmin) or like ``MPCcontrollerReward`` (learned reward, argmax);
+  cheetah cost or a ``cost_functions.TermCost``, argmin) or like
+  ``MPCcontrollerReward`` (learned reward, argmax);
 * the ``n_elite`` best (NaN last, ties to the lower index) refit mu / sigma to
   their mean / std, smoothed by ``alpha``;
 * the answer is the first action of the best candidate of ALL iterations.
@@ -37,7 +38,7 @@ import numpy as np
 from . import _lib
 from . import distributed as _dist
 from . import weights as _weights
-from .controllers import Controller, _BatchPlans, _check_model, _default_device
+from .controllers import Controller, _BatchPlans, _check_model, _default_device, _device_terms, _opt
 from .cost_functions import is_cheetah_cost
 from .engine import RolloutEngine
 
@@ -119,20 +120,23 @@ class CEMcontroller(_BatchPlans, Controller):
             mu = np.tile(mid, (H, 1))
         return mu, np.tile(sd, (H, 1))
 
-    def _engine_for(self, spec, S, A, k_local) -> RolloutEngine:
+    def _engine_for(self, spec, S, A, k_local, terms=None) -> RolloutEngine:
         dev = _default_device() if self._device is None else self._device
         key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev)
+               int(k_local), dev, terms is not None)
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.close()
             reward = spec.model == "reward"
             self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
                                          int(self.horizon), int(k_local), device=dev,
-                                         cost="reward" if reward else "cheetah", model=spec.model)
+                                         cost="reward" if reward else "terms" if terms is not None else "cheetah",
+                                         model=spec.model)
             self._engine.set_action_bounds(*self._bounds())
             self._engine_key = key
             self._gamma_set = None
+        if terms is not None:
+            self._engine.set_cost_terms(terms)
         if spec.model == "reward" and self._gamma_set != float(self.gamma):
             self._engine.set_discount(float(self.gamma))
             self._gamma_set = float(self.gamma)
@@ -149,17 +153,21 @@ class CEMcontroller(_BatchPlans, Controller):
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         spec, norm, version = _weights.extract(self.dyn_model)
         reward = spec.model == "reward"
+        terms = None
         if not reward:
             _check_model(spec, "delta", type(self).__name__)
-            if not is_cheetah_cost(self.cost_fn, S, A):
+            terms = _device_terms(self.cost_fn, S, A)
+            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
                 raise ValueError("CEMcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
         mu0, sd0 = self.initial_distribution()
         seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
         rank, ws = _dist.world(self._group)
         lo, hi = _dist.shard_range(K, rank, ws)
         E = min(self.n_elite, K)
+        if ws > 1 and terms is not None:
+            raise NotImplementedError("multi-rank CEM with a TermCost is not built yet (one rank only)")
         if ws == 1:
-            eng = self._engine_for(spec, S, A, K)
+            eng = self._engine_for(spec, S, A, K, *_opt(terms))
             eng.set_weights(spec, norm, version)
             res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, E, self.alpha, seed)
             cost, pos, first = res.best_cost, res.best_index, res.first_action
@@ -190,14 +198,16 @@ class CEMcontroller(_BatchPlans, Controller):
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
         spec, norm, version = _weights.extract(self.dyn_model)
+        terms = None
         if spec.model != "reward":
             _check_model(spec, "delta", type(self).__name__)
-            if not is_cheetah_cost(self.cost_fn, S, A):
+            terms = _device_terms(self.cost_fn, S, A)
+            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
                 raise ValueError("CEMcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
         B = states.shape[0]
         mu0, sd0 = self.batch_initial_distribution(B)
         seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
-        eng = self._batch_engine_for(spec, S, A, B * K)
+        eng = self._batch_engine_for(spec, S, A, B * K, *_opt(terms))
         eng.set_weights(spec, norm, version)
         res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
         self._store_plans(mu)

@@ -45,7 +45,7 @@ import numpy as np
 from . import distributed as _dist
 from . import policy as _policy
 from . import weights as _weights
-from .cost_functions import is_cheetah_cost, trajectory_cost_fn
+from .cost_functions import TermCost, is_cheetah_cost, trajectory_cost_fn
 from .engine import RolloutEngine
 
 
@@ -128,6 +128,20 @@ def _minloc(ctrl, eng, valid, cost, index, first, A):
     return _dist.allgather_minloc(valid, cost, index, first, A, ctrl._group, device=_comm_device(ctrl))
 
 
+def _device_terms(cost_fn, S: int, A: int):
+    """The ``TermCost`` a controller evaluates on the device (``RolloutEngine(cost="terms")``), or None: the
+    cheetah cost is fused into the rollout kernels, and any other callable stays on the host."""
+    if isinstance(cost_fn, TermCost) and not is_cheetah_cost(cost_fn, S, A):
+        return cost_fn
+    return None
+
+
+def _opt(terms) -> tuple:
+    """The trailing ``terms`` argument of the ``_engine_for`` methods, passed only when there is one (a
+    subclass or test double that replaces ``_engine_for`` with the earlier signature keeps working)."""
+    return () if terms is None else (terms,)
+
+
 def _batch_rng_check(rng: str) -> None:
     """get_actions draws in the kernel only: the host-stream modes promise ONE draw per get_action call
     in the reference's order, and a batch of environments in one launch cannot keep that order."""
@@ -189,20 +203,23 @@ class _BatchPlans:
             raise ValueError(f"states shape {states.shape} != (B, S) = (B >= 1, {S})")
         return states
 
-    def _batch_engine_for(self, spec, S: int, A: int, k_total: int) -> RolloutEngine:
+    def _batch_engine_for(self, spec, S: int, A: int, k_total: int, terms=None) -> RolloutEngine:
         dev = _default_device() if self._device is None else self._device
         key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_total), dev)
+               int(k_total), dev, terms is not None)
         if self._batch_engine is None or self._batch_key != key:
             if self._batch_engine is not None:
                 self._batch_engine.close()
             reward = spec.model == "reward"
             self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
                                                int(self.horizon), int(k_total), device=dev,
-                                               cost="reward" if reward else "cheetah", model=spec.model)
+                                               cost="reward" if reward else "terms" if terms is not None
+                                               else "cheetah", model=spec.model)
             self._batch_engine.set_action_bounds(*self._bounds())
             self._batch_key = key
             self._batch_gamma = None
+        if terms is not None:
+            self._batch_engine.set_cost_terms(terms)
         if spec.model == "reward" and self._batch_gamma != float(self.gamma):
             self._batch_engine.set_discount(float(self.gamma))
             self._batch_gamma = float(self.gamma)
@@ -260,20 +277,22 @@ class MPCcontroller(Controller):
         A = len(self.env.action_space.high)
         return S, A
 
-    def _engine_for(self, spec, S, A, k_local, fused) -> RolloutEngine:
+    def _engine_for(self, spec, S, A, k_local, fused, terms=None) -> RolloutEngine:
         dev = _default_device() if self._device is None else self._device
         key = (S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev, fused)
+               int(k_local), dev, fused, terms is not None)
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.close()
             self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
                                          int(self.horizon), int(k_local), device=dev,
-                                         cost="cheetah" if fused else "none")
+                                         cost="cheetah" if fused else "terms" if terms is not None else "none")
             self._engine.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
                                            np.asarray(self.env.action_space.high, dtype=np.float64))
             self._engine_key = key
             self._traj_buf = None
+        if terms is not None:
+            self._engine.set_cost_terms(terms)
         return _attach_comm(self, self._engine, fused)
 
     def _next_seed(self) -> int:
@@ -309,7 +328,8 @@ class MPCcontroller(Controller):
             raise TypeError("MPCcontroller needs an NNDynamicsModel: NNDynamicsRewardModel.predict returns "
                             "(next_state, reward) (dynamics.py:238); use MPCcontrollerReward")
         fused = is_cheetah_cost(self.cost_fn, S, A)
-        if not fused and self.rng != "numpy":
+        terms = _device_terms(self.cost_fn, S, A)          # a TermCost is scored on the device, either rng
+        if not fused and terms is None and self.rng != "numpy":
             raise ValueError("a non-cheetah cost_fn needs rng='numpy' (actions must exist on the host)")
 
         if K == 0:                                          # (the reference draws before failing)
@@ -344,10 +364,10 @@ class MPCcontroller(Controller):
 
         valid, cost, index, first = False, float("inf"), -1, None
         if hi > lo:
-            eng = self._engine_for(spec, S, A, hi - lo, fused)
+            eng = self._engine_for(spec, S, A, hi - lo, fused, *_opt(terms))
             eng.set_weights(spec, norm, version)            # no-op unless the version changed
             local = None if action_paths is None else np.ascontiguousarray(action_paths[:, lo:hi, :])
-            if fused:
+            if fused or terms is not None:
                 res = eng.get_action(state, local, seed=seed, cand_offset=lo, return_costs=self.keep_costs)
                 valid, cost, index, first = True, res.best_cost, res.best_index, res.first_action
                 self.last_costs = res.costs
@@ -370,7 +390,7 @@ class MPCcontroller(Controller):
         launch chain (``RolloutEngine.get_actions``).  Returns ``[B, A]`` float64.  Row ``b`` is what
         ``get_action(states[b])`` returns on the Philox candidates ``b*K .. (b+1)*K`` of the call's seed
         (one seed is drawn per call, as ``get_action`` draws one).  ``rng="device"`` on one rank with the
-        fused cheetah cost only."""
+        fused cheetah cost or a ``TermCost`` only."""
         _batch_rng_check(self.rng)
         S, A = self._dims()
         K = int(self.num_simulated_paths)
@@ -380,24 +400,27 @@ class MPCcontroller(Controller):
         spec, norm, version = _weights.extract(self.dyn_model)
         if spec.model != "delta":
             raise TypeError("MPCcontroller needs an NNDynamicsModel; use MPCcontrollerReward")
-        if not is_cheetah_cost(self.cost_fn, S, A):
+        terms = _device_terms(self.cost_fn, S, A)
+        if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
             raise ValueError("get_actions needs the fused cheetah cost_fn")
         seed = self._next_seed()
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
         dev = _default_device() if self._device is None else self._device
         key = (S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               states.shape[0] * K, dev)
+               states.shape[0] * K, dev, terms is not None)
         eng = getattr(self, "_batch_engine", None)
         if eng is None or self._batch_key != key:
             if eng is not None:
                 eng.close()
             eng = self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation,
                                                      spec.layer_norm, int(self.horizon), states.shape[0] * K,
-                                                     device=dev, cost="cheetah")
+                                                     device=dev, cost="cheetah" if terms is None else "terms")
             eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
                                   np.asarray(self.env.action_space.high, dtype=np.float64))
             self._batch_key = key
+        if terms is not None:
+            eng.set_cost_terms(terms)
         eng.set_weights(spec, norm, version)
         res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
         self.last_costs, self.last_cost, self.last_index = res.costs, res.best_cost, res.best_index

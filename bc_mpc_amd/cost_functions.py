@@ -45,6 +45,136 @@ def trajectory_cost_fn(cost_fn, states, actions, next_states):
     return trajectory_cost
 
 
+# ---------------------------------------------------------------- declarative costs ("terms")
+# The engine cannot run Python, so a cost other than the cheetah's reaches the device as a list of terms
+# (include/bcmpc.h bcmpc_cost_term, csrc/term_cost.hip).  The per-step cost of (s, a, s') is acc = 0.0, then
+# for each term in list order
+#   threshold  if x cmp value: acc = acc + weight        (NaN compares false)
+#   progress   acc = acc + weight * ((s'[index] - s[index]) / dt)
+#   linear     acc = acc + weight * x
+#   quadratic  d = x - target; acc = acc + weight * (d * d)
+# every operation one IEEE f64 operation.  TermCost.__call__ below IS that definition (NumPy f64, elementwise,
+# term order); the kernel is tested against it bit for bit.
+THRESHOLD, DIFF, LINEAR, QUADRATIC = range(4)
+STATE, NEXT_STATE, ACTION = range(3)
+GE, GT, LE, LT = range(4)
+MAX_TERMS = 32
+_SOURCES = {"state": STATE, "next_state": NEXT_STATE, "action": ACTION}
+_CMPS = {">=": GE, ">": GT, "<=": LE, "<": LT}
+_CMP_FN = {GE: np.greater_equal, GT: np.greater, LE: np.less_equal, LT: np.less}
+
+
+class Term(tuple):
+    """One term: ``(kind, source, index, cmp, weight, param)`` (bcmpc_cost_term's fields)."""
+    __slots__ = ()
+
+    def __new__(cls, kind, source, index, cmp, weight, param):
+        return super().__new__(cls, (int(kind), int(source), int(index), int(cmp), float(weight), float(param)))
+
+    kind = property(lambda self: self[0])
+    source = property(lambda self: self[1])
+    index = property(lambda self: self[2])
+    cmp = property(lambda self: self[3])
+    weight = property(lambda self: self[4])
+    param = property(lambda self: self[5])
+
+
+def _source(on) -> int:
+    if on not in _SOURCES:
+        raise ValueError(f"on must be one of {sorted(_SOURCES)}, not {on!r}")
+    return _SOURCES[on]
+
+
+def threshold(index, op, value, weight, on="state") -> Term:
+    """``+ weight`` where ``x op value`` (op one of ``>=  >  <=  <``); nothing where it is false or NaN."""
+    if op not in _CMPS:
+        raise ValueError(f"op must be one of {sorted(_CMPS)}, not {op!r}")
+    return Term(THRESHOLD, _source(on), index, _CMPS[op], weight, value)
+
+
+def progress(index, dt, weight=-1.0) -> Term:
+    """``+ weight * ((next_state[index] - state[index]) / dt)``: with the default weight, forward velocity
+    along ``index`` is rewarded (``cheetah_cost_fn``'s last line is ``progress(17, 0.01)``)."""
+    return Term(DIFF, STATE, index, GE, weight, dt)
+
+
+def linear(index, weight, on="state") -> Term:
+    """``+ weight * x``."""
+    return Term(LINEAR, _source(on), index, GE, weight, 0.0)
+
+
+def quadratic(index, weight, target=0.0, on="state") -> Term:
+    """``+ weight * (x - target)**2`` (``on="action"``, target 0: one summand of ``weight * sum(a**2)``)."""
+    return Term(QUADRATIC, _source(on), index, GE, weight, target)
+
+
+class TermCost:
+    """A cost built from terms, with the reference's ``cost_fn(state, action, next_state)`` signature for
+    1-D (one transition) and 2-D (a batch, one row each) inputs.  Passed as ``cost_fn`` to MPCcontroller,
+    CEMcontroller or MPPIcontroller it is evaluated on the device (``RolloutEngine(cost="terms")``) for any
+    state size; called, it evaluates the same expressions in NumPy f64 -- the definition the kernel is
+    tested against.  Minimised; weights may be negative."""
+
+    def __init__(self, terms=()):
+        self.terms = tuple(t if isinstance(t, Term) else Term(*t) for t in terms)
+        if len(self.terms) > MAX_TERMS:
+            raise ValueError(f"a TermCost holds at most {MAX_TERMS} terms, got {len(self.terms)}")
+        for i, t in enumerate(self.terms):
+            if t.kind not in (THRESHOLD, DIFF, LINEAR, QUADRATIC):
+                raise ValueError(f"term {i}: unknown kind {t.kind}")
+            if t.source not in (STATE, NEXT_STATE, ACTION):
+                raise ValueError(f"term {i}: unknown source {t.source}")
+            if t.kind == THRESHOLD and t.cmp not in (GE, GT, LE, LT):
+                raise ValueError(f"term {i}: unknown cmp {t.cmp}")
+            if t.kind == DIFF and t.source != STATE:
+                raise ValueError(f"term {i}: a progress term reads the state")
+            if t.index < 0:
+                raise ValueError(f"term {i}: negative index {t.index}")
+            if not (np.isfinite(t.weight) and np.isfinite(t.param)):
+                raise ValueError(f"term {i}: weight and param must be finite")
+            if t.kind == DIFF and t.param == 0.0:
+                raise ValueError(f"term {i}: a progress term's dt must not be 0")
+
+    def key(self):
+        return self.terms
+
+    def validate(self, state_dim: int, action_dim: int) -> None:
+        """Every index inside the state / the action of this task (the engine checks the same)."""
+        for i, t in enumerate(self.terms):
+            lim = action_dim if t.source == ACTION else state_dim
+            if t.index >= lim:
+                raise ValueError(f"term {i}: index {t.index} outside [0, {lim})")
+
+    def __len__(self):
+        return len(self.terms)
+
+    def __repr__(self):
+        return f"TermCost({list(map(tuple, self.terms))})"
+
+    def __call__(self, state, action, next_state):
+        s, a, ns = (np.asarray(x, dtype=np.float64) for x in (state, action, next_state))
+        src = (s, ns, a)
+        acc = np.zeros(s.shape[:-1])
+        for t in self.terms:
+            x = src[t.source][..., t.index]
+            if t.kind == THRESHOLD:
+                acc = np.where(_CMP_FN[t.cmp](x, t.param), acc + t.weight, acc)
+            elif t.kind == DIFF:
+                acc = acc + t.weight * ((ns[..., t.index] - x) / t.param)
+            elif t.kind == LINEAR:
+                acc = acc + t.weight * x
+            else:
+                d = x - t.param
+                acc = acc + t.weight * (d * d)
+        return acc if acc.ndim else float(acc)
+
+
+def cheetah_terms() -> TermCost:
+    """``cheetah_cost_fn`` as terms, bit for bit: ``acc + (-1.0 * q)`` is ``acc - q``."""
+    return TermCost([threshold(5, ">=", 0.2, 10.0), threshold(6, ">=", 0.0, 10.0), threshold(7, ">=", 0.0, 10.0),
+                     progress(17, 0.01, -1.0)])
+
+
 _PROBED: dict = {}     # (cost_fn, state_dim, action_dim) -> verdict of the probe below
 
 

@@ -315,6 +315,12 @@ struct bcmpc_engine {
     uint32_t* d_spec_xs = nullptr;
     uint32_t* d_spec_part = nullptr;
     bcmpc_comm* comm = nullptr;         // attached communicator: results exchanged after every argmin
+    // BCMPC_COST_TERMS (term_cost.hip): the launch template bcmpc_set_cost_terms builds (digested terms, slots)
+    // and the trajectory scratch [H+1][num_paths][S] the rollout writes when the caller passes no d_traj --
+    // allocated at create, never inside a stream-ordered entry (a captured graph keeps the address)
+    TermCostArgs tc{};
+    bool has_terms = false;
+    double* d_tc_traj = nullptr;
     // team kernel: a team that could not meet (its workgroups not all resident: another process or
     // kernel holding CUs for ~1 s) makes a synchronous call rerun on this fallback engine -- the same
     // net on the split slab kernel, or the fp32 group kernel where only the team kernel takes the net
@@ -360,7 +366,8 @@ int bcmpc_create(const bcmpc_config* cfg, bcmpc_engine** out) {
     if (c.activation != BCMPC_ACT_TANH && c.activation != BCMPC_ACT_RELU) return fail(BCMPC_ERR_UNSUPPORTED, "activation must be tanh or relu");
     if (c.horizon < 1) return fail(BCMPC_ERR_ARG, "horizon must be >= 1");
     if (c.num_paths < 0) return fail(BCMPC_ERR_ARG, "num_paths must be >= 0");
-    if (c.cost != BCMPC_COST_CHEETAH && c.cost != BCMPC_COST_NONE && c.cost != BCMPC_COST_REWARD)
+    if (c.cost != BCMPC_COST_CHEETAH && c.cost != BCMPC_COST_NONE && c.cost != BCMPC_COST_REWARD &&
+        c.cost != BCMPC_COST_TERMS)
         return fail(BCMPC_ERR_UNSUPPORTED, "unknown cost");
     if (c.model != BCMPC_MODEL_DELTA && c.model != BCMPC_MODEL_REWARD) return fail(BCMPC_ERR_ARG, "unknown model");
     const bool reward = c.model == BCMPC_MODEL_REWARD;
@@ -374,6 +381,8 @@ int bcmpc_create(const bcmpc_config* cfg, bcmpc_engine** out) {
         if (c.state_dim > 31) return fail(BCMPC_ERR_UNSUPPORTED, "reward model: state_dim must be <= 31");
     }
     if (c.cost == BCMPC_COST_CHEETAH && c.state_dim < 18) return fail(BCMPC_ERR_UNSUPPORTED, "cheetah cost needs state_dim >= 18");
+    if (c.cost == BCMPC_COST_TERMS && c.policy_hidden > 0)
+        return fail(BCMPC_ERR_UNSUPPORTED, "cost terms: engines with a fused policy need their fused cost");
     if (c.precision != BCMPC_PREC_FP32 && c.precision != BCMPC_PREC_SPLIT_F16 && c.precision != BCMPC_PREC_F16)
         return fail(BCMPC_ERR_UNSUPPORTED, "precision must be FP32, SPLIT_F16 or F16");
     // single-pass f16 (BASELINE cfg3's bf16-class GEMM): the split slab kernels' plain tanh delta net only
@@ -659,6 +668,12 @@ int bcmpc_create(const bcmpc_config* cfg, bcmpc_engine** out) {
             return cleanup(BCMPC_ERR_HIP);
         }
     }
+    if (c.cost == BCMPC_COST_TERMS &&
+        hipMalloc(&e->d_tc_traj, (size_t)(c.horizon + 1) * (size_t)std::max<int64_t>(1, c.num_paths) * c.state_dim *
+                                     sizeof(double)) != hipSuccess) {
+        g_last_error = "device allocation failed (the trajectory scratch of the cost terms)";
+        return cleanup(BCMPC_ERR_HIP);
+    }
     if (reward) {
         if (hipMalloc(&e->d_gpow, (size_t)c.horizon * sizeof(double)) != hipSuccess) {
             g_last_error = "device allocation failed";
@@ -706,7 +721,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
-                    (void*)e->d_bstats, (void*)e->d_belite})
+                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_tc_traj})
         if (p) (void)hipFree(p);
     if (e->h_bresults) (void)hipHostFree(e->h_bresults);
     if (e->h_result) (void)hipHostFree(e->h_result);
@@ -1091,6 +1106,93 @@ int bcmpc_first_actions(bcmpc_engine* e, double* out) {
     return BCMPC_OK;
 }
 
+int bcmpc_set_cost_terms(bcmpc_engine* e, const bcmpc_cost_term* terms, int32_t n) {
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    const bcmpc_config& c = e->cfg;
+    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "cost terms need an engine created with BCMPC_COST_TERMS");
+    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of cost terms must be in [0, 32]");
+    if (n > 0 && !terms) return fail(BCMPC_ERR_ARG, "null argument");
+    TermCostArgs a{};
+    // the slots: every (state dim) the terms read, then every (action) -- term_cost.hip wants the actions last
+    int slot_of[2][BCMPC_MAX_STATE];
+    for (auto& row : slot_of)
+        for (int& v : row) v = -1;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int t = 0; t < n; ++t) {
+            const bcmpc_cost_term& T = terms[t];
+            const std::string at = "cost term " + std::to_string(t) + ": ";
+            if (pass == 0) {
+                if (T.kind < BCMPC_TERM_THRESHOLD || T.kind > BCMPC_TERM_QUADRATIC) return fail(BCMPC_ERR_ARG, at + "unknown kind");
+                if (T.source < BCMPC_SRC_STATE || T.source > BCMPC_SRC_ACTION) return fail(BCMPC_ERR_ARG, at + "unknown source");
+                if (T.kind == BCMPC_TERM_THRESHOLD && (T.cmp < BCMPC_CMP_GE || T.cmp > BCMPC_CMP_LT))
+                    return fail(BCMPC_ERR_ARG, at + "unknown cmp");
+                if (T.kind == BCMPC_TERM_DIFF && T.source != BCMPC_SRC_STATE)
+                    return fail(BCMPC_ERR_ARG, at + "a DIFF term's source must be STATE");
+                const int lim = T.source == BCMPC_SRC_ACTION ? c.action_dim : c.state_dim;
+                if (T.index < 0 || T.index >= lim)
+                    return fail(BCMPC_ERR_ARG, at + "index " + std::to_string(T.index) + " outside [0, " + std::to_string(lim) + ")");
+                if (!std::isfinite(T.weight) || !std::isfinite(T.param))
+                    return fail(BCMPC_ERR_ARG, at + "weight and param must be finite");
+                if (T.kind == BCMPC_TERM_DIFF && T.param == 0.0) return fail(BCMPC_ERR_ARG, at + "a DIFF term's param must not be 0");
+            }
+            const int is_act = T.source == BCMPC_SRC_ACTION ? 1 : 0;
+            if (is_act != pass) continue;
+            int& sl = slot_of[is_act][T.index];
+            if (sl < 0) {
+                sl = a.n_slots++;
+                a.slot_index[sl] = (uint8_t)T.index;
+                a.slot_action[sl] = (uint8_t)is_act;
+                if (!is_act) a.n_state_slots = a.n_slots;
+            }
+            TermDev& d = a.terms[t];
+            d.weight = T.weight; d.param = T.param;
+            d.meta = (uint32_t)T.kind | (T.kind == BCMPC_TERM_THRESHOLD ? (uint32_t)T.cmp << 2 : 0u) |
+                     (T.source == BCMPC_SRC_NEXT_STATE ? 1u << 4 : 0u) | (uint32_t)sl << 8;
+            if (T.kind == BCMPC_TERM_DIFF) {
+                // div_rn's precondition (device_common.h): r = RN(1 / b), and neither near the subnormals
+                const double r = 1.0 / T.param, mb = std::fabs(T.param), mr = std::fabs(r);
+                d.rparam = r;
+                if (mb > 0x1p-500 && mb < 0x1p500 && mr > 0x1p-500 && mr < 0x1p500) d.meta |= 1u << 5;
+            }
+        }
+    a.n_terms = n;
+    a.H = c.horizon; a.S = c.state_dim; a.A = c.action_dim;
+    e->tc = a;
+    e->has_terms = true;
+    if (e->fb) return bcmpc_set_cost_terms(e->fb, terms, n);
+    return BCMPC_OK;
+}
+
+// one term-cost launch on st: the engine's template plus this launch's trajectory, action source and K
+static int term_cost_launch(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
+                            int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
+                            int64_t K, double* d_costs, hipStream_t st) {
+    TermCostArgs a = e->tc;
+    a.traj = d_traj; a.actions = d_actions; a.costs = d_costs;
+    a.cem_mu = d_mu; a.cem_sigma = d_sigma; a.cem_iter = cem_iter;
+    a.seed = seed; a.cand_offset = cand_offset; a.K = K;
+    for (int j = 0; j < e->cfg.action_dim; ++j) {
+        a.low[j] = e->h_consts[6 * kConstCols + j];
+        a.high[j] = e->h_consts[7 * kConstCols + j];
+    }
+    HIP_TRY(launch_term_cost(a, st));
+    return BCMPC_OK;
+}
+
+int bcmpc_trajectory_cost_async(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
+                                int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
+                                int64_t K, double* d_costs, void* stream) {
+    if (!e || !d_traj || !d_costs) return fail(BCMPC_ERR_ARG, "null argument");
+    if (e->cfg.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "trajectory_cost needs an engine created with BCMPC_COST_TERMS");
+    if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
+    if (d_mu && !d_sigma) return fail(BCMPC_ERR_ARG, "d_mu without d_sigma");
+    if (cem_iter < 0 || cem_iter >= (1 << 22)) return fail(BCMPC_ERR_ARG, "cem_iter must be in [0, 2^22)");
+    if (!e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return term_cost_launch(e, d_traj, d_actions, seed, cand_offset, d_mu, d_sigma, cem_iter, K, d_costs,
+                            (hipStream_t)stream);
+}
+
 int bcmpc_set_action_bounds(bcmpc_engine* e, const double* low, const double* high) {
     if (!e || !low || !high) return fail(BCMPC_ERR_ARG, "null argument");
     for (int j = 0; j < e->cfg.action_dim; ++j) {
@@ -1234,6 +1336,10 @@ static int team_fallback(bcmpc_engine* e, bool collective = false) {
     }
     if (e->reward)
         if (const int rc = bcmpc_set_discount(f, e->gamma)) return rc;
+    if (e->has_terms) {                              // (the same shape: the launch template carries over)
+        f->tc = e->tc;
+        f->has_terms = true;
+    }
     double lo[BCMPC_MAX_ACTION], hi[BCMPC_MAX_ACTION];
     for (int j = 0; j < e->cfg.action_dim; ++j) {
         lo[j] = e->h_consts[6 * kConstCols + j];
@@ -1334,6 +1440,11 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
     if (stride != 0 && stride != c.state_dim) return fail(BCMPC_ERR_ARG, "state_stride must be 0 or state_dim");
     if (c.cost != BCMPC_COST_NONE && !d_costs) return fail(BCMPC_ERR_ARG, "the fused objective needs a costs buffer");
     if (d_result && c.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "argmin needs the fused cost");
+    // cost terms: the rollout kernel runs as a BCMPC_COST_NONE launch that writes the trajectory (the caller's
+    // or the scratch), term_cost_kernel turns it into d_costs, and the ordinary argmin launch follows
+    const bool terms = c.cost == BCMPC_COST_TERMS;
+    if (terms && !e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
+    if (terms) d_traj = d_traj ? d_traj : e->d_tc_traj;
     RolloutArgs a{};
     for (int l = 0; l < e->nwl; ++l) {
         const size_t end = l + 1 < e->nwl ? e->w_off[l + 1] : e->w_floats;
@@ -1364,10 +1475,10 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
         a.state_inline = 1;
         for (int i = 0; i < c.state_dim; ++i) a.state_v[i] = state_inline[i];
     }
-    a.actions = d_actions; a.costs = d_costs; a.traj = d_traj;
+    a.actions = d_actions; a.costs = terms ? nullptr : d_costs; a.traj = d_traj;
     a.seed = seed; a.cand_offset = cand_offset; a.K = c.num_paths;
     a.H = c.horizon; a.S = c.state_dim; a.A = c.action_dim; a.L = c.n_layers;
-    a.hidden = c.hidden; a.act = c.activation; a.ln = c.layer_norm; a.cost = c.cost;
+    a.hidden = c.hidden; a.act = c.activation; a.ln = c.layer_norm; a.cost = terms ? BCMPC_COST_NONE : c.cost;
     if (e->PL > 0) {
         if (!e->has_policy) return fail(BCMPC_ERR_STATE, "bcmpc_set_policy has not been called");
         if (c.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_UNSUPPORTED, "policy engines need the fused cost");
@@ -1423,7 +1534,7 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
         const char* v = std::getenv("BCMPC_TEAM_FUSED_ARGMIN");
         return !(v && v[0] == '0');
     }();
-    const bool fused = d_result && !cem &&
+    const bool fused = d_result && !cem && !terms &&
                        (e->kernel == BCMPC_KERNEL_TEAM ? team_fused
                                                        : e->split && fa && fa[0] == '1');
     if (fused) {
@@ -1540,6 +1651,10 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
     } else {
         HIP_TRY(launch_rollout_grp(a, e->HP, kern_waves(e->kernel), st));
     }
+    if (terms)
+        if (const int rc = term_cost_launch(e, d_traj, d_actions, seed, cand_offset, cem ? cem->mu : nullptr,
+                                            cem ? cem->sigma : nullptr, cem ? cem->iter : 0, c.num_paths, d_costs, st))
+            return rc;
     if (record_events) HIP_TRY(hipEventRecord(e->ev[1], st));
     if (d_result && (!fused || team_skipped)) HIP_TRY(launch_argmin(m, st));
     if (d_result && e->comm && !cem) {
@@ -2196,6 +2311,9 @@ int bcmpc_get_action_mt19937(bcmpc_engine* e, const double* state, uint32_t* mt_
     if (!e || !state || !mt_key || !mt_pos || !low || !high || !out) return fail(BCMPC_ERR_ARG, "null argument");
     const bcmpc_config& c = e->cfg;
     if (c.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "get_action needs a fused objective (cheetah cost or learned reward)");
+    if (c.cost == BCMPC_COST_TERMS)
+        return fail(BCMPC_ERR_UNSUPPORTED, "the NumPy-stream draw does not cover cost-term engines: draw on the host "
+                                           "and pass the array to bcmpc_get_action");
     if (k_global < c.num_paths || cand_offset < 0 || cand_offset + c.num_paths > k_global)
         return fail(BCMPC_ERR_ARG, "this engine's candidates must lie inside [0, k_global)");
     if (*mt_pos < 0 || *mt_pos > 624) return fail(BCMPC_ERR_ARG, "MT19937 position out of range");
@@ -3032,6 +3150,8 @@ int bcmpc_engine_set_comm(bcmpc_engine* e, bcmpc_comm* comm) {
         return fail(BCMPC_ERR_ARG, "the communicator was created for another device");
     if (comm && e->cfg.cost == BCMPC_COST_NONE)
         return fail(BCMPC_ERR_ARG, "the exchange needs the fused objective (argmin records)");
+    if (comm && e->cfg.cost == BCMPC_COST_TERMS)
+        return fail(BCMPC_ERR_UNSUPPORTED, "cost-term engines do not exchange records inside the library yet");
     e->comm = comm;
     return BCMPC_OK;
 }
@@ -3084,7 +3204,7 @@ int bcmpc_engine_layout(const bcmpc_engine* e, char* buf, int32_t cap) {
             else
                 std::snprintf(s, sizeof(s), "rollout_x3<%d,NC=%d,NW=%d> %s", e->HP, e->nc, e->nw, prec);
     }
-    std::snprintf(buf, (size_t)cap, "%s", s);
+    std::snprintf(buf, (size_t)cap, "%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "");
     return BCMPC_OK;
 }
 

@@ -256,6 +256,34 @@ struct SegmentArgminArgs {                   // one np.argmin record per environ
     int32_t n_envs, A;
     int32_t maximize;                        // np.argmax (learned reward)
 };
+// ---- declarative cost terms (term_cost.hip): costs[K] from a stored trajectory ----
+// The host compacts what the terms read into at most BCMPC_MAX_COST_TERMS slots: slot i of row r is the
+// state dim slot_index[i] of traj[r][k] (slot_action[i] == 0) or action slot_index[i] of step r (== 1, last).  A term
+// reads its slot of row h (STATE, ACTION, DIFF's s) or of row h + 1 (NEXT_STATE, DIFF's s').
+struct TermDev {                             // one bcmpc_cost_term as the kernel reads it: one 32-byte scalar load
+    double weight, param;
+    double rparam;                           // DIFF: RN(1 / param), div_rn's r
+    uint32_t meta;                           // kind | cmp << 2 | (NEXT_STATE) << 4 | (div_rn applies) << 5 | slot << 8
+    uint32_t pad;
+};
+struct TermCostArgs {
+    const double* traj;                      // [H+1][K][S]
+    const double* actions;                   // [H][K][A] or nullptr => regenerated (action slots only)
+    const double* cem_mu;                    // [H][A] or nullptr: cem_action instead of rng_action
+    const double* cem_sigma;
+    double* costs;                           // [K]
+    uint64_t seed;
+    int64_t cand_offset, K;
+    int32_t H, S, A, cem_iter;
+    int32_t n_terms, n_slots, n_state_slots;  // slots [n_state_slots, n_slots) are the action slots
+    uint8_t slot_index[BCMPC_MAX_COST_TERMS];
+    uint8_t slot_action[BCMPC_MAX_COST_TERMS];
+    uint32_t slot_word[BCMPC_MAX_COST_TERMS / 4];   // (filled by launch_term_cost) the two arrays, a byte per slot
+    double low[BCMPC_MAX_ACTION], high[BCMPC_MAX_ACTION];   // action bounds (regenerated actions)
+    TermDev terms[BCMPC_MAX_COST_TERMS];     // by value: 32 x 32 bytes, no per-launch upload
+};
+hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);
+
 hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);
 hipError_t launch_argmin_segments(const SegmentArgminArgs& a, hipStream_t st);
 

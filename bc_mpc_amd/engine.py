@@ -145,7 +145,11 @@ class RolloutEngine:
                  device: int = 0, cost: str = "cheetah", kernel: Optional[str] = None,
                  policy_hidden: int = 0, policy_layers: int = 0, policy_mode: str = "explore",
                  model: str = "delta", precision: Optional[str] = None):
-        """``precision``: "fp32" (v_mfma_f32_16x16x4_f32), "split" (f32-accurate hi/lo f16
+        """``cost``: "cheetah" (fused cheetah_cost_fn, needs state_dim >= 18), "reward" (the learned reward of
+        ``model="reward"``), "terms" (a ``cost_functions.TermCost`` given with set_cost_terms, scored on the device
+        from the trajectory; any state_dim, no fused policy) or "none" (no objective: the caller scores the
+        trajectory rollout_async returns).
+        ``precision``: "fp32" (v_mfma_f32_16x16x4_f32), "split" (f32-accurate hi/lo f16
         operands on v_mfma_f32_16x16x32_f16, rollout_x3.hip; relu / LayerNorm only for the plain delta net
         with hidden <= 512; a fused policy needs a tanh net of hidden 449..1024, 449..512 with the reward
         net), "f16" (one f16 MFMA pass on the split slab kernels: BASELINE cfg3's "bf16 MFMA GEMM + fp32
@@ -160,7 +164,8 @@ class RolloutEngine:
         cfg.activation = _ACT[activation]
         cfg.layer_norm = int(bool(layer_norm))
         cfg.horizon = int(horizon)
-        costs = {"cheetah": _lib.COST_CHEETAH, "none": _lib.COST_NONE, "reward": _lib.COST_REWARD}
+        costs = {"cheetah": _lib.COST_CHEETAH, "none": _lib.COST_NONE, "reward": _lib.COST_REWARD,
+                 "terms": _lib.COST_TERMS}
         models = {"delta": _lib.MODEL_DELTA, "reward": _lib.MODEL_REWARD}
         if cost not in costs or model not in models:
             raise ValueError(f"cost must be one of {sorted(costs)}, model one of {sorted(models)}")
@@ -218,6 +223,7 @@ class RolloutEngine:
         self.comm = None
         self._mt_fast = None        # get_action_numpy_stream's prepared ctypes arguments
         self._ga_fast = None        # get_action's (device actions, no cost vector) prepared ctypes arguments
+        self.cost_terms = None      # the TermCost of a cost="terms" engine (set_cost_terms)
 
     # ------------------------------------------------------------------ weights
     def set_weights(self, spec: MLPSpec, normalization: Sequence, version: int) -> None:
@@ -320,6 +326,38 @@ class RolloutEngine:
         _lib.check(self._lib.bcmpc_predraw_stats(self._h, out))
         return {"hits": int(out[0]), "late": int(out[1]), "misses": int(out[2]), "spec_hits": int(out[3]),
                 "spec_misses": int(out[4])}
+
+    def set_cost_terms(self, term_cost) -> None:
+        """The objective of a ``cost="terms"`` engine (bcmpc_set_cost_terms): a ``cost_functions.TermCost``
+        (or an iterable of its terms).  Every rollout entry raises until this has been called; calling it
+        again replaces the list for the next launch."""
+        from .cost_functions import TermCost
+        tc = term_cost if isinstance(term_cost, TermCost) else TermCost(term_cost)
+        if self.cost_terms is not None and tc.key() == self.cost_terms.key():
+            return
+        tc.validate(self.state_dim, self.action_dim)
+        arr = (_lib.CostTerm * max(1, len(tc.terms)))()
+        for dst, t in zip(arr, tc.terms):
+            dst.kind, dst.source, dst.index, dst.cmp = t.kind, t.source, t.index, t.cmp
+            dst.weight, dst.param = t.weight, t.param
+        _lib.check(self._lib.bcmpc_set_cost_terms(self._h, arr, ctypes.c_int32(len(tc.terms))))
+        self.cost_terms = tc
+
+    def trajectory_cost_async(self, d_traj: int, K: int, d_costs: int, d_actions: Optional[int] = None,
+                              seed: int = 0, cand_offset: int = 0, d_mu: Optional[int] = None,
+                              d_sigma: Optional[int] = None, cem_iter: int = 0,
+                              stream: Optional[int] = None) -> None:
+        """The term-cost kernel alone on device pointers (bcmpc_trajectory_cost_async), stream-ordered:
+        ``d_traj`` ``[H+1, K, S]`` f64 -> ``d_costs`` ``[K]`` f64 under the terms of set_cost_terms.  ACTION
+        terms read ``d_actions`` ``[H, K, A]``, or, when it is None, the actions the rollout kernels draw
+        for (``seed``, ``cand_offset + k``): the Philox shooting draw, or the CEM / MPPI sample of
+        ``cem_iter`` from ``d_mu`` / ``d_sigma`` ``[H, A]``.  ``K`` need not equal ``num_paths``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_trajectory_cost_async(
+            self._h, vp(d_traj), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
+            vp(d_mu), vp(d_sigma), ctypes.c_int32(cem_iter), ctypes.c_int64(K), vp(d_costs),
+            ctypes.c_void_p(stream)))
 
     def set_action_bounds(self, low, high) -> None:
         lo, hi = _f64(low), _f64(high)

@@ -6,7 +6,8 @@ reference's constructor and ``get_action(state)`` contract, keyword extras only:
 
 * a round samples every candidate's ``[H, A]`` actions as ``clip(mu + sigma * z, low, high)``
   in the rollout kernel, exactly as a CEM iteration does (same Philox stream);
-* the candidates are scored like ``MPCcontroller.get_action`` (fused cheetah cost) or like
+* the candidates are scored like ``MPCcontroller.get_action`` (fused cheetah cost, or a
+  ``cost_functions.TermCost`` on any state size) or like
   ``MPCcontrollerReward`` (learned reward, negated so that lower is better);
 * EVERY candidate with a finite score gets the weight ``exp(-(v - v_min) / temperature)`` and
   the plan becomes the weighted mean of the candidates' actions; sigma stays as it is;
@@ -32,7 +33,7 @@ import numpy as np
 
 from . import distributed as _dist
 from . import weights as _weights
-from .controllers import Controller, _BatchPlans, _check_model, _default_device
+from .controllers import Controller, _BatchPlans, _check_model, _default_device, _device_terms, _opt
 from .cost_functions import is_cheetah_cost
 from .engine import RolloutEngine
 
@@ -106,20 +107,23 @@ class MPPIcontroller(_BatchPlans, Controller):
             mu = np.tile(mid, (H, 1))
         return mu, np.tile(sd, (H, 1))
 
-    def _engine_for(self, spec, S, A, k_local) -> RolloutEngine:
+    def _engine_for(self, spec, S, A, k_local, terms=None) -> RolloutEngine:
         dev = _default_device() if self._device is None else self._device
         key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev)
+               int(k_local), dev, terms is not None)
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.close()
             reward = spec.model == "reward"
             self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
                                          int(self.horizon), int(k_local), device=dev,
-                                         cost="reward" if reward else "cheetah", model=spec.model)
+                                         cost="reward" if reward else "terms" if terms is not None else "cheetah",
+                                         model=spec.model)
             self._engine.set_action_bounds(*self._bounds())
             self._engine_key = key
             self._gamma_set = None
+        if terms is not None:
+            self._engine.set_cost_terms(terms)
         if spec.model == "reward" and self._gamma_set != float(self.gamma):
             self._engine.set_discount(float(self.gamma))
             self._gamma_set = float(self.gamma)
@@ -140,13 +144,15 @@ class MPPIcontroller(_BatchPlans, Controller):
                 "partials of the weighted mean is not built yet")
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         spec, norm, version = _weights.extract(self.dyn_model)
+        terms = None
         if spec.model != "reward":
             _check_model(spec, "delta", type(self).__name__)
-            if not is_cheetah_cost(self.cost_fn, S, A):
+            terms = _device_terms(self.cost_fn, S, A)
+            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
                 raise ValueError("MPPIcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
         mu0, sd0 = self.initial_distribution()
         seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
-        eng = self._engine_for(spec, S, A, K)
+        eng = self._engine_for(spec, S, A, K, *_opt(terms))
         eng.set_weights(spec, norm, version)
         res, mu, stats = eng.mppi_get_action(state, mu0, sd0, self.iterations, self.temperature, seed)
         self._mu = mu
@@ -171,14 +177,16 @@ class MPPIcontroller(_BatchPlans, Controller):
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
         spec, norm, version = _weights.extract(self.dyn_model)
+        terms = None
         if spec.model != "reward":
             _check_model(spec, "delta", type(self).__name__)
-            if not is_cheetah_cost(self.cost_fn, S, A):
+            terms = _device_terms(self.cost_fn, S, A)
+            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
                 raise ValueError("MPPIcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
         B = states.shape[0]
         mu0, sd0 = self.batch_initial_distribution(B)
         seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
-        eng = self._batch_engine_for(spec, S, A, B * K)
+        eng = self._batch_engine_for(spec, S, A, B * K, *_opt(terms))
         eng.set_weights(spec, norm, version)
         res, mu, stats = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed)
         self._store_plans(mu)

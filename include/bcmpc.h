@@ -51,9 +51,35 @@ typedef enum bcmpc_activation {  /* dynamics.py:60 activation / train_mpc_ppo.py
 typedef enum bcmpc_cost {
     BCMPC_COST_CHEETAH = 0,     /* fused cheetah_cost_fn (cost_functions.py:10-30), argmin  */
     BCMPC_COST_NONE = 1,        /* no fused cost: caller scores the trajectory              */
-    BCMPC_COST_REWARD = 2       /* learned reward: sum_h reward_h * gamma**h, ARGMAX
+    BCMPC_COST_REWARD = 2,      /* learned reward: sum_h reward_h * gamma**h, ARGMAX
                                    (controllers.py:139,150-152); needs BCMPC_MODEL_REWARD  */
+    BCMPC_COST_TERMS = 3        /* a list of bcmpc_cost_term (bcmpc_set_cost_terms) scored from the
+                                   rolled-out trajectory by a kernel of its own, argmin; any state_dim;
+                                   BCMPC_MODEL_DELTA engines without a fused policy.  Additive to ABI 5:
+                                   callers detect it by the symbol bcmpc_set_cost_terms           */
 } bcmpc_cost;
+
+/* Declarative cost ("terms"): the per-step cost of (s, a, s') is acc = 0.0, then for each term in list
+ * order, x being the value `source`/`index` names,
+ *   THRESHOLD  if (x cmp param) acc = acc + weight          (NaN compares false, as in NumPy)
+ *   DIFF       acc = acc + weight * ((s'[index] - s[index]) / param)       source must be STATE
+ *   LINEAR     acc = acc + weight * x
+ *   QUADRATIC  d = x - param; acc = acc + weight * (d * d)
+ * every operation an individually rounded IEEE f64 operation (no contraction; the division correctly
+ * rounded).  The trajectory cost is total = 0.0; for h in 0..H-1: total = total + c_h
+ * (trajectory_cost_fn's order, cost_functions.py:59-63); the engine minimises it.
+ * {THRESHOLD s[5] >= 0.2 +10, THRESHOLD s[6] >= 0 +10, THRESHOLD s[7] >= 0 +10, DIFF 17 / 0.01 weight -1}
+ * is cheetah_cost_fn (cost_functions.py:10-30). */
+#define BCMPC_MAX_COST_TERMS 32
+typedef enum bcmpc_term_kind { BCMPC_TERM_THRESHOLD = 0, BCMPC_TERM_DIFF = 1, BCMPC_TERM_LINEAR = 2,
+                               BCMPC_TERM_QUADRATIC = 3 } bcmpc_term_kind;
+typedef enum bcmpc_term_source { BCMPC_SRC_STATE = 0, BCMPC_SRC_NEXT_STATE = 1, BCMPC_SRC_ACTION = 2 } bcmpc_term_source;
+typedef enum bcmpc_term_cmp { BCMPC_CMP_GE = 0, BCMPC_CMP_GT = 1, BCMPC_CMP_LE = 2, BCMPC_CMP_LT = 3 } bcmpc_term_cmp;
+typedef struct bcmpc_cost_term {   /* 32 bytes */
+    int32_t kind, source, index, cmp;   /* bcmpc_term_kind, bcmpc_term_source, dim (< S, or < A for ACTION),
+                                           bcmpc_term_cmp (THRESHOLD only) */
+    double weight, param;               /* param: threshold / divisor / unused / target */
+} bcmpc_cost_term;
 
 typedef enum bcmpc_model {      /* which dynamics net (dynamics.py)                          */
     BCMPC_MODEL_DELTA = 0,      /* NNDynamicsModel: L x dense(h) -> dense(S) (:54-71)        */
@@ -230,6 +256,26 @@ int bcmpc_set_policy(bcmpc_engine* eng, const bcmpc_policy* p, uint64_t version)
  * gamma**h (host pow, as Python's float ** int).  Default 1.0.  Reward engines only. */
 int bcmpc_set_discount(bcmpc_engine* eng, double gamma);
 
+/* The cost of a BCMPC_COST_TERMS engine (BCMPC_ERR_ARG on any other): n terms, 0 <= n <=
+ * BCMPC_MAX_COST_TERMS, copied.  n == 0: every cost is 0 and index 0 wins.  BCMPC_ERR_ARG: unknown kind /
+ * source / cmp, index outside the state (ACTION: the action), a DIFF whose source is not STATE, weight or
+ * param not finite, a DIFF param of 0.  Every rollout entry of such an engine returns BCMPC_ERR_STATE
+ * before this call.  May be called again between launches (the next launch uses the new list). */
+int bcmpc_set_cost_terms(bcmpc_engine* eng, const bcmpc_cost_term* terms, int32_t n);
+
+/* The term-cost kernel alone, stream-ordered, on a caller's trajectory:
+ *   d_traj    : device [H+1][K][S] doubles (the layout bcmpc_rollout_async's d_traj has)
+ *   d_actions : device [H][K][A] doubles read by ACTION terms, or NULL => regenerated: the Philox shooting
+ *               draw (seed, cand_offset + k, h, j) when d_mu is NULL, else the CEM / MPPI sample of
+ *               iteration cem_iter from d_mu / d_sigma [H][A]; never touched without an ACTION term
+ *   K         : candidates (>= 1; need not equal num_paths); H, S, A and the action bounds are the engine's
+ *   d_costs   : device K doubles
+ * BCMPC_ERR_ARG: null pointers, K < 1, cem_iter outside [0, 2^22), not a BCMPC_COST_TERMS engine.
+ * BCMPC_ERR_STATE: no terms set. */
+int bcmpc_trajectory_cost_async(bcmpc_engine* eng, const double* d_traj, const double* d_actions, uint64_t seed,
+                                int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
+                                int64_t K, double* d_costs, void* stream);
+
 /* env.action_space.low / .high (controllers.py:53). Defaults: [-1, 1]^A. */
 int bcmpc_set_action_bounds(bcmpc_engine* eng, const double* low, const double* high);
 
@@ -310,8 +356,9 @@ int bcmpc_first_actions(bcmpc_engine* eng, double* out);
  *   d_state      : device, S doubles, or [K, S] when state_stride == S (predict mode,
  *                  dynamics.py:106 on per-candidate states)
  *   d_actions    : device [H, K, A] doubles, or NULL => device RNG
- *   d_costs      : device K doubles (required when cost == CHEETAH or REWARD)
- *   d_traj       : device [H+1, K, S] doubles or NULL (states_paths_all, controllers.py:65-74)
+ *   d_costs      : device K doubles (required when cost == CHEETAH, REWARD or TERMS)
+ *   d_traj       : device [H+1, K, S] doubles or NULL (states_paths_all, controllers.py:65-74; a
+ *                  BCMPC_COST_TERMS engine scores the trajectory it writes here, or its own scratch)
  *   d_result     : device bcmpc_result or NULL (argmin + first action)
  *   stream       : hipStream_t the launches are enqueued on, used verbatim (NULL is HIP's
  *                  null stream; pass bcmpc_stream(eng) for the engine's own stream) */
@@ -552,7 +599,7 @@ int bcmpc_comm_init(const uint8_t* id, int32_t nranks, int32_t rank, int32_t dev
                     bcmpc_comm** out);                                          /* ncclCommInitRank  */
 int bcmpc_comm_destroy(bcmpc_comm* comm);
 /* attach (comm != NULL) or detach (NULL); the comm's device must be the engine's.
- * CEM calls (bcmpc_cem_*) do not exchange. */
+ * CEM calls (bcmpc_cem_*) do not exchange.  BCMPC_COST_TERMS engines: BCMPC_ERR_UNSUPPORTED for now. */
 int bcmpc_engine_set_comm(bcmpc_engine* eng, bcmpc_comm* comm);
 /* Host only: the np.argmin (maximize: np.argmax) winner of n result records, for hosts
  * that exchange the records themselves (e.g. MPI / gloo). */
@@ -593,7 +640,7 @@ int bcmpc_engine_info(const bcmpc_engine* eng, int32_t* hidden_padded, int64_t* 
                       int32_t* waves_per_block, int32_t* kernel);
 /* The device kernel instance the engine launches per rollout, as text (e.g. "rollout_pp<512> f16",
  * "rollout_x3<512,NC=4,NW=8> split"), NUL-terminated and truncated to cap bytes: tests and the bench
- * assert / report which layout the engine selected.  Round 5 (ABI 4). */
+ * assert / report which layout the engine selected ("+terms" appended on BCMPC_COST_TERMS engines).  Round 5 (ABI 4). */
 int bcmpc_engine_layout(const bcmpc_engine* eng, char* buf, int32_t cap);
 
 #ifdef __cplusplus
