@@ -13,9 +13,11 @@ from .cem import CEMcontroller
 from .mppi import MPPIcontroller
 from .cost_functions import TermCost, cheetah_cost_fn, cheetah_terms, trajectory_cost_fn
 from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
+from .ensemble import EnsembleDynamicsModel, EnsembleEngine
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
-           "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult"]
+           "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult",
+           "EnsembleEngine", "EnsembleDynamicsModel"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

@@ -34,6 +34,9 @@ MAX_COST_TERMS = 32
 TERM_THRESHOLD, TERM_DIFF, TERM_LINEAR, TERM_QUADRATIC = range(4)
 SRC_STATE, SRC_NEXT_STATE, SRC_ACTION = range(3)
 CMP_GE, CMP_GT, CMP_LE, CMP_LT = range(4)
+MAX_MEMBERS = 16
+ENSEMBLE_MEAN, ENSEMBLE_MEAN_STD, ENSEMBLE_WORST = range(3)
+ENSEMBLE_RULES = {"mean": ENSEMBLE_MEAN, "mean_std": ENSEMBLE_MEAN_STD, "worst": ENSEMBLE_WORST}
 MODEL_DELTA, MODEL_REWARD = 0, 1
 PREC_FP32, PREC_SPLIT_F16, PREC_F16 = 0, 1, 2
 # "f16": single-pass f16 MFMA (BASELINE cfg3's bf16-class GEMM), not the fp32 tolerance
@@ -248,6 +251,24 @@ SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
       ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p]),
+    ("bcmpc_ensemble_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bcmpc_ensemble_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_ensemble_size", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_ensemble_member", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bcmpc_ensemble_set_rule", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    ("bcmpc_ensemble_get_action", ctypes.c_int,
+     [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP, _DP]),
+    ("bcmpc_ensemble_get_actions_batch", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP,
+      _DP]),
+    ("bcmpc_ensemble_cem_get_action", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Cem), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result)]),
+    ("bcmpc_ensemble_mppi_get_action", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result),
+      ctypes.POINTER(MppiStats)]),
+    ("bcmpc_ensemble_reduce_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_stream", ctypes.c_void_p, [ctypes.c_void_p]),
     ("bcmpc_engine_status", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_engine_team_reruns", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),

@@ -143,6 +143,9 @@ class CEMcontroller(_BatchPlans, Controller):
         return self._engine
 
     def get_action(self, state):
+        if getattr(self.dyn_model, "is_ensemble", False):   # an EnsembleDynamicsModel (ensemble.py)
+            from . import ensemble as _ensemble
+            return _ensemble.cem_get_action(self, state)
         S = int(math.prod(self.env.observation_space.shape))
         A = len(self.env.action_space.high)
         K = int(self.num_simulated_paths)
@@ -189,6 +192,8 @@ class CEMcontroller(_BatchPlans, Controller):
         ``reset``); one seed is drawn per call.  Returns ``[B, A]`` float64: each environment's best
         sample's first action.  ``last_mu`` / ``last_sigma`` (``[B, H, A]``), ``last_cost`` /
         ``last_position`` (``[B]``) describe the call.  One rank only."""
+        if getattr(self.dyn_model, "is_ensemble", False):
+            raise NotImplementedError("batched CEM over an EnsembleDynamicsModel is not built yet: use get_action")
         S = int(math.prod(self.env.observation_space.shape))
         A = len(self.env.action_space.high)
         K = int(self.num_simulated_paths)

@@ -301,6 +301,9 @@ class MPCcontroller(Controller):
 
     # controllers.py:57-88
     def get_action(self, state):
+        if getattr(self.dyn_model, "is_ensemble", False):   # an EnsembleDynamicsModel (ensemble.py)
+            from . import ensemble as _ensemble
+            return _ensemble.mpc_get_action(self, state)
         fp = getattr(self, "_fast", None)
         if fp is not None:
             # the per-env-step repeat (utils.py:202): same env / model / cost / shape as the last call, the
@@ -391,6 +394,9 @@ class MPCcontroller(Controller):
         ``get_action(states[b])`` returns on the Philox candidates ``b*K .. (b+1)*K`` of the call's seed
         (one seed is drawn per call, as ``get_action`` draws one).  ``rng="device"`` on one rank with the
         fused cheetah cost or a ``TermCost`` only."""
+        if getattr(self.dyn_model, "is_ensemble", False):
+            from . import ensemble as _ensemble
+            return _ensemble.mpc_get_actions(self, states)
         _batch_rng_check(self.rng)
         S, A = self._dims()
         K = int(self.num_simulated_paths)

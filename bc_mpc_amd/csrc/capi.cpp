@@ -1429,6 +1429,33 @@ static int wait_done(bcmpc_engine* e, unsigned long long seq) {
     return BCMPC_OK;
 }
 
+// the argmin launch's arguments over d_costs [num_paths]: np.argmin (np.argmax for the learned reward), the
+// first action from d_actions / the policy's output / Philox / the CEM sampler, CEM's cross-iteration merge,
+// the completion word of a lean synchronous step.  rollout_impl launches it behind its rollout (or hands it
+// to a kernel that reduces in its own tail); the ensemble calls launch it behind their reduce
+static ArgminArgs argmin_args(bcmpc_engine* e, const double* d_costs, const double* d_actions,
+                              const double* act_out_all, uint64_t seed, int64_t cand_offset, bcmpc_result* d_result,
+                              const CemLaunch* cem) {
+    const bcmpc_config& c = e->cfg;
+    ArgminArgs m{};
+    m.costs = d_costs; m.actions = d_actions; m.consts = e->d_consts; m.out = d_result;
+    m.act_out = e->PL > 0 ? (act_out_all ? act_out_all : e->d_first) : nullptr;
+    m.seed = seed; m.cand_offset = cand_offset; m.K = c.num_paths; m.A = c.action_dim;
+    m.maximize = c.cost == BCMPC_COST_REWARD;
+    m.scratch_c = e->d_amin_c;
+    m.scratch_i = e->d_amin_i;
+    m.nparts = argmin_parts(c.num_paths);
+    if (e->want_done && !e->comm) {
+        m.done = e->d_done;
+        m.seq = ++e->seq;
+    }
+    if (cem) {
+        m.cem_mu = cem->mu; m.cem_sigma = cem->sigma; m.cem_iter = cem->iter;
+        m.merge = cem->merge; m.pos_base = cem->pos_base;
+    }
+    return m;
+}
+
 static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, const double* d_actions,
                         uint64_t seed, int64_t cand_offset, double* d_costs, double* d_traj,
                         bcmpc_result* d_result, hipStream_t st, const CemLaunch* cem = nullptr,
@@ -1507,23 +1534,7 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
         a.cem_iter = cem->iter;
     }
     ArgminArgs m{};
-    if (d_result) {
-        m.costs = d_costs; m.actions = d_actions; m.consts = e->d_consts; m.out = d_result;
-        m.act_out = e->PL > 0 ? (act_out_all ? act_out_all : e->d_first) : nullptr;
-        m.seed = seed; m.cand_offset = cand_offset; m.K = c.num_paths; m.A = c.action_dim;
-        m.maximize = c.cost == BCMPC_COST_REWARD;
-        m.scratch_c = e->d_amin_c;
-        m.scratch_i = e->d_amin_i;
-        m.nparts = argmin_parts(c.num_paths);
-        if (e->want_done && !e->comm) {
-            m.done = e->d_done;
-            m.seq = ++e->seq;
-        }
-        if (cem) {
-            m.cem_mu = cem->mu; m.cem_sigma = cem->sigma; m.cem_iter = cem->iter;
-            m.merge = cem->merge; m.pos_base = cem->pos_base;
-        }
-    }
+    if (d_result) m = argmin_args(e, d_costs, d_actions, act_out_all, seed, cand_offset, d_result, cem);
     // BCMPC_FUSED_ARGMIN=1: the split kernel reduces np.argmin in its own tail (one launch per
     // get_action).  Off by default: the tail's ticket + acquire cost ~6 us in-kernel, as much as the
     // two argmin launches it replaces, and p50 did not move (cfg1/cfg2/run.sh recipe)
@@ -3142,6 +3153,344 @@ int bcmpc_mppi_get_actions_batch(bcmpc_engine* e, const double* states, int32_t 
         return fail(BCMPC_ERR_ARG, "batched MPPI: k_global must be 0 or num_paths / n_envs");
     return plan_get_actions(e, states, n_envs, nullptr, p, seed, cand_offset, mu, nullptr, sigma, out, stats,
                             costs_out);
+}
+
+// ---- model ensembles: E member engines, one launch chain on member 0's stream -----------
+// Per iteration: every member's rollout (no result record) into its row of d_member [E][num_paths], the
+// reduce (ensemble.hip) into member 0's d_costs, then what a single engine runs on its costs -- the argmin
+// launch, select + refit or the MPPI update -- on member 0.  The members run one after the other on ONE
+// stream: the team kernel needs its whole grid resident, which is what team_order_* guards across streams.
+struct bcmpc_ensemble {
+    std::vector<bcmpc_engine*> m;       // the members (owned; a fallback view: the members' fallback engines)
+    double* d_member = nullptr;         // [E][num_paths] member costs, allocated at create
+    int32_t mode = BCMPC_ENSEMBLE_MEAN;
+    double kappa = 0.0;
+    bool owns = true;
+    bcmpc_ensemble* fb = nullptr;       // the ensemble of the members' fallback engines (team give-up)
+};
+
+static const char* ensemble_rule_error(int32_t mode, double kappa) {
+    if (mode < BCMPC_ENSEMBLE_MEAN || mode > BCMPC_ENSEMBLE_WORST) return "unknown ensemble mode";
+    if (!std::isfinite(kappa)) return "kappa must be finite";
+    return nullptr;
+}
+
+static int ensemble_reduce_impl(const double* d_member, int64_t ld, int32_t E, int64_t K, int32_t mode, double kappa,
+                                double* d_out, hipStream_t st) {
+    EnsembleReduceArgs r{};
+    r.member_costs = d_member; r.out = d_out; r.ld = ld; r.K = K; r.E = E; r.mode = mode; r.kappa = kappa;
+    HIP_TRY(launch_ensemble_reduce(r, st));
+    return BCMPC_OK;
+}
+
+// refusals of a call that need no HIP call: a member with a communicator attached
+static int ensemble_call_check(const bcmpc_ensemble* s) {
+    for (const bcmpc_engine* e : s->m)
+        if (e->comm)
+            return fail(BCMPC_ERR_UNSUPPORTED, "ensemble calls do not cover members with a communicator attached");
+    return BCMPC_OK;
+}
+
+struct EnsembleSync {                               // every member inside a synchronous entry point
+    const bcmpc_ensemble* s;
+    explicit EnsembleSync(const bcmpc_ensemble* x) : s(x) { for (bcmpc_engine* e : s->m) e->sync_call = true; }
+    ~EnsembleSync() { for (bcmpc_engine* e : s->m) e->sync_call = false; }
+};
+
+// any member's team gave up (every member's flag is read, which clears it)
+static bool ensemble_failed(bcmpc_ensemble* s) {
+    bool any = false;
+    for (bcmpc_engine* e : s->m) any = team_failed(e) || any;
+    return any;
+}
+
+// the ensemble a failed call reruns on: every team member's fallback engine, in member order
+static int ensemble_fallback(bcmpc_ensemble* s, bcmpc_ensemble** r) {
+    if (!s->fb) {
+        s->fb = new bcmpc_ensemble();
+        s->fb->owns = false;
+    }
+    bcmpc_ensemble* f = s->fb;
+    f->m.clear();
+    for (bcmpc_engine* e : s->m) {
+        if (e->kernel == BCMPC_KERNEL_TEAM) {
+            if (const int fr = team_fallback(e)) return fr;
+            f->m.push_back(e->fb);
+        } else {
+            f->m.push_back(e);
+        }
+    }
+    if (!f->d_member)
+        HIP_TRY(hipMalloc(&f->d_member, s->m.size() * (size_t)std::max<int64_t>(1, s->m[0]->cfg.num_paths) * sizeof(double)));
+    f->mode = s->mode;
+    f->kappa = s->kappa;
+    *r = f;
+    return BCMPC_OK;
+}
+
+static bool ensemble_has_team(const bcmpc_ensemble* s) {
+    for (const bcmpc_engine* e : s->m)
+        if (e->kernel == BCMPC_KERNEL_TEAM) return true;
+    return false;
+}
+
+int bcmpc_ensemble_create(const bcmpc_config* cfg, int32_t n_members, bcmpc_ensemble** out) {
+    if (!cfg || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (n_members < 1 || n_members > BCMPC_MAX_MEMBERS)
+        return fail(BCMPC_ERR_ARG, "n_members must be in [1, " + std::to_string(BCMPC_MAX_MEMBERS) + "]");
+    if (cfg->policy_hidden > 0) return fail(BCMPC_ERR_UNSUPPORTED, "ensembles do not cover engines with a fused policy");
+    if (cfg->model == BCMPC_MODEL_REWARD || cfg->cost == BCMPC_COST_REWARD)
+        return fail(BCMPC_ERR_UNSUPPORTED, "ensembles do not cover the reward model / the learned-reward objective");
+    if (cfg->cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_UNSUPPORTED, "ensembles need a fused cost (cheetah or terms)");
+    bcmpc_ensemble* s = new bcmpc_ensemble();
+    for (int i = 0; i < n_members; ++i) {
+        bcmpc_engine* e = nullptr;
+        const int rc = bcmpc_create(cfg, &e);
+        if (rc != BCMPC_OK) {
+            (void)bcmpc_ensemble_destroy(s);
+            return rc;
+        }
+        s->m.push_back(e);
+    }
+    if (hipMalloc(&s->d_member, (size_t)n_members * (size_t)std::max<int64_t>(1, cfg->num_paths) * sizeof(double)) !=
+        hipSuccess) {
+        (void)bcmpc_ensemble_destroy(s);
+        return fail(BCMPC_ERR_HIP, "hipMalloc of the member cost buffer failed");
+    }
+    *out = s;
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_destroy(bcmpc_ensemble* s) {
+    if (!s) return BCMPC_OK;
+    if (!s->m.empty() && s->m[0]->stream) {
+        (void)hipSetDevice(s->m[0]->cfg.device);
+        (void)hipStreamSynchronize(s->m[0]->stream);
+    }
+    if (s->fb) {
+        if (s->fb->d_member) (void)hipFree(s->fb->d_member);
+        delete s->fb;
+    }
+    if (s->d_member) (void)hipFree(s->d_member);
+    if (s->owns)
+        for (bcmpc_engine* e : s->m) (void)bcmpc_destroy(e);
+    delete s;
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_size(const bcmpc_ensemble* s) { return s ? (int)s->m.size() : 0; }
+
+int bcmpc_ensemble_member(bcmpc_ensemble* s, int32_t i, bcmpc_engine** out) {
+    if (!s || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (i < 0 || i >= (int32_t)s->m.size()) return fail(BCMPC_ERR_ARG, "member index out of range");
+    *out = s->m[i];
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_set_rule(bcmpc_ensemble* s, int32_t mode, double kappa) {
+    if (const char* why = ensemble_rule_error(mode, kappa)) return fail(BCMPC_ERR_ARG, why);
+    if (!s) return fail(BCMPC_ERR_ARG, "null argument");
+    s->mode = mode;
+    s->kappa = kappa;
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_reduce_async(bcmpc_engine* e, const double* d_member_costs, int64_t ld, int32_t n_members,
+                                int64_t K, int32_t mode, double kappa, double* d_out, void* stream) {
+    // (scalars first, then pointers: a bad call is answered before any HIP call)
+    if (n_members < 1 || n_members > BCMPC_MAX_MEMBERS)
+        return fail(BCMPC_ERR_ARG, "n_members must be in [1, " + std::to_string(BCMPC_MAX_MEMBERS) + "]");
+    if (const char* why = ensemble_rule_error(mode, kappa)) return fail(BCMPC_ERR_ARG, why);
+    if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
+    if (ld < K) return fail(BCMPC_ERR_ARG, "ld must be >= K");
+    if (!e || !d_member_costs || !d_out) return fail(BCMPC_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return ensemble_reduce_impl(d_member_costs, ld, n_members, K, mode, kappa, d_out, (hipStream_t)stream);
+}
+
+int bcmpc_ensemble_get_action(bcmpc_ensemble* s, const double* state, const double* actions, uint64_t seed,
+                              int64_t cand_offset, bcmpc_result* out, double* costs_out, double* member_costs_out) {
+    if (!s || !state || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = ensemble_call_check(s)) return rc;
+    bcmpc_engine* e0 = s->m[0];
+    const bcmpc_config& c = e0->cfg;
+    const int32_t E = (int32_t)s->m.size();
+    const int64_t K = c.num_paths;
+    if (K == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    HIP_TRY(hipSetDevice(c.device));
+    const EnsembleSync sync_guard(s);
+    hipStream_t st = e0->stream;
+    const double* d_act = nullptr;
+    if (actions) {                                     // one upload, read by every member
+        const size_t n = (size_t)c.horizon * (size_t)K * (size_t)c.action_dim;
+        if (const int rc = actions_buffer(e0, n)) return rc;
+        HIP_TRY(hipMemcpyAsync(e0->d_actions, actions, n * sizeof(double), hipMemcpyHostToDevice, st));
+        d_act = e0->d_actions;
+    }
+    for (int32_t i = 0; i < E; ++i)                    // the state travels in the kernel arguments
+        if (const int rc = rollout_impl(s->m[i], nullptr, 0, d_act, seed, cand_offset, s->d_member + (size_t)i * K,
+                                        nullptr, nullptr, st, nullptr, false, nullptr, state))
+            return rc;
+    if (const int rc = ensemble_reduce_impl(s->d_member, K, E, K, s->mode, s->kappa, e0->d_costs, st)) return rc;
+    // the ordinary argmin launch on v; its record goes straight into mapped host memory
+    e0->want_done = !costs_out && !member_costs_out;
+    const ArgminArgs am = argmin_args(e0, e0->d_costs, d_act, nullptr, seed, cand_offset, e0->d_result_map, nullptr);
+    const bool spin = e0->want_done;
+    e0->want_done = false;
+    HIP_TRY(launch_argmin(am, st));
+    if (costs_out) HIP_TRY(hipMemcpyAsync(costs_out, e0->d_costs, sizeof(double) * K, hipMemcpyDeviceToHost, st));
+    if (member_costs_out)
+        HIP_TRY(hipMemcpyAsync(member_costs_out, s->d_member, sizeof(double) * (size_t)E * K, hipMemcpyDeviceToHost, st));
+    if (spin) {
+        if (const int wr = wait_done(e0, e0->seq)) return wr;
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (ensemble_failed(s)) {                          // a team gave up: the whole call on the fallback engines
+        bcmpc_ensemble* f = nullptr;
+        if (const int fr = ensemble_fallback(s, &f)) return fr;
+        return bcmpc_ensemble_get_action(f, state, actions, seed, cand_offset, out, costs_out, member_costs_out);
+    }
+    *out = *e0->h_result_map;
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_get_actions_batch(bcmpc_ensemble* s, const double* states, int32_t n_envs, const double* actions,
+                                     uint64_t seed, int64_t cand_offset, bcmpc_result* out, double* costs_out,
+                                     double* member_costs_out) {
+    if (!s || !states || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = ensemble_call_check(s)) return rc;
+    bcmpc_engine* e0 = s->m[0];
+    if (const int rc = batch_check(e0, n_envs)) return rc;
+    const bcmpc_config& c = e0->cfg;
+    const int32_t E = (int32_t)s->m.size();
+    const int64_t Ktot = c.num_paths, K = Ktot / n_envs;
+    HIP_TRY(hipSetDevice(c.device));
+    const EnsembleSync sync_guard(s);
+    if (const int rc = batch_buffers(e0, n_envs)) return rc;
+    if (!e0->d_tiled) HIP_TRY(hipMalloc(&e0->d_tiled, (size_t)Ktot * c.state_dim * sizeof(double)));
+    hipStream_t st = e0->stream;
+    HIP_TRY(hipMemcpyAsync(e0->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
+    const double* d_act = nullptr;
+    if (actions) {
+        const size_t n = (size_t)c.horizon * (size_t)Ktot * (size_t)c.action_dim;
+        if (const int rc = actions_buffer(e0, n)) return rc;
+        HIP_TRY(hipMemcpyAsync(e0->d_actions, actions, n * sizeof(double), hipMemcpyHostToDevice, st));
+        d_act = e0->d_actions;
+    }
+    TileStatesArgs t{};
+    t.states = e0->d_bstates; t.out = e0->d_tiled; t.K = K; t.Ktot = Ktot; t.S = c.state_dim;
+    HIP_TRY(launch_tile_states(t, st));
+    for (int32_t i = 0; i < E; ++i)
+        if (const int rc = rollout_impl(s->m[i], e0->d_tiled, c.state_dim, d_act, seed, cand_offset,
+                                        s->d_member + (size_t)i * Ktot, nullptr, nullptr, st, nullptr, false))
+            return rc;
+    if (const int rc = ensemble_reduce_impl(s->d_member, Ktot, E, Ktot, s->mode, s->kappa, e0->d_costs, st)) return rc;
+    SegmentArgminArgs m{};
+    m.costs = e0->d_costs; m.actions = d_act; m.consts = e0->d_consts; m.out = e0->d_bresults;
+    m.seed = seed; m.cand_offset = cand_offset; m.K = K; m.n_envs = n_envs; m.A = c.action_dim;
+    m.maximize = 0;
+    HIP_TRY(launch_argmin_segments(m, st));
+    HIP_TRY(hipMemcpyAsync(e0->h_bresults, e0->d_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
+    if (costs_out) HIP_TRY(hipMemcpyAsync(costs_out, e0->d_costs, sizeof(double) * Ktot, hipMemcpyDeviceToHost, st));
+    if (member_costs_out)
+        HIP_TRY(hipMemcpyAsync(member_costs_out, s->d_member, sizeof(double) * (size_t)E * Ktot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ensemble_failed(s)) {
+        bcmpc_ensemble* f = nullptr;
+        if (const int fr = ensemble_fallback(s, &f)) return fr;
+        return bcmpc_ensemble_get_actions_batch(f, states, n_envs, actions, seed, cand_offset, out, costs_out,
+                                                member_costs_out);
+    }
+    std::memcpy(out, e0->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
+    return BCMPC_OK;
+}
+
+// CEM (p != nullptr) or MPPI (q != nullptr) over the ensemble: bcmpc_cem_get_action's / bcmpc_mppi_get_action's
+// chain with the E rollouts + reduce in place of the one rollout
+static int ensemble_plan(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, const bcmpc_mppi* q, uint64_t seed,
+                         double* mu, double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    bcmpc_engine* e0 = s->m[0];
+    const bcmpc_config& c = e0->cfg;
+    const int32_t E = (int32_t)s->m.size();
+    const int64_t K = c.num_paths;
+    const int32_t iterations = p ? p->iterations : q->iterations;
+    HIP_TRY(hipSetDevice(c.device));
+    const EnsembleSync sync_guard(s);
+    int rc = cem_buffers(e0, p ? p->n_elite : 0);
+    if (rc != BCMPC_OK) return rc;
+    if (q && !e0->d_mppi_stats) HIP_TRY(hipMalloc(&e0->d_mppi_stats, sizeof(bcmpc_mppi_stats)));
+    const size_t ha = (size_t)c.horizon * c.action_dim;
+    hipStream_t st = e0->stream;
+    std::vector<double> mu0, sigma0;                   // (team members: the inputs, for a rerun)
+    if (ensemble_has_team(s)) {
+        mu0.assign(mu, mu + ha);
+        sigma0.assign(sigma, sigma + ha);
+    }
+    HIP_TRY(hipMemcpyAsync(e0->d_state, state, sizeof(double) * c.state_dim, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e0->d_mu, mu, ha * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e0->d_sigma, sigma, ha * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int it = 0; it < iterations; ++it) {
+        const CemLaunch cl{e0->d_mu, e0->d_sigma, it, it > 0, (int64_t)it * K};
+        for (int32_t i = 0; i < E; ++i) {
+            rc = rollout_impl(s->m[i], e0->d_state, 0, nullptr, seed, 0, s->d_member + (size_t)i * K, nullptr, nullptr, st,
+                              &cl, false);
+            if (rc != BCMPC_OK) return rc;
+        }
+        rc = ensemble_reduce_impl(s->d_member, K, E, K, s->mode, s->kappa, e0->d_costs, st);
+        if (rc != BCMPC_OK) return rc;
+        HIP_TRY(launch_argmin(argmin_args(e0, e0->d_costs, nullptr, nullptr, seed, 0, e0->d_result, &cl), st));
+        if (p) {
+            rc = select_impl(e0, nullptr, e0->d_costs, K, 0, p->n_elite, e0->d_elite, e0->d_count, st);
+            if (rc != BCMPC_OK) return rc;
+            rc = refit_impl(e0, e0->d_elite, e0->d_count, seed, it, p->alpha, e0->d_mu, e0->d_sigma, st);
+        } else {
+            rc = mppi_update_impl(e0, e0->d_costs, K, 0, seed, it, q->lambda, e0->d_mu, e0->d_sigma, e0->d_mppi_stats, st);
+        }
+        if (rc != BCMPC_OK) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(e0->h_result, e0->d_result, sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mu, e0->d_mu, ha * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (p) HIP_TRY(hipMemcpyAsync(sigma, e0->d_sigma, ha * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (q) HIP_TRY(hipMemcpyAsync(stats, e0->d_mppi_stats, sizeof(*stats), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ensemble_failed(s)) {
+        bcmpc_ensemble* f = nullptr;
+        if (const int fr = ensemble_fallback(s, &f)) return fr;
+        std::memcpy(mu, mu0.data(), ha * sizeof(double));
+        if (p) std::memcpy(sigma, sigma0.data(), ha * sizeof(double));
+        return ensemble_plan(f, state, p, q, seed, mu, sigma, out, stats);
+    }
+    *out = *e0->h_result;
+    return BCMPC_OK;
+}
+
+int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, uint64_t seed,
+                                  double* mu, double* sigma, bcmpc_result* out) {
+    if (!s || !state || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = ensemble_call_check(s)) return rc;
+    const bcmpc_config& c = s->m[0]->cfg;
+    if (p->iterations < 1 || p->iterations > (1 << 22)) return fail(BCMPC_ERR_ARG, "iterations must be in [1, 2^22]");
+    if (p->n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (p->k_global != 0 && p->k_global != c.num_paths)
+        return fail(BCMPC_ERR_ARG, "ensemble CEM: k_global must be 0 or num_paths");
+    if (c.num_paths == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    return ensemble_plan(s, state, p, nullptr, seed, mu, sigma, out, nullptr);
+}
+
+int bcmpc_ensemble_mppi_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_mppi* q, uint64_t seed,
+                                   double* mu, const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    if (!s || !state || !q || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = ensemble_call_check(s)) return rc;
+    const bcmpc_config& c = s->m[0]->cfg;
+    if (q->iterations < 1 || q->iterations > (1 << 22)) return fail(BCMPC_ERR_ARG, "iterations must be in [1, 2^22]");
+    if (!(std::isfinite(q->lambda) && q->lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (q->k_global != 0 && q->k_global != c.num_paths)
+        return fail(BCMPC_ERR_ARG, "ensemble MPPI: k_global must be 0 or num_paths");
+    if (c.num_paths == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    // (MPPI reads sigma only: the shared chain never writes it back on this path)
+    return ensemble_plan(s, state, nullptr, q, seed, mu, const_cast<double*>(sigma), out, stats);
 }
 
 int bcmpc_engine_set_comm(bcmpc_engine* e, bcmpc_comm* comm) {

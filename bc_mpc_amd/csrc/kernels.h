@@ -284,6 +284,16 @@ struct TermCostArgs {
 };
 hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);
 
+// ---- model ensembles (ensemble.hip): out[k] = rule over member_costs[0..E-1][k] ----
+struct EnsembleReduceArgs {
+    const double* member_costs;              // [E][ld], row e = member e's costs
+    double* out;                             // [K]
+    int64_t ld, K;                           // ld >= K
+    int32_t E, mode;                         // 1 <= E <= BCMPC_MAX_MEMBERS; bcmpc_ensemble_mode
+    double kappa;                            // MEAN_STD only
+};
+hipError_t launch_ensemble_reduce(const EnsembleReduceArgs& a, hipStream_t st);
+
 hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);
 hipError_t launch_argmin_segments(const SegmentArgminArgs& a, hipStream_t st);
 

@@ -137,6 +137,59 @@ def _legacy_mt_state():
     return _MT_STATE[0] if ok else None
 
 
+def _engine_config(state_dim: int, action_dim: int, hidden: int, n_layers: int, activation: str, layer_norm: bool,
+                   horizon: int, num_paths: int, device: int, cost: str, kernel: Optional[str], policy_hidden: int,
+                   policy_layers: int, policy_mode: str, model: str, precision: Optional[str]):
+    """The bcmpc_config of RolloutEngine's constructor arguments (and of ensemble.EnsembleEngine's): returns
+    (config, resolved precision name, whether a refused split-precision create is retried in fp32)."""
+    if activation not in _ACT:
+        raise ValueError(f"unsupported activation {activation!r} (tanh | relu)")
+    cfg = _lib.Config()
+    cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.n_layers = state_dim, action_dim, hidden, n_layers
+    cfg.activation = _ACT[activation]
+    cfg.layer_norm = int(bool(layer_norm))
+    cfg.horizon = int(horizon)
+    costs = {"cheetah": _lib.COST_CHEETAH, "none": _lib.COST_NONE, "reward": _lib.COST_REWARD,
+             "terms": _lib.COST_TERMS}
+    models = {"delta": _lib.MODEL_DELTA, "reward": _lib.MODEL_REWARD}
+    if cost not in costs or model not in models:
+        raise ValueError(f"cost must be one of {sorted(costs)}, model one of {sorted(models)}")
+    cfg.cost, cfg.model = costs[cost], models[model]
+    cfg.num_paths = int(num_paths)
+    cfg.device = int(device)
+    kernel = kernel or os.environ.get("BCMPC_KERNEL", "auto")
+    if kernel not in _lib.KERNELS:
+        raise ValueError(f"unknown kernel {kernel!r}; one of {sorted(_lib.KERNELS)}")
+    cfg.kernel = _lib.KERNELS[kernel]
+    if precision is None:
+        precision = "split" if kernel.startswith("split") or kernel == "team" else os.environ.get("BCMPC_PRECISION", "auto")
+    if precision == "auto":
+        # a fused policy runs in the split kernel's 8-wave groups (dynamics hidden 449..1024;
+        # the reward net: hidden <= 512)
+        top = 512 if model == "reward" else 1024
+        plain = activation == "tanh" and not layer_norm
+        split_ok = ((plain or (model == "delta" and not policy_hidden and hidden <= 512))
+                    and (model == "delta" or state_dim >= 16)
+                    and (not policy_hidden or 448 < hidden <= top)
+                    and kernel in ("auto", "split1", "split2", "split4", "team"))
+        # the small-K team kernel also takes relu / LayerNorm dynamics under a fused policy (hidden
+        # <= 256: train_mpc_ppo.py's 2x256 relu + LN net) and the LayerNorm reward net (the run.sh
+        # recipe) when its grid is resident: tried in split, fp32 when bcmpc_create refuses
+        team_try = (not split_ok and kernel == "auto" and n_layers == 2 and state_dim >= 16
+                    and bool(policy_hidden or model == "reward"))
+        precision = "split" if split_ok or team_try else "fp32"
+    else:
+        team_try = False
+    if precision not in _lib.PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; one of {sorted(_lib.PRECISIONS)}")
+    cfg.precision = _lib.PRECISIONS[precision]
+    if policy_mode not in _lib.POLICY_MODES:
+        raise ValueError(f"unknown policy_mode {policy_mode!r}")
+    cfg.policy_hidden, cfg.policy_layers = int(policy_hidden), int(policy_layers)
+    cfg.policy_mode = _lib.POLICY_MODES[policy_mode]
+    return cfg, precision, team_try
+
+
 class RolloutEngine:
     """Owns one bcmpc_engine (one device, one candidate shard of size K)."""
 
@@ -157,52 +210,10 @@ class RolloutEngine:
         where it applies, else fp32).
         Default: "split" for the split* kernels, else $BCMPC_PRECISION or "auto"."""
         self._lib = _lib.load()
-        if activation not in _ACT:
-            raise ValueError(f"unsupported activation {activation!r} (tanh | relu)")
-        cfg = _lib.Config()
-        cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.n_layers = state_dim, action_dim, hidden, n_layers
-        cfg.activation = _ACT[activation]
-        cfg.layer_norm = int(bool(layer_norm))
-        cfg.horizon = int(horizon)
-        costs = {"cheetah": _lib.COST_CHEETAH, "none": _lib.COST_NONE, "reward": _lib.COST_REWARD,
-                 "terms": _lib.COST_TERMS}
-        models = {"delta": _lib.MODEL_DELTA, "reward": _lib.MODEL_REWARD}
-        if cost not in costs or model not in models:
-            raise ValueError(f"cost must be one of {sorted(costs)}, model one of {sorted(models)}")
-        cfg.cost, cfg.model = costs[cost], models[model]
-        cfg.num_paths = int(num_paths)
-        cfg.device = int(device)
-        kernel = kernel or os.environ.get("BCMPC_KERNEL", "auto")
-        if kernel not in _lib.KERNELS:
-            raise ValueError(f"unknown kernel {kernel!r}; one of {sorted(_lib.KERNELS)}")
-        cfg.kernel = _lib.KERNELS[kernel]
-        if precision is None:
-            precision = "split" if kernel.startswith("split") or kernel == "team" else os.environ.get("BCMPC_PRECISION", "auto")
-        if precision == "auto":
-            # a fused policy runs in the split kernel's 8-wave groups (dynamics hidden 449..1024;
-            # the reward net: hidden <= 512)
-            top = 512 if model == "reward" else 1024
-            plain = activation == "tanh" and not layer_norm
-            split_ok = ((plain or (model == "delta" and not policy_hidden and hidden <= 512))
-                        and (model == "delta" or state_dim >= 16)
-                        and (not policy_hidden or 448 < hidden <= top)
-                        and kernel in ("auto", "split1", "split2", "split4", "team"))
-            # the small-K team kernel also takes relu / LayerNorm dynamics under a fused policy (hidden
-            # <= 256: train_mpc_ppo.py's 2x256 relu + LN net) and the LayerNorm reward net (the run.sh
-            # recipe) when its grid is resident: tried in split, fp32 when bcmpc_create refuses
-            team_try = (not split_ok and kernel == "auto" and n_layers == 2 and state_dim >= 16
-                        and bool(policy_hidden or model == "reward"))
-            precision = "split" if split_ok or team_try else "fp32"
-        else:
-            team_try = False
-        if precision not in _lib.PRECISIONS:
-            raise ValueError(f"unknown precision {precision!r}; one of {sorted(_lib.PRECISIONS)}")
-        cfg.precision = _lib.PRECISIONS[precision]
+        cfg, precision, team_try = _engine_config(state_dim, action_dim, hidden, n_layers, activation, layer_norm,
+                                                  horizon, num_paths, device, cost, kernel, policy_hidden,
+                                                  policy_layers, policy_mode, model, precision)
         self.precision = precision
-        if policy_mode not in _lib.POLICY_MODES:
-            raise ValueError(f"unknown policy_mode {policy_mode!r}")
-        cfg.policy_hidden, cfg.policy_layers = int(policy_hidden), int(policy_layers)
-        cfg.policy_mode = _lib.POLICY_MODES[policy_mode]
         h = ctypes.c_void_p()
         rc = self._lib.bcmpc_create(ctypes.byref(cfg), ctypes.byref(h))
         if rc == _lib.ERR_UNSUPPORTED and team_try:

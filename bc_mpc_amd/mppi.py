@@ -130,6 +130,9 @@ class MPPIcontroller(_BatchPlans, Controller):
         return self._engine
 
     def get_action(self, state):
+        if getattr(self.dyn_model, "is_ensemble", False):   # an EnsembleDynamicsModel (ensemble.py)
+            from . import ensemble as _ensemble
+            return _ensemble.mppi_get_action(self, state)
         S = int(math.prod(self.env.observation_space.shape))
         A = len(self.env.action_space.high)
         K = int(self.num_simulated_paths)
@@ -168,6 +171,8 @@ class MPPIcontroller(_BatchPlans, Controller):
         ``reset``); one seed is drawn per call.  Returns ``[B, A]`` float64: ``mu'[b, 0]``.  ``last_mu``
         (``[B, H, A]``), ``last_ess`` / ``last_cost`` / ``last_position`` (``[B]``) and ``last_stats`` (a
         ``[B]`` record array) describe the call.  One rank only."""
+        if getattr(self.dyn_model, "is_ensemble", False):
+            raise NotImplementedError("batched MPPI over an EnsembleDynamicsModel is not built yet: use get_action")
         S = int(math.prod(self.env.observation_space.shape))
         A = len(self.env.action_space.high)
         K = int(self.num_simulated_paths)

@@ -529,6 +529,69 @@ int bcmpc_mppi_update_batch_async(bcmpc_engine* eng, const double* d_costs, int3
                                   void* stream);
 
 /* ------------------------------------------------------------------------
+ * Model ensembles (additive to ABI 5; callers detect them by the symbol bcmpc_ensemble_create; not in
+ * the reference, semantics in DESIGN.md 9g).  An ensemble holds E dynamics nets of one architecture and
+ * one configuration -- E member engines of the same config, hence the same kernel layout.  Candidate k
+ * of a call has ONE action sequence (the explicit array's column, the Philox draw at cand_offset + k, or
+ * the CEM / MPPI sample at that index); member e scores it as c[e][k], bit for bit what a single engine
+ * holding member e's weights returns; the candidate's value is
+ *   MEAN      t = c[0]; for e = 1..E-1: t = t + c[e]; v = t / E
+ *   MEAN_STD  m as above; q = 0.0; for e = 0..E-1: d = c[e] - m; q = q + d * d; v = m + kappa * sqrt(q / E)
+ *   WORST     np.maximum.reduce(c): the largest member cost, NaN if any member's is NaN
+ * every operation an individually rounded IEEE f64 operation (no contraction; division and square root
+ * correctly rounded).  MEAN starts from c[0]: E == 1 returns c[0]'s bits.  The argmin, CEM's elite
+ * selection and refit and the MPPI update then run on v with the rules they have on a single engine's
+ * costs (a NaN value wins the argmin).
+ * Launch order: everything on member 0's stream -- per iteration the members' rollouts in member order,
+ * each into its row of an ensemble-owned [E][num_paths] buffer (allocated at create), the reduce into
+ * member 0's cost vector, the ordinary argmin, then select + refit or the MPPI update.  Members never run
+ * concurrently.  One host synchronisation per call.  Team-kernel members: if any member's team gave up,
+ * the whole call reruns on the members' fallback engines from the saved inputs (the answer is then that
+ * of an ensemble of the fallback layout).
+ * Not covered: a fused policy, the reward model / BCMPC_COST_REWARD, BCMPC_COST_NONE (create returns
+ * BCMPC_ERR_UNSUPPORTED); batched CEM / MPPI; members with a communicator attached (refused at call time). */
+#define BCMPC_MAX_MEMBERS 16
+typedef enum bcmpc_ensemble_mode {
+    BCMPC_ENSEMBLE_MEAN = 0,
+    BCMPC_ENSEMBLE_MEAN_STD = 1,
+    BCMPC_ENSEMBLE_WORST = 2
+} bcmpc_ensemble_mode;
+
+typedef struct bcmpc_ensemble bcmpc_ensemble;
+
+/* 1 <= n_members <= BCMPC_MAX_MEMBERS, else BCMPC_ERR_ARG (checked before any HIP call). */
+int bcmpc_ensemble_create(const bcmpc_config* cfg, int32_t n_members, bcmpc_ensemble** out);
+int bcmpc_ensemble_destroy(bcmpc_ensemble* ens);
+int bcmpc_ensemble_size(const bcmpc_ensemble* ens);   /* E, or 0 for NULL */
+/* Member i, lent out (owned by the ensemble) for bcmpc_set_weights, bcmpc_set_cost_terms,
+ * bcmpc_set_action_bounds, bcmpc_engine_info, bcmpc_engine_layout, bcmpc_engine_team_reruns. */
+int bcmpc_ensemble_member(bcmpc_ensemble* ens, int32_t i, bcmpc_engine** out);
+/* The rule of the following calls (default MEAN, kappa 0).  BCMPC_ERR_ARG: unknown mode, kappa not finite. */
+int bcmpc_ensemble_set_rule(bcmpc_ensemble* ens, int32_t mode, double kappa);
+
+/* bcmpc_get_action over the ensemble.  costs_out: optional [K] values v; member_costs_out: optional
+ * [E][K] member costs.  out->best_cost is v[best]. */
+int bcmpc_ensemble_get_action(bcmpc_ensemble* ens, const double* state, const double* actions, uint64_t seed,
+                              int64_t cand_offset, bcmpc_result* out, double* costs_out, double* member_costs_out);
+/* bcmpc_get_actions_batch over the ensemble (segment layout as there): costs_out [num_paths] values,
+ * member_costs_out [E][num_paths]. */
+int bcmpc_ensemble_get_actions_batch(bcmpc_ensemble* ens, const double* states, int32_t n_envs,
+                                     const double* actions, uint64_t seed, int64_t cand_offset, bcmpc_result* out,
+                                     double* costs_out, double* member_costs_out);
+/* bcmpc_cem_get_action / bcmpc_mppi_get_action over the ensemble: every iteration's elites / weights
+ * come from v. */
+int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* ens, const double* state, const bcmpc_cem* params, uint64_t seed,
+                                  double* mu, double* sigma, bcmpc_result* out);
+int bcmpc_ensemble_mppi_get_action(bcmpc_ensemble* ens, const double* state, const bcmpc_mppi* params,
+                                   uint64_t seed, double* mu, const double* sigma, bcmpc_result* out,
+                                   bcmpc_mppi_stats* stats);
+/* The reduce alone (device pointers, stream-ordered, allocates nothing; `eng` names the device):
+ * d_member_costs [n_members][ld] (ld >= K), d_out [K].  BCMPC_ERR_ARG: null pointers, n_members outside
+ * [1, BCMPC_MAX_MEMBERS], K < 1, ld < K, unknown mode, kappa not finite. */
+int bcmpc_ensemble_reduce_async(bcmpc_engine* eng, const double* d_member_costs, int64_t ld, int32_t n_members,
+                                int64_t K, int32_t mode, double kappa, double* d_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * NNDynamicsModel.fit (dynamics.py:81-104) on the GPU:
  * `iterations` Adam steps (TF1 AdamOptimizer, dynamics.py:50-52) on the mean
  * squared error of the normalised state deltas, batches gathered on the device
