@@ -150,6 +150,19 @@ void announce_test_hook(const char* name, const char* value) {
 }  // namespace bcmpc
 
 static thread_local bool g_no_team = false;         // bcmpc_create: never pick the team kernel (fallbacks)
+static thread_local bool g_no_pp3 = false;          // bcmpc_create: never pick rollout_pp3 (ensemble members)
+
+// BCMPC_SPLIT_PP: 1 forces the two-group pipelined split kernel (rollout_pp3) at any K, 0 turns it off, unset
+// leaves the choice to kernel="auto" (kSplitPpAutoCols candidate columns and more, horizon >= kSplitPpAutoMinH)
+// (the A/B that places the column threshold.  The horizon: the two-group pipeline runs 2H + 2
+//  barrier intervals for 2H segments of work, each interval 0.90 of a rollout_x3 step per 128 candidates at
+//  cfg3, so it breaks even at H = 10 and clears 3% from H = 14)
+constexpr int64_t kSplitPpAutoCols = 2048;
+constexpr int kSplitPpAutoMinH = 14;
+static int split_pp_env() {
+    const char* v = std::getenv("BCMPC_SPLIT_PP");
+    return !(v && *v) ? -1 : v[0] == '1' ? 1 : 0;
+}
 
 struct bcmpc_engine {
     bcmpc_config cfg{};
@@ -162,6 +175,8 @@ struct bcmpc_engine {
     bool pp = false;                   // BCMPC_PREC_F16 on the two-group pipelined kernel (rollout_pp)
     bool pp_fold = false;              // ... with the folded operands (rollout_pp<, FOLD>; BCMPC_PP_FOLD=0: off)
     bool pp_fold_w = false;            //     active for the current weights (|W| x 2 log2 e within f16's range)
+    bool pp3 = false;                  // BCMPC_PREC_SPLIT_F16 on the two-group pipelined kernel (rollout_pp3): the
+                                       // launches it implements; the others run rollout_x3 on the same weights
     int nc = 0;                        // split kernel: 16-candidate columns per workgroup
     int nwl = 0;                       // packed weight layers (RolloutArgs.w entries)
     float winv[BCMPC_MAX_LAYERS + 1]{};  // split kernel: 1 / operand scales per layer
@@ -483,6 +498,15 @@ int bcmpc_create(const bcmpc_config* cfg, bcmpc_engine** out) {
         const char* ev = std::getenv("BCMPC_TEAM");
         use_team = !(ev && ev[0] == '0');
     }
+    // rollout_pp3 (two 64-candidate groups pipelined over one slab): the plain 2-layer tanh delta net at hidden
+    // 512 under kernel="auto"; cost terms and ensemble members stay on rollout_x3.  Forced, it also replaces the
+    // small-K team kernel
+    const int pp3_env = split_pp_env();
+    const bool pp3_shape = split && !f16 && !reward && e->PL == 0 && c.kernel == BCMPC_KERNEL_AUTO && !g_no_pp3 &&
+                           c.activation == BCMPC_ACT_TANH && !c.layer_norm && c.cost != BCMPC_COST_TERMS &&
+                           c.horizon >= 1 && x3_pp3_ok(e->HP, c.n_layers, c.state_dim, c.action_dim);
+    const bool pp3_forced = pp3_shape && pp3_env == 1 && c.num_paths >= 1;
+    if (pp3_forced) use_team = false;
     if (use_team) {
         e->split = true;
         e->nc = 1;
@@ -553,6 +577,11 @@ int bcmpc_create(const bcmpc_config* cfg, bcmpc_engine** out) {
             // (hidden <= 256: 32-candidate groups, two or three workgroups per CU, measured 6-18% ahead of 64)
             for (int n : {4, 2})
                 if (fits(n) && cols >= (int64_t)n * 256 && !(n == 4 && e->HP <= 256)) { nc = n; break; }
+            // rollout_pp3 reads rollout_x3<512, NC=4, NW=8>'s packed weights: the engine stays a split4 engine
+            if (pp3_shape && nwx == 8 && fits(4) && (pp3_forced || (pp3_env != 0 && cols >= kSplitPpAutoCols && c.horizon >= kSplitPpAutoMinH))) {
+                e->pp3 = true;
+                nc = 4;
+            }
         }
         if (!f16 && !fits(nc)) {
             delete e;
@@ -1628,7 +1657,9 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
         static size_t st_n = 0;
         const bool stamps = diag_env("BCMPC_X3_STAMPS") != nullptr;
         const int nw = e->nw;
-        const size_t blocks = (size_t)((c.num_paths + 16 * e->nc - 1) / (16 * e->nc));
+        const bool pp3 = e->pp3 && !terms && x3_pp3_args_ok(a, e->HP);
+        const int cpb = pp3 ? 128 : 16 * e->nc;           // candidates per workgroup
+        const size_t blocks = (size_t)((c.num_paths + cpb - 1) / cpb);
         if (stamps) {
             if (st_n < blocks * nw * 10) {
                 if (d_st) (void)hipFree(d_st);
@@ -1638,12 +1669,17 @@ static int rollout_impl(bcmpc_engine* e, const double* d_state, int64_t stride, 
             HIP_TRY(hipMemsetAsync(d_st, 0, st_n * sizeof(uint64_t), st));
             a.stamps = d_st;
         }
-        HIP_TRY(e->f16 ? launch_rollout_x3_f16(a, e->HP, e->nc, st) : launch_rollout_x3(a, e->HP, e->nc, st));
+        HIP_TRY(e->f16 ? launch_rollout_x3_f16(a, e->HP, e->nc, st)
+                : pp3  ? launch_rollout_pp3(a, e->HP, st)
+                       : launch_rollout_x3(a, e->HP, e->nc, st));
         if (stamps) {
             std::vector<uint64_t> h(blocks * nw * 10);
             HIP_TRY(hipMemcpyAsync(h.data(), d_st, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            const char* names[10] = {"owner", "input", "B1", "layer0", "slab", "mm", "epi", "out", "B3B4", "-"};
+            const char* names_x3[10] = {"owner", "input", "B1", "layer0", "slab", "mm", "epi", "out", "B3B4", "-"};
+            const char* names_pp3[10] = {"EC:tanh+out", "EC:wait", "EC:owner", "EC:layer0", "M:slab+wait", "M:mm", "-",
+                                         "barrier", "-", "-"};
+            const char* const* names = pp3 ? names_pp3 : names_x3;
             // (waves 0..nw/2-1, the older half that wins the MFMA / VALU arbitration, vs the younger half)
             for (int grp = 0; grp < 2; ++grp) {
                 std::fprintf(stderr, "x3 stamps %s:", grp == 0 ? "waves<nw/2 " : "waves>=nw/2");
@@ -3246,7 +3282,9 @@ int bcmpc_ensemble_create(const bcmpc_config* cfg, int32_t n_members, bcmpc_ense
     bcmpc_ensemble* s = new bcmpc_ensemble();
     for (int i = 0; i < n_members; ++i) {
         bcmpc_engine* e = nullptr;
+        g_no_pp3 = true;                              // (members run rollout_x3: DESIGN.md 6.9)
         const int rc = bcmpc_create(cfg, &e);
+        g_no_pp3 = false;
         if (rc != BCMPC_OK) {
             (void)bcmpc_ensemble_destroy(s);
             return rc;
@@ -3550,11 +3588,19 @@ int bcmpc_engine_layout(const bcmpc_engine* e, char* buf, int32_t cap) {
         default:
             if (e->pp)
                 std::snprintf(s, sizeof(s), "rollout_pp<%d%s> %s", e->HP, e->pp_fold_w ? ",fold" : "", prec);
+            else if (e->pp3)
+                std::snprintf(s, sizeof(s), "rollout_pp3<%d> %s", e->HP, prec);
             else
                 std::snprintf(s, sizeof(s), "rollout_x3<%d,NC=%d,NW=%d> %s", e->HP, e->nc, e->nw, prec);
     }
     std::snprintf(buf, (size_t)cap, "%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "");
     return BCMPC_OK;
+}
+
+int64_t bcmpc_split_pp_lds_bytes(int32_t hidden, int32_t n_layers, int32_t state_dim, int32_t action_dim) {
+    if (hidden < 1 || hidden > 1024) return -1;
+    const int hp = padded_hidden(hidden);
+    return x3_pp3_ok(hp, n_layers, state_dim, action_dim) ? (int64_t)x3_pp3_lds(hp, state_dim, action_dim) : -1;
 }
 
 int bcmpc_engine_info(const bcmpc_engine* e, int32_t* hidden_padded, int64_t* packed_weight_bytes,

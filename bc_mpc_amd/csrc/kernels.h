@@ -218,6 +218,12 @@ bool x3_policy_ok(int hidden_padded, int nc);
 bool x3_f16_layout_ok(int hidden_padded, int nc, int nw);
 size_t x3_f16_lds(int hidden_padded, int n_layers, int nc, int nw, int action_dim);
 bool x3_pp_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);   // rollout_pp's shapes
+// split precision on the two-group pipelined kernel (rollout_pp3): its shapes, its LDS bytes, the launch
+// arguments it implements (every other launch runs rollout_x3 on the same packed weights)
+bool x3_pp3_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);
+size_t x3_pp3_lds(int hidden_padded, int state_dim, int action_dim);
+bool x3_pp3_args_ok(const RolloutArgs& a, int hidden_padded);
+hipError_t launch_rollout_pp3(const RolloutArgs& a, int hidden_padded, hipStream_t st);
 hipError_t launch_rollout_x3(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
 hipError_t launch_rollout_x3_f16(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
 // rollout_team.hip; kind: 0 the plain delta net, 1 + fused policy, 2 the reward net (+ policy)

@@ -1919,8 +1919,433 @@ void rollout_pp(const RolloutArgs a) {
     }
 }
 
+// ----------------------------------------------------------- rollout_pp3 ----
+// Split precision (hi + lo operands, three MFMA passes) as rollout_pp's two-group pipeline over ONE
+// time-shared slab.  A 512-thread workgroup holds two 64-candidate groups, waves 0-3 and
+// 4-7 (waves w and w + 4 share a SIMD); within a group wave wl owns candidate column wl (all 32 state
+// dims) and hidden tiles [8wl, 8wl + 8) of all four columns.  A group's control step is two segments:
+//   M   its own column of the hidden-layer input (packed hi | lo pairs, in registers since the previous
+//       interval) into the slab, the group's "inputs published" counter, the hidden layer (16 k-steps x
+//       8 tiles x 4 columns x 3 passes); the accumulators stay in registers across the barrier;
+//   EC  tanh + split of those accumulators, the K-split output layer from registers, the partials into
+//       their own region, the group's "partials published" counter, the four partials summed in fixed
+//       wave order, f64 de-normalise + residual + cost, the next input (column power-of-two scale,
+//       split), layer 0 for the wave's OWN column from registers (all 32 tiles, no slab), its tanh and
+//       split -- which stay in the registers the accumulators occupied.
+// Every segment ends at the workgroup barrier and group 1 runs one segment ahead, so every interval
+// pairs one group's M (the matrix pipe) with the other's EC (the VALU).  At the barrier the M group has
+// finished reading the slab and the EC group everything, so the one slab and the one partials region are
+// never live for both groups.  The 128 registers R carry the hidden accumulators out of M and the packed
+// layer-0 output out of EC.  Weights in rollout_x3's NW = 8 packing (4 tiles per block: wave wl reads the
+// blocks 2wl and 2wl + 1), so an engine can launch either kernel on the same buffers.  Arithmetic as
+// rollout_x3; the output partials are four sums of four k-steps (there: eight of two).
+// wave priority per segment (s_setprio).  The interval is bound by EC, one in-order wave's VALU chain beside its
+// SIMD partner's MFMAs (stamps: EC 40.1k ticks, M 32.0k + 8.4k at the barrier, profiles/pp3_stamps.txt), so EC goes
+// first: cfg3 1.736 / 1.741 ms per step against 1.759 / 1.763 with equal priorities and 1.789 / 1.789 with M first
+// (M at 2: 1.790 / 1.791; profiles/pp3_prio_ab.txt)
+#ifndef PP3_PRIO_M
+#define PP3_PRIO_M 0
+#endif
+#ifndef PP3_PRIO_EC
+#define PP3_PRIO_EC 1
+#endif
+// a scheduling barrier that only vector-memory instructions cannot cross: the weight loads of the unrolled
+// EC phases stay in their slots (without it the scheduler issues every fragment load of a phase up front and
+// spills), the MFMAs and the VALU around them still interleave
+#define PP3_PIN_LOADS() __builtin_amdgcn_sched_barrier(0x78F)
+// LDS: consts | biases | slab [P][4 columns][hi|lo] | tile-0 partials [4 waves][4 columns][64 lanes] |
+// tile-1 partials, the lane rows that hold a state dim only [4][4][16 x rows] | action inputs of one step
+// [2 groups][64][A] | counters [2 groups][2]
+__host__ __device__ constexpr int pp3_xa_bytes(int A) { return (64 * A * 4 + 15) & ~15; }
+__host__ __device__ constexpr int pp3_tile1_rows(int S) { return S > 16 ? (S - 16 + 3) / 4 : 0; }
+__host__ __device__ constexpr int pp3_part_bytes(int S) { return 16 * (1024 + 256 * pp3_tile1_rows(S)); }
+__host__ __device__ constexpr int pp3_lds_total(int HP, int S, int A) {
+    return param_bytes(2, HP) + (HP / 32) * 4 * 2048 + pp3_part_bytes(S) + 2 * pp3_xa_bytes(A) + 16;
+}
+
+template <int HP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void rollout_pp3(const RolloutArgs a) {
+    constexpr int NC = 4;                         // 16-candidate columns per group
+    constexpr int T = HP / 16, P = T / 2;         // hidden tiles, k-steps
+    constexpr int TW = T / 4, PW = TW / 2;        // per wave (4 waves per group)
+    constexpr int CB = 16 * NC;                   // candidates per group
+    static_assert(T == 32 && TW == 8 && PW == 4, "hidden 512");
+    extern __shared__ __attribute__((aligned(16))) f4 lds[];
+
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = w >> 2, wl = w & 3;
+    // (q, m: re-derived from an opaque copy of the lane index after every M segment, so that nothing derived
+    //  from them stays in registers across the hidden layer, where the accumulators and operand sets fill the file)
+    int ln = lane, q = lane >> 4, m = lane & 15;
+    const int64_t gc0 = (int64_t)blockIdx.x * (2 * CB) + grp * CB;     // the group's first candidate
+    const int64_t cand = gc0 + 16 * wl + m;                           // this lane's candidate (column wl)
+    const bool valid = cand < a.K;
+    const int S = a.S, A = a.A;
+    const int nq1 = pp3_tile1_rows(S);            // lane rows of output tile 1 that hold a state dim
+
+    double* C = reinterpret_cast<double*>(lds);
+    float* Bl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + kConstRows * kConstCols * 8);
+    for (int i = threadIdx.x; i < kConstRows * kConstCols; i += blockDim.x) C[i] = a.consts[i];
+    for (int l = 0; l < 2; ++l)
+        for (int i = threadIdx.x; i < HP; i += blockDim.x) Bl[l * HP + i] = a.b[l][i] * kTanhK;
+    float* const Bout = Bl + 2 * HP;
+    for (int i = threadIdx.x; i < 32; i += blockDim.x) Bout[i] = a.b[2][i];
+    f4* const slab = reinterpret_cast<f4*>(reinterpret_cast<char*>(lds) + param_bytes(2, HP));
+    f4* const part0 = slab + P * NC * 2 * 64;
+    f4* const part1 = part0 + 4 * NC * 64;
+    float* const xa = reinterpret_cast<float*>(part1 + 4 * NC * 16 * nq1) + grp * (pp3_xa_bytes(A) / 4);
+    int* const cnt0 = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + pp3_lds_total(HP, S, A) - 16);
+    int* const cnt = cnt0 + 2 * grp;              // [0] M's inputs published, [1] EC's partials published
+    if (threadIdx.x < 4) cnt0[threadIdx.x] = 0;
+
+    // lane (q, m) holds dims 16k + 4q + r (k = 0, 1) of its candidate: the MFMA B-fragment order
+    double s[2][4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = 16 * k + 4 * q + r;
+            s[k][r] = (valid && d < S) ? (a.state_inline ? a.state_v[d] : a.state[cand * a.state_stride + d]) : 0.0;
+        }
+    if (a.traj && valid) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int d = 16 * k + 4 * q + r;
+                if (d < S) a.traj[cand * S + d] = s[k][r];
+            }
+    }
+    double cost = 0.0;                                  // trajectory_cost = 0 (cost_functions.py:60)
+
+    // the group's action inputs of step h: f64 normalise (dynamics.py:110), f32 (the TF feed); the group's
+    // 256 threads
+    const int gt = threadIdx.x - 256 * grp;
+    auto fill_actions = [&](int h) __attribute__((always_inline)) {
+        if (!a.cem_mu && !a.actions) {
+            const int AP = (A + 1) >> 1;
+            for (int i = gt; i < CB * AP; i += 256) {
+                const int kl = i / AP, p2 = i - kl * AP;
+                const int j0 = 2 * p2, j1 = min(2 * p2 + 1, A - 1);
+                float x0 = 0.f, x1 = 0.f;
+                if (gc0 + kl < a.K) {
+                    double v0, v1;
+                    rng_action_pair(a.seed, (uint64_t)(a.cand_offset + gc0 + kl), h, p2, C[6 * 32 + j0],
+                                    C[7 * 32 + j0], C[6 * 32 + j1], C[7 * 32 + j1], v0, v1);
+                    x0 = (float)div_rn(__dsub_rn(v0, C[2 * 32 + j0]), C[3 * 32 + j0], C[9 * 32 + j0]);
+                    x1 = (float)div_rn(__dsub_rn(v1, C[2 * 32 + j1]), C[3 * 32 + j1], C[9 * 32 + j1]);
+                }
+                float* const dst = xa + kl * A;
+                dst[j0] = x0;
+                if (2 * p2 + 1 < A) dst[j1] = x1;
+            }
+            return;
+        }
+        for (int i = gt; i < CB * A; i += 256) {
+            const int kl = i / A, j = i - kl * A;
+            float xv = 0.f;
+            if (gc0 + kl < a.K) {
+                const int64_t c = gc0 + kl;
+                const uint64_t gg = (uint64_t)(a.cand_offset + c);
+                const double v = a.cem_mu ? cem_action(a.seed, gg, h, j, a.cem_iter, a.cem_mu[h * A + j],
+                                                       a.cem_sigma[h * A + j], C[6 * 32 + j], C[7 * 32 + j])
+                                          : a.actions[((int64_t)h * a.K + c) * A + j];
+                xv = (float)div_rn(__dsub_rn(v, C[2 * 32 + j]), C[3 * 32 + j], C[9 * 32 + j]);
+            }
+            xa[kl * A + j] = xv;
+        }
+    };
+    __syncthreads();
+
+    const int voff = lane * 16;
+    const __amdgpu_buffer_rsrc_t rs0 = layer_rsrc(a.w[0], a.wbytes[0]);
+    const __amdgpu_buffer_rsrc_t rs1 = layer_rsrc(a.w[1], a.wbytes[1]);
+    const __amdgpu_buffer_rsrc_t rso = layer_rsrc(a.w[2], a.wbytes[2]);
+    const float f1 = a.winv[1] * kTanhK, fo = a.winv[2];
+
+    // M: the hidden accumulators, tile j x column c at R[4j + c]; EC: the wave's own column of the hidden-layer
+    // input, k-step p's packed hi at R[2p] and lo at R[2p + 1]
+    f4 R[TW * NC];
+    // (X3_STAMP variant builds: s_memtime per phase; slots 0 EC/tanh + output + fill, 1 EC/group wait, 2 EC/owner,
+    //  3 EC/layer 0 + tanh, 4 M/slab write + group wait, 5 M/MFMAs, 7 barrier)
+    uint64_t ph_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t tp_ = X3_STAMP ? __builtin_amdgcn_s_memtime() : 0;
+    // (an opaque zero, refreshed every step, added to every weight offset and LDS table base: the weights and
+    //  tables are the same every step, and without it the compiler hoists the loop-invariant loads out of the loop)
+    int wz = 0;
+    const double* Cz = C;
+    const float* Blz = Bl;
+    const float* Boutz = Bout;
+    auto refresh = [&]() __attribute__((always_inline)) {
+        wz = 0;
+        asm volatile("" : "+s"(wz));
+        Cz = C + wz;
+        Blz = Bl + wz;
+        Boutz = Bout + wz;
+    };
+
+    // layer 0's fragments: tile pairs through three register sets, two pairs ahead of the MFMAs
+    h8 a0h[3][2], a0l[3][2];
+    auto load0 = [&](int p, auto SETc) __attribute__((always_inline)) {
+        constexpr int st = decltype(SETc)::value;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            a0h[st][v] = fload(rs0, voff, wz + (2 * p + v) * 2048);
+            a0l[st][v] = fload(rs0, voff, wz + (2 * p + v) * 2048 + 1024);
+        }
+    };
+    // EC's hand-off inside the group: a workgroup-scope release of this wave's LDS writes (partials, action
+    // inputs), the count, layer 0's first fragments (in flight through the wait and the owner phase), the wait
+    // for the group's four waves, an acquire.  LDS only ("local"), so the weight loads stay in flight
+    auto ec_sync = [&](int h) __attribute__((always_inline)) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        if (lane == 0) __hip_atomic_fetch_add(cnt + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        load0(0, std::integral_constant<int, 0>{});
+        load0(1, std::integral_constant<int, 1>{});
+        PP3_PIN_LOADS();
+        X3_ST(0);
+        while (__hip_atomic_load(cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 4 * (h + 1))
+            __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        X3_ST(1);
+    };
+    // EC, step h's head: normalise the state (dynamics.py:109), f32 (TF feed), the staged actions; the column's
+    // power-of-two scale (max |x| -> [2^11, 2^12)); the split (this lane's B fragment of layer 0); layer 0
+    // [S+A -> h] for the own column, its tanh and split: every tile pair is one k-step of the hidden-layer input
+    auto ec_head = [&]() __attribute__((always_inline)) {
+        const float* xr = xa + (16 * wl + m) * A;
+        float xin[8];
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int d = 16 * v + 4 * q + r;
+                float xv = 0.f;
+                if (d < S) xv = (float)div_rn(__dsub_rn(s[v][r], Cz[0 * 32 + d]), Cz[1 * 32 + d], Cz[8 * 32 + d]);
+                else if (d < S + A) xv = xr[d - S];
+                xin[4 * v + r] = xv;
+            }
+        float mx = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(xin[i]));
+        mx = max_rows32(max_rows16(mx));
+        int e = 0;
+        (void)frexpf(mx, &e);                          // mx in [2^(e-1), 2^e)
+        int sh = 12 - e;
+        sh = mx > 0.f ? (sh < -100 ? -100 : (sh > 100 ? 100 : sh)) : 0;
+        const float sc = ldexpf(1.0f, sh);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) xin[i] *= sc;
+        h8 bh, bl;
+        split8(xin, bh, bl);
+        const float cf = ldexpf(a.winv[0], -sh) * kTanhK;   // this lane's column factor
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if (p + 2 < P) {
+                if (p % 3 == 0) load0(p + 2, std::integral_constant<int, 2>{});
+                else if (p % 3 == 1) load0(p + 2, std::integral_constant<int, 0>{});
+                else load0(p + 2, std::integral_constant<int, 1>{});
+            }
+            PP3_PIN_LOADS();
+            f4 z0 = (f4){0.f, 0.f, 0.f, 0.f}, z1 = (f4){0.f, 0.f, 0.f, 0.f};
+            z0 = mfma16(a0h[p % 3][0], bh, z0);
+            z1 = mfma16(a0h[p % 3][1], bh, z1);
+            z0 = mfma16(a0h[p % 3][0], bl, z0);
+            z1 = mfma16(a0h[p % 3][1], bl, z1);
+            z0 = mfma16(a0l[p % 3][0], bh, z0);
+            z1 = mfma16(a0l[p % 3][1], bh, z1);
+            h8 xh, xl;
+            epi_pair(z0, z1, cf, Blz, 2 * p, q, xh, xl);
+            R[2 * p] = __builtin_bit_cast(f4, xh);
+            R[2 * p + 1] = __builtin_bit_cast(f4, xl);
+        }
+        X3_ST(3);
+    };
+
+    // Group 1 runs one segment ahead: group 0 sits out the first interval, group 1 the last.  Every wave
+    // executes every increment, spin and barrier, whatever its candidates.
+    if (grp == 0) __syncthreads();
+    // ---------------- EC(0): step 0's head ----------------
+    refresh();
+    __builtin_amdgcn_s_setprio(PP3_PRIO_EC);
+    fill_actions(0);
+    ec_sync(0);
+    ec_head();
+    __syncthreads();
+    for (int h = 0;; ++h) {
+        refresh();
+        // ---------------- M(h): the hidden layer ----------------
+        __builtin_amdgcn_s_setprio(PP3_PRIO_M);
+        X3_ST(7);
+        {
+            // weights in units of one tile (hi | lo) through four register sets, three units ahead of the
+            // MFMAs; tile jj of this wave is tile jj & 3 of block 2wl + (jj >> 2) (rollout_x3's packing)
+            auto woff = [&](int p, int jj) __attribute__((always_inline)) {
+                return wz + (((2 * wl + (jj >> 2)) * P + p) * 4 + (jj & 3)) * 2048;
+            };
+            h8 th[4], tl[4];
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                th[u] = fload(rs1, voff, woff(0, u));
+                tl[u] = fload(rs1, voff, woff(0, u) + 1024);
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                swrite(slab + sidx<NC>(p, wl, 0, lane), __builtin_bit_cast(h8, R[2 * p]));
+                swrite(slab + sidx<NC>(p, wl, 1, lane), __builtin_bit_cast(h8, R[2 * p + 1]));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            if (lane == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+            for (int i = 0; i < TW * NC; ++i) R[i] = (f4){0.f, 0.f, 0.f, 0.f};
+            // the group's four columns of the layer input published
+            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 4 * (h + 1))
+                __builtin_amdgcn_s_sleep(1);
+            // (acquire: the slab reads below cannot move above the wait)
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            X3_ST(4);
+#pragma unroll 1
+            for (int p = 0; p < P; ++p) {
+                h8 bh[NC], bl[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) bh[c] = sread(slab + sidx<NC>(p, c, 0, lane));
+#pragma unroll
+                for (int c = 0; c < NC; ++c) bl[c] = sread(slab + sidx<NC>(p, c, 1, lane));
+                const int pn = (p + 1) & (P - 1);              // (the last k-step's look-ahead wraps: unconditional loads)
+#pragma unroll
+                for (int u = 0; u < TW; ++u) {
+                    const int o = woff(u + 3 < TW ? p : pn, (u + 3) % TW);
+                    th[(u + 3) % 4] = fload(rs1, voff, o);
+                    tl[(u + 3) % 4] = fload(rs1, voff, o + 1024);
+                    __builtin_amdgcn_sched_barrier(0);         // keep the loads ahead of the MFMAs they overlap
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) R[u * NC + c] = mfma16(th[u % 4], bh[c], R[u * NC + c]);
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) R[u * NC + c] = mfma16(th[u % 4], bl[c], R[u * NC + c]);
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) R[u * NC + c] = mfma16(tl[u % 4], bh[c], R[u * NC + c]);
+                }
+            }
+            X3_ST(5);
+        }
+        __syncthreads();
+        X3_ST(7);
+        {
+            int lz = lane;
+            asm volatile("" : "+v"(lz));
+            ln = lz;
+            q = lz >> 4;
+            m = lz & 15;
+        }
+        // ---------------- EC(h + 1): step h's tail, step h + 1's head ----------------
+        __builtin_amdgcn_s_setprio(PP3_PRIO_EC);
+        const bool more = h + 1 < a.H;
+        if (more) fill_actions(h + 1);
+        {
+            f4 po[2][NC];
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) po[v][c] = (f4){0.f, 0.f, 0.f, 0.f};
+            h8 oh[2][2], ol[2][2];                             // the output layer's k-step wl * PW + pp, one ahead
+            auto load_o = [&](int pp, auto SETc) __attribute__((always_inline)) {
+                constexpr int st = decltype(SETc)::value;
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const int o = wz + (((wl * PW + pp) * 2 + v) * 2) * 1024;
+                    oh[st][v] = fload(rso, voff, o);
+                    ol[st][v] = fload(rso, voff, o + 1024);
+                }
+            };
+            load_o(0, std::integral_constant<int, 0>{});
+            PP3_PIN_LOADS();
+#pragma unroll
+            for (int pp = 0; pp < PW; ++pp) {
+                if (pp + 1 < PW) {
+                    if (pp % 2 == 0) load_o(pp + 1, std::integral_constant<int, 1>{});
+                    else load_o(pp + 1, std::integral_constant<int, 0>{});
+                }
+                PP3_PIN_LOADS();
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    h8 xh, xl;
+                    epi_pair(R[(2 * pp) * NC + c], R[(2 * pp + 1) * NC + c], f1, Blz + HP, wl * TW + 2 * pp, q, xh, xl);
+#pragma unroll
+                    for (int v = 0; v < 2; ++v) {
+                        po[v][c] = mfma16(oh[pp % 2][v], xh, po[v][c]);
+                        po[v][c] = mfma16(oh[pp % 2][v], xl, po[v][c]);
+                        po[v][c] = mfma16(ol[pp % 2][v], xh, po[v][c]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                part0[(wl * NC + c) * 64 + ln] = po[0][c];
+                if (q < nq1) part1[(wl * NC + c) * 16 * nq1 + ln] = po[1][c];
+            }
+        }
+        ec_sync(h + 1);
+        {
+            f4 o[2];
+            o[0] = part0[(0 * NC + wl) * 64 + ln];
+            o[1] = q < nq1 ? part1[(0 * NC + wl) * 16 * nq1 + ln] : (f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g2 = 1; g2 < 4; ++g2) {                   // fixed summation order
+                o[0] += part0[(g2 * NC + wl) * 64 + ln];
+                if (q < nq1) o[1] += part1[(g2 * NC + wl) * 16 * nq1 + ln];
+            }
+            // cheetah penalties on the current state (cost_functions.py:16-26): dims 5..7 in row q = 1
+            const int npen = partner_row16((s[0][1] >= 0.2) + (s[0][2] >= 0.0) + (s[0][3] >= 0.0));
+            const double s17 = s[1][1];
+            // de-normalise + residual (dynamics.py:113,116), f64, no FMA
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+                const f4 bv = *reinterpret_cast<const f4*>(Boutz + 16 * v + 4 * q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int d = 16 * v + 4 * q + r;
+                    if (d < S) {
+                        const float dn = fmaf(o[v][r], fo, bv[r]);                 // BiasAdd (f32)
+                        const double ud = __dadd_rn(__dmul_rn((double)dn, Cz[5 * 32 + d]), Cz[4 * 32 + d]);
+                        s[v][r] = __dadd_rn(s[v][r], ud);
+                    }
+                }
+            }
+            if (a.cost == BCMPC_COST_CHEETAH) {
+                const double score = __dsub_rn(10.0 * (double)npen, div_rn(__dsub_rn(s[1][1], s17), 0.01, 1.0 / 0.01));
+                cost = __dadd_rn(cost, score);
+            }
+            const int64_t cd = gc0 + 16 * wl + m;
+            if (a.traj && cd < a.K) {
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int d = 16 * v + 4 * q + r;
+                        if (d < S) a.traj[((int64_t)(h + 1) * a.K + cd) * S + d] = s[v][r];
+                    }
+            }
+        }
+        X3_ST(2);
+        if (!more) break;
+        ec_head();
+        __syncthreads();
+    }
+    __syncthreads();                                    // the last EC's interval
+    if (grp == 1) __syncthreads();
+    if constexpr (X3_STAMP) {
+        if (a.stamps && lane == 0)
+            for (int k2 = 0; k2 < 10; ++k2) a.stamps[((size_t)blockIdx.x * 8 + w) * 10 + k2] = ph_[k2];
+    }
+    // the cost holder: row 0 (dims 1, 17 and the penalty count)
+    const int64_t cd = gc0 + 16 * wl + (lane & 15);
+    if (a.costs && cd < a.K && (lane >> 4) == 0) a.costs[cd] = cost;
+}
+
 // ------------------------------------------------------------ launchers ----
-#ifndef X3_PROBE           // (tools/x3_probe.sh: one instantiation, resource report only)
+#ifndef X3_PROBE         // (tools/x3_probe.sh: one instantiation, resource report only)
 // X3_PART splits the instantiations over two translation units so each can be built with its own
 // scheduler (Makefile): 1 = the plain tanh delta net without a policy (cfg2..cfg5; built with
 // -amdgpu-sched-strategy=iterative-ilp, measured -2% kernel time at cfg3), 2 = everything else plus
@@ -2078,8 +2503,40 @@ hipError_t launch_rollout_x3_f16(const RolloutArgs& a, int hidden_padded, int nc
         default: return hipErrorInvalidValue;
     }
 }
+// rollout_pp3's shapes: the plain 2-layer net at hidden 512 whose slab, partials and action inputs fit
+// the CU's 160 KiB (at S + A <= 32: S <= 20 with A <= 10)
+bool x3_pp3_ok(int hidden_padded, int n_layers, int state_dim, int action_dim) {
+    return hidden_padded == 512 && n_layers == 2 && state_dim >= 1 && action_dim >= 1 &&
+           state_dim + action_dim <= 32 && x3_pp3_lds(hidden_padded, state_dim, action_dim) <= 160 * 1024;
+}
+size_t x3_pp3_lds(int hidden_padded, int state_dim, int action_dim) {
+    return (size_t)pp3_lds_total(hidden_padded, state_dim, action_dim);
+}
+// (the launch arguments rollout_pp3 implements: capi.cpp sends every other launch to rollout_x3)
+bool x3_pp3_args_ok(const RolloutArgs& a, int hidden_padded) {
+    return x3_pp3_ok(hidden_padded, a.L, a.S, a.A) && a.model == BCMPC_MODEL_DELTA && a.pL == 0 &&
+           a.act == BCMPC_ACT_TANH && !a.ln && !a.f16_single && !a.fused_argmin &&
+           (a.cost == BCMPC_COST_CHEETAH || a.cost == BCMPC_COST_NONE) && a.K >= 1 && a.H >= 1;
+}
+hipError_t launch_rollout_pp3(const RolloutArgs& a, int hidden_padded, hipStream_t st) {
+    if (!x3_pp3_args_ok(a, hidden_padded)) return hipErrorInvalidValue;
+    static bool attr_set = false;
+    if (!attr_set) {
+        const hipError_t e = hipFuncSetAttribute((const void*)rollout_pp3<512>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    const int64_t blocks = (a.K + 127) / 128;
+    hipLaunchKernelGGL((rollout_pp3<512>), dim3((unsigned)blocks), dim3(512), x3_pp3_lds(512, a.S, a.A), st, a);
+    return hipGetLastError();
+}
 #endif
 #ifdef X3_ONLY   // (variant builds carry no single-pass layouts: capi.cpp still links their shape queries)
+bool x3_pp3_ok(int, int, int, int) { return false; }
+size_t x3_pp3_lds(int, int, int) { return 0; }
+bool x3_pp3_args_ok(const RolloutArgs&, int) { return false; }
+hipError_t launch_rollout_pp3(const RolloutArgs&, int, hipStream_t) { return hipErrorInvalidValue; }
 bool x3_f16_layout_ok(int, int, int) { return false; }
 size_t x3_f16_lds(int, int, int, int, int) { return 0; }
 bool x3_pp_ok(int, int, int, int) { return false; }

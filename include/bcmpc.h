@@ -705,6 +705,11 @@ int bcmpc_engine_info(const bcmpc_engine* eng, int32_t* hidden_padded, int64_t* 
  * "rollout_x3<512,NC=4,NW=8> split"), NUL-terminated and truncated to cap bytes: tests and the bench
  * assert / report which layout the engine selected ("+terms" appended on BCMPC_COST_TERMS engines).  Round 5 (ABI 4). */
 int bcmpc_engine_layout(const bcmpc_engine* eng, char* buf, int32_t cap);
+/* LDS bytes per workgroup of the two-group pipelined split kernel (rollout_pp3: BCMPC_PREC_SPLIT_F16 under
+ * kernel auto at large K, or forced with BCMPC_SPLIT_PP=1) for a net shape, or -1 where the layout does not
+ * cover the shape (it covers n_layers == 2, hidden padded to 512, state_dim + action_dim <= 32, within the
+ * CU's 160 KiB).  No device call. */
+int64_t bcmpc_split_pp_lds_bytes(int32_t hidden, int32_t n_layers, int32_t state_dim, int32_t action_dim);
 
 #ifdef __cplusplus
 }
