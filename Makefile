@@ -4,18 +4,16 @@ ARCH     ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function
 SRC      := bc_mpc_amd/csrc
 LIB      := bc_mpc_amd/libbcmpc.so
-OBJ      := build/rollout.o build/rollout_grp.o build/rollout_x3.o build/rollout_x3_plain.o build/rollout_team.o build/cem.o build/mppi.o build/batch.o build/plan_batch.o build/term_cost.o build/ensemble.o build/fit.o build/capi.o build/mt19937.o build/mt_jump.o build/mt_device.o build/comm.o
-HDR      := include/bcmpc.h $(SRC)/kernels.h $(SRC)/device_common.h $(SRC)/argmin_common.h
+# objects by how they compile: host units that see the kernels' launch headers (hipcc -x hip), plain C++ (g++),
+# every other one a kernel unit (.hip); OBJ in link order
+HOSTOBJ  := capi mt_draw planners
+CXXOBJ   := mt19937 mt_jump
+OBJ      := $(patsubst %,build/%.o,rollout rollout_grp rollout_x3 rollout_x3_plain rollout_team cem mppi batch \
+              plan_batch term_cost ensemble fit $(HOSTOBJ) $(CXXOBJ) mt_device comm)
+# header dependencies come from the compiler (build/*.d): a header rebuilds exactly the objects that include it
+DEPFLAGS := -MMD -MP
 
 all: $(LIB)
-
-build/rollout.o: $(SRC)/rollout.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/rollout_grp.o: $(SRC)/rollout_grp.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the split kernel in two units (X3_PART in rollout_x3.hip), each with the scheduler that measured best
 # (profiles/r01_sched_ilp_ab.txt, profiles/r01_sched_part2_ab.txt): the plain tanh delta net with
@@ -23,80 +21,44 @@ build/rollout_grp.o: $(SRC)/rollout_grp.hip $(HDR)
 # (-0.6..1.7%; iterative-ILP spills the policy+reward kernel, +10%)
 X3ILP    ?= -mllvm -amdgpu-sched-strategy=iterative-ilp
 X3P2     ?= -mllvm -amdgpu-sched-strategy=max-ilp
-
-build/rollout_x3.o: $(SRC)/rollout_x3.hip $(HDR) $(SRC)/split_common.h
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) $(X3P2) -DX3_PART=2 -c $< -o $@
-
-build/rollout_x3_plain.o: $(SRC)/rollout_x3.hip $(HDR) $(SRC)/split_common.h
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) $(X3ILP) -DX3_PART=1 -c $< -o $@
+build/rollout_x3.o:       EXTRA = $(X3P2) -DX3_PART=2
+build/rollout_x3_plain.o: EXTRA = $(X3ILP) -DX3_PART=1
 
 # the team kernels with the iterative ILP scheduler: ppo_defaults -2.4 us, ppo_mpc_default -5.5 us, run.sh
 # recipe -4.8 us per call against the default (max-ilp +2.5..+21 us, iterative-minreg +0..+24 us;
 # profiles/r04_team_sched_ab.jsonl)
 TEAMSCHED ?= -mllvm -amdgpu-sched-strategy=iterative-ilp
-build/rollout_team.o: $(SRC)/rollout_team.hip $(HDR) $(SRC)/split_common.h
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) $(TEAMSCHED) -c $< -o $@
+build/rollout_team.o:     EXTRA = $(TEAMSCHED)
 
-build/fit.o: $(SRC)/fit.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+HIPCOMPILE = $(strip $(HIPCC) $(HIPFLAGS) $(EXTRA) $(DEPFLAGS) -c $< -o $@)
 
-build/mt_device.o: $(SRC)/mt_device.hip $(HDR)
+build/%.o: $(SRC)/%.hip
 	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCOMPILE)
 
-build/comm.o: $(SRC)/comm.hip $(HDR)
+build/rollout_x3_plain.o: $(SRC)/rollout_x3.hip
 	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCOMPILE)
 
-build/cem.o: $(SRC)/cem.hip $(HDR) $(SRC)/cem_common.h
+$(HOSTOBJ:%=build/%.o): build/%.o: $(SRC)/%.cpp
 	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -x hip $(DEPFLAGS) -c $< -o $@
 
-build/mppi.o: $(SRC)/mppi.hip $(HDR) $(SRC)/cem_common.h $(SRC)/mppi_common.h
+$(CXXOBJ:%=build/%.o): build/%.o: $(SRC)/%.cpp
 	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Wall $(DEPFLAGS) -c $< -o $@
 
-build/batch.o: $(SRC)/batch.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/term_cost.o: $(SRC)/term_cost.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/ensemble.o: $(SRC)/ensemble.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/plan_batch.o: $(SRC)/plan_batch.hip $(HDR) $(SRC)/cem_common.h $(SRC)/mppi_common.h
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/mt19937.o: $(SRC)/mt19937.cpp $(SRC)/mt19937.h
-	@mkdir -p build
-	g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -c $< -o $@
-
-build/mt_jump.o: $(SRC)/mt_jump.cpp $(SRC)/mt19937.h
-	@mkdir -p build
-	g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -c $< -o $@
-
-build/capi.o: $(SRC)/capi.cpp $(HDR) $(SRC)/mt19937.h
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+-include $(OBJ:.o=.d)
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJ) -ldl
 
 # resource usage report (VGPR/SGPR/LDS/occupancy) for the rollout kernels
-resources: $(SRC)/rollout.hip $(SRC)/rollout_grp.hip $(HDR)
+resources: $(SRC)/rollout.hip $(SRC)/rollout_grp.hip
 	$(HIPCC) $(HIPFLAGS) -c $(SRC)/rollout.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs|Spill|Occupancy|LDS"
 	$(HIPCC) $(HIPFLAGS) -c $(SRC)/rollout_grp.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs|Spill|Occupancy|LDS" 
 
-asm: $(SRC)/rollout.hip $(SRC)/rollout_grp.hip $(HDR)
+asm: $(SRC)/rollout.hip $(SRC)/rollout_grp.hip
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only $(SRC)/rollout.hip -o build/rollout.s
 	$(HIPCC) $(HIPFLAGS) -S --cuda-device-only $(SRC)/rollout_grp.hip -o build/rollout_grp.s

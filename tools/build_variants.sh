@@ -4,7 +4,8 @@
 #   default: flags apply to rollout.hip + rollout_grp.hip (f32 kernels)
 #   -x     : flags apply to rollout_x3.hip only, built for one width / NC ($X3W, default 512; $X3NC, default 4)
 #   -p     : flags apply to both units of rollout_x3.hip (X3_PART=1 / 2, every width and NC, the
-#            production schedulers), linked with the in-tree build's other objects
+#            production schedulers)
+# Every variant links the in-tree build's other objects and the host units rebuilt as a diagnostic build.
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build/variants
@@ -13,7 +14,15 @@ X3=0
 if [ "${1:-}" = "-x" ]; then X3=1; shift; fi
 if [ "${1:-}" = "-p" ]; then X3=2; shift; fi
 make -s -j8 ARCH=gfx950 >/dev/null
-$H -x hip -c bc_mpc_amd/csrc/capi.cpp -o build/variants/capi.o
+HOST="capi mt_draw planners"
+HOSTOBJ=""
+for u in $HOST; do
+  $H -x hip -c bc_mpc_amd/csrc/$u.cpp -o build/variants/$u.o
+  HOSTOBJ="$HOSTOBJ build/variants/$u.o"
+done
+# the in-tree build's objects except the host units and the named ones (the variant's own replace them)
+others() { ls build/*.o | grep -v -E "/(${HOST// /|}|$1)\.o$"; }
+link() { name=$1; shift; /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/variants/libbcmpc_$name.so "$@" $HOSTOBJ -ldl; }
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   src=bc_mpc_amd/csrc/rollout_x3.hip
@@ -25,18 +34,14 @@ for spec in "$@"; do
   if [ $X3 = 2 ]; then
     ( $H -mllvm -amdgpu-sched-strategy=iterative-ilp -DX3_PART=1 $flags -c $src -o build/variants/rollout_x3_plain_$name.o &&
       $H -mllvm -amdgpu-sched-strategy=max-ilp -DX3_PART=2 $flags -c $src -o build/variants/rollout_x3_$name.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/variants/libbcmpc_$name.so \
-          $(ls build/*.o | grep -v -E "/(rollout_x3|rollout_x3_plain|capi)\.o$") build/variants/rollout_x3_$name.o build/variants/rollout_x3_plain_$name.o build/variants/capi.o -ldl ) &
+      link $name $(others "rollout_x3|rollout_x3_plain") build/variants/rollout_x3_$name.o build/variants/rollout_x3_plain_$name.o ) &
   elif [ $X3 = 1 ]; then
     ( $H -DX3_ONLY=${X3W:-512} -DX3_ONLY_NC=${X3NC:-4} $flags -c $src -o build/variants/rollout_x3_$name.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/variants/libbcmpc_$name.so \
-          build/rollout.o build/rollout_grp.o build/cem.o build/fit.o build/mt19937.o build/mt_jump.o build/mt_device.o build/comm.o build/rollout_team.o build/variants/rollout_x3_$name.o build/variants/capi.o -ldl ) &
+      link $name $(others "rollout_x3|rollout_x3_plain") build/variants/rollout_x3_$name.o ) &
   else
     ( $H $flags -c bc_mpc_amd/csrc/rollout.hip -o build/variants/rollout_$name.o &&
       $H $flags -c bc_mpc_amd/csrc/rollout_grp.hip -o build/variants/rollout_grp_$name.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/variants/libbcmpc_$name.so \
-          build/variants/rollout_$name.o build/variants/rollout_grp_$name.o build/cem.o build/fit.o build/mt19937.o build/mt_jump.o build/mt_device.o build/comm.o build/rollout_x3.o build/rollout_x3_plain.o build/rollout_team.o \
-          build/variants/capi.o -ldl ) &
+      link $name $(others "rollout|rollout_grp") build/variants/rollout_$name.o build/variants/rollout_grp_$name.o ) &
   fi
 done
 wait
