@@ -31,22 +31,21 @@ from __future__ import annotations
 import ctypes
 from typing import Optional
 
-import math
-
 import numpy as np
 
 from . import _lib
 from . import distributed as _dist
-from . import weights as _weights
-from .controllers import Controller, _BatchPlans, _check_model, _default_device, _device_terms, _opt
-from .cost_functions import is_cheetah_cost
-from .engine import RolloutEngine
+from .controllers import Planner
 
 _ELITE_BYTES = ctypes.sizeof(_lib.Elite)
 
 
-class CEMcontroller(_BatchPlans, Controller):
-    """Cross-entropy-method MPC on the MI355X engine (BASELINE cfg5 CEM outer loop)."""
+class CEMcontroller(Planner):
+    """Cross-entropy-method MPC on the MI355X engine (BASELINE cfg5 CEM outer loop).  ``get_action`` /
+    ``get_actions`` return the first action of the best sample of all iterations; ``last_mu`` / ``last_sigma``
+    hold the refitted distribution, ``last_cost`` / ``last_position`` the best sample (batched: ``[B, H, A]``
+    and ``[B]``)."""
+    _KIND = "CEM"
 
     def __init__(self,
                  env,
@@ -65,30 +64,12 @@ class CEMcontroller(_BatchPlans, Controller):
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
                  process_group=None):
-        self.env = env
-        self.dyn_model = dyn_model
-        self.horizon = horizon
-        self.cost_fn = cost_fn
-        self.num_simulated_paths = num_simulated_paths
-        self.gamma = gamma
-        if iterations < 1:
-            raise ValueError("iterations must be >= 1")
-        self.iterations = int(iterations)
+        super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
+                         warm_start, 0xCE5EED if seed is None else seed, device, process_group)
         self.elite_frac = float(elite_frac)
         self._n_elite = n_elite
         self.alpha = float(alpha)
-        self.init_std = init_std
-        self.warm_start = warm_start
-        self._seed_rng = np.random.RandomState(0xCE5EED if seed is None else seed)
-        self._device = device
-        self._group = process_group
-        self._engine: Optional[RolloutEngine] = None
-        self._engine_key = None
-        self._gamma_set = None
-        self._mu = None
-        self.last_mu = self.last_sigma = None
-        self.last_cost = None
-        self.last_position = None
+        self.last_sigma = None
 
     @property
     def n_elite(self) -> int:
@@ -96,124 +77,28 @@ class CEMcontroller(_BatchPlans, Controller):
             return int(self._n_elite)
         return max(1, int(round(self.elite_frac * int(self.num_simulated_paths))))
 
-    def reset(self, env_ids=None) -> None:
-        """Forget the warm-start mean (call at episode boundaries).  ``env_ids``: forget only those
-        environments' plans of ``get_actions`` (an episode boundary in one simulator of a batch)."""
-        if env_ids is None:
-            self._mu = None
-        self._reset_plans(env_ids)
+    def _solve(self, eng, state, mu0, sd0, seed, K):
+        res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        return self._publish(res.best_cost, res.best_index, res.first_action, mu, sd)
 
-    def _bounds(self):
-        return (np.asarray(self.env.action_space.low, dtype=np.float64),
-                np.asarray(self.env.action_space.high, dtype=np.float64))
-
-    def initial_distribution(self):
-        """mu0: the previous solution shifted by one step (warm start) or the box centre;
-        sigma0: init_std, default (high - low) / 4."""
-        low, high = self._bounds()
-        H = int(self.horizon)
-        mid = (low + high) / 2.0
-        sd = np.full_like(low, self.init_std) if self.init_std is not None else (high - low) / 4.0
-        if self.warm_start and self._mu is not None and self._mu.shape == (H, low.shape[0]):
-            mu = np.vstack([self._mu[1:], mid[None]])
-        else:
-            mu = np.tile(mid, (H, 1))
-        return mu, np.tile(sd, (H, 1))
-
-    def _engine_for(self, spec, S, A, k_local, terms=None) -> RolloutEngine:
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev, terms is not None)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            reward = spec.model == "reward"
-            self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
-                                         int(self.horizon), int(k_local), device=dev,
-                                         cost="reward" if reward else "terms" if terms is not None else "cheetah",
-                                         model=spec.model)
-            self._engine.set_action_bounds(*self._bounds())
-            self._engine_key = key
-            self._gamma_set = None
-        if terms is not None:
-            self._engine.set_cost_terms(terms)
-        if spec.model == "reward" and self._gamma_set != float(self.gamma):
-            self._engine.set_discount(float(self.gamma))
-            self._gamma_set = float(self.gamma)
-        return self._engine
-
-    def get_action(self, state):
-        if getattr(self.dyn_model, "is_ensemble", False):   # an EnsembleDynamicsModel (ensemble.py)
-            from . import ensemble as _ensemble
-            return _ensemble.cem_get_action(self, state)
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
-        if K == 0:
-            raise ValueError("attempt to get argmin of an empty sequence")
-        state = np.asarray(state, dtype=np.float64).reshape(-1)
-        spec, norm, version = _weights.extract(self.dyn_model)
-        reward = spec.model == "reward"
-        terms = None
-        if not reward:
-            _check_model(spec, "delta", type(self).__name__)
-            terms = _device_terms(self.cost_fn, S, A)
-            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
-                raise ValueError("CEMcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
-        mu0, sd0 = self.initial_distribution()
-        seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
-        rank, ws = _dist.world(self._group)
+    def _sharded(self, rank, ws, state, spec, norm, version, terms, mu0, sd0, seed, S, A, K):
+        """Every rank rolls out its shard of the K candidates (cem_multi_rank)."""
         lo, hi = _dist.shard_range(K, rank, ws)
-        E = min(self.n_elite, K)
-        if ws > 1 and terms is not None:
+        if terms is not None:
             raise NotImplementedError("multi-rank CEM with a TermCost is not built yet (one rank only)")
-        if ws == 1:
-            eng = self._engine_for(spec, S, A, K, *_opt(terms))
-            eng.set_weights(spec, norm, version)
-            res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, E, self.alpha, seed)
-            cost, pos, first = res.best_cost, res.best_index, res.first_action
-        else:
-            if K < ws:
-                raise ValueError(f"multi-rank CEM needs num_simulated_paths >= world size ({K} < {ws})")
-            shard = _EngineShard(self, spec, norm, version, S, A, hi - lo)
-            cost, pos, first, mu, sd = cem_multi_rank(shard, state, mu0, sd0, self.iterations, E, self.alpha, seed,
-                                                      lo, hi, K, A, reward, self._group)
+        if K < ws:
+            raise ValueError(f"multi-rank CEM needs num_simulated_paths >= world size ({K} < {ws})")
+        shard = _EngineShard(self, spec, norm, version, S, A, hi - lo)
+        return self._publish(*cem_multi_rank(shard, state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha,
+                                             seed, lo, hi, K, A, spec.model == "reward", self._group))
+
+    def _publish(self, cost, pos, first, mu, sd):
         self._mu = mu
         self.last_mu, self.last_sigma = mu, sd
         self.last_cost, self.last_position = cost, pos
         return first
 
-    def get_actions(self, states):
-        """Batched control step: ``states`` is ``[B, S]``, one independent CEM answer per row with
-        ``num_simulated_paths`` candidates and ``n_elite`` elites each, all environments in one launch
-        chain (``RolloutEngine.cem_get_actions``).  Every environment keeps its own warm-start plan (see
-        ``reset``); one seed is drawn per call.  Returns ``[B, A]`` float64: each environment's best
-        sample's first action.  ``last_mu`` / ``last_sigma`` (``[B, H, A]``), ``last_cost`` /
-        ``last_position`` (``[B]``) describe the call.  One rank only."""
-        if getattr(self.dyn_model, "is_ensemble", False):
-            raise NotImplementedError("batched CEM over an EnsembleDynamicsModel is not built yet: use get_action")
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
-        states = self._plan_states(states, S)
-        if K == 0:
-            raise ValueError("attempt to get argmin of an empty sequence")
-        spec, norm, version = _weights.extract(self.dyn_model)
-        terms = None
-        if spec.model != "reward":
-            _check_model(spec, "delta", type(self).__name__)
-            terms = _device_terms(self.cost_fn, S, A)
-            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
-                raise ValueError("CEMcontroller needs the fused cheetah cost_fn or a learned-reward dyn_model")
-        B = states.shape[0]
-        mu0, sd0 = self.batch_initial_distribution(B)
-        seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
-        eng = self._batch_engine_for(spec, S, A, B * K, *_opt(terms))
-        eng.set_weights(spec, norm, version)
+    def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
         self._store_plans(mu)
         self.last_mu, self.last_sigma = mu, sd

@@ -129,7 +129,7 @@ def _minloc(ctrl, eng, valid, cost, index, first, A):
 
 
 def _device_terms(cost_fn, S: int, A: int):
-    """The ``TermCost`` a controller evaluates on the device (``RolloutEngine(cost="terms")``), or None: the
+    """The ``TermCost`` a controller evaluates on the device (an engine of ``cost="terms"``), or None: the
     cheetah cost is fused into the rollout kernels, and any other callable stays on the host."""
     if isinstance(cost_fn, TermCost) and not is_cheetah_cost(cost_fn, S, A):
         return cost_fn
@@ -159,22 +159,114 @@ def _batch_states(states, S: int, group) -> np.ndarray:
     return states
 
 
-class _BatchPlans:
-    """The batched planners' host state (CEMcontroller / MPPIcontroller ``get_actions``): one warm-start
-    plan per environment and the B*K-candidate engine, kept next to ``get_action``'s own plan and engine.
-    The host class provides ``env``, ``horizon``, ``gamma``, ``init_std``, ``warm_start``, ``_device``,
-    ``_group`` and ``_bounds()``."""
-    _bmu = None             # [B, H, A]: the last batched call's plans
-    _bkeep = None           # [B] bool: plan b is shifted and reused (False after reset([b]))
-    _batch_engine = None
-    _batch_key = None
-    _batch_gamma = None
+def _shape(ctrl):
+    """``(S, A, K)`` of a controller's problem; an empty horizon is refused as the reference's indexing
+    refuses it (controllers.py:85 at H = 0)."""
+    S = int(math.prod(ctrl.env.observation_space.shape))
+    A = len(ctrl.env.action_space.high)
+    K = int(ctrl.num_simulated_paths)
+    if ctrl.horizon < 1:
+        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    return S, A, K
+
+
+def _device(ctrl) -> int:
+    return _default_device() if ctrl._device is None else ctrl._device
+
+
+def _bounds(ctrl):
+    """The environment's action box as f64 vectors (what a new engine is given, and the planners' plans sit in)."""
+    return (np.asarray(ctrl.env.action_space.low, dtype=np.float64),
+            np.asarray(ctrl.env.action_space.high, dtype=np.float64))
+
+
+def _cached_engine(ctrl, store: str, slot: str, *args, make=None, **kwargs):
+    """The controllers' one engine cache: the engine in ``ctrl.<store>[slot]`` (kept there as ``(key, engine)``)
+    for the constructor arguments ``args`` / ``kwargs``.  The arguments ARE the key: an engine is closed and
+    built anew exactly when one of them differs from those it was built with, and a new engine gets the
+    environment's action bounds.  ``make``: the engine class when it is not RolloutEngine.  What may change
+    from call to call without a rebuild (weights, cost terms, discount, communicator, ensemble rule) is set by
+    the caller after the lookup; each of those setters returns at once on a value the engine already has."""
+    cache = ctrl.__dict__.setdefault(store, {})
+    key = (args, kwargs)
+    hit = cache.get(slot)
+    if hit is None or hit[0] != key:
+        if hit is not None:
+            cache.pop(slot)[1].close()      # (popped first: a constructor that raises leaves no closed engine behind)
+        eng = RolloutEngine(*args, **kwargs) if make is None else make(*args, **kwargs)
+        eng.set_action_bounds(*_bounds(ctrl))
+        cache[slot] = hit = (key, eng)
+    return hit[1]
+
+
+class Planner(Controller):
+    """What CEMcontroller (cem.py) and MPPIcontroller (mppi.py) share: a plan ``mu`` ``[H, A]`` refined over
+    ``iterations`` rounds of sampling around it, warm-started from the previous call's plan; ``get_actions``
+    keeps one plan per environment and the B*K-candidate engine next to ``get_action``'s own.  A subclass names
+    itself (``_KIND``), adds its constructor arguments and runs its engine call in ``_solve`` / ``_solve_batch``,
+    which publish the ``last_*`` attributes, store the plan and return the action(s)."""
+    _KIND = None            # "CEM" | "MPPI": the refusals' wording
+
+    def __init__(self, env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
+                 warm_start, seed, device, process_group):
+        self.env = env
+        self.dyn_model = dyn_model
+        self.horizon = horizon
+        self.cost_fn = cost_fn
+        self.num_simulated_paths = num_simulated_paths
+        self.gamma = gamma
+        if iterations < 1:
+            raise ValueError("iterations must be >= 1")
+        self.iterations = int(iterations)
+        self.init_std = init_std
+        self.warm_start = warm_start
+        self._seed_rng = np.random.RandomState(seed)
+        self._device = device
+        self._group = process_group
+        self._engine: Optional[RolloutEngine] = None
+        self._batch_engine: Optional[RolloutEngine] = None
+        self._mu = None         # [H, A]: get_action's last plan
+        self._bmu = None        # [B, H, A]: the last batched call's plans
+        self._bkeep = None      # [B] bool: plan b is shifted and reused (False after reset([b]))
+        self.last_mu = None
+        self.last_cost = None
+        self.last_position = None
+
+    def reset(self, env_ids=None) -> None:
+        """Forget the warm-start plan (call at episode boundaries).  ``env_ids``: forget only those
+        environments' plans of ``get_actions`` (an episode boundary in one simulator of a batch)."""
+        if env_ids is None:
+            self._mu = None
+        self._reset_plans(env_ids)
 
     def _reset_plans(self, env_ids) -> None:
         if env_ids is None:
             self._bmu = self._bkeep = None
         elif self._bmu is not None:
             self._bkeep[np.asarray(env_ids, dtype=np.int64).reshape(-1)] = False
+
+    def _bounds(self):
+        return _bounds(self)
+
+    def _refuse_ranks(self, ws: int) -> None:
+        """Called first thing on more than one rank: a planner that cannot shard its candidates raises here."""
+
+    def _sharded(self, rank, ws, state, spec, norm, version, terms, mu0, sd0, seed, S, A, K):
+        """get_action on ``ws`` > 1 ranks, after the checks and the draws of the one-rank call."""
+        raise NotImplementedError(f"{self._KIND}controller runs on one rank (world size {ws})")
+
+    def initial_distribution(self):
+        """mu0: the previous plan shifted by one step with the box centre appended (warm start), or the box
+        centre; sigma0: init_std, default (high - low) / 4."""
+        low, high = self._bounds()
+        H = int(self.horizon)
+        mid = (low + high) / 2.0
+        sd = np.full_like(low, self.init_std) if self.init_std is not None else (high - low) / 4.0
+        if self.warm_start and self._mu is not None and self._mu.shape == (H, low.shape[0]):
+            mu = np.vstack([self._mu[1:], mid[None]])
+        else:
+            mu = np.tile(mid, (H, 1))
+        return mu, np.tile(sd, (H, 1))
 
     def batch_initial_distribution(self, n_envs: int):
         """``initial_distribution()`` per environment, ``[B, H, A]`` each: plan b of the last batched call
@@ -203,27 +295,87 @@ class _BatchPlans:
             raise ValueError(f"states shape {states.shape} != (B, S) = (B >= 1, {S})")
         return states
 
-    def _batch_engine_for(self, spec, S: int, A: int, k_total: int, terms=None) -> RolloutEngine:
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_total), dev, terms is not None)
-        if self._batch_engine is None or self._batch_key != key:
-            if self._batch_engine is not None:
-                self._batch_engine.close()
-            reward = spec.model == "reward"
-            self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
-                                               int(self.horizon), int(k_total), device=dev,
-                                               cost="reward" if reward else "terms" if terms is not None
-                                               else "cheetah", model=spec.model)
-            self._batch_engine.set_action_bounds(*self._bounds())
-            self._batch_key = key
-            self._batch_gamma = None
+    def _next_seed(self) -> int:
+        return int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
+
+    def _model(self, S: int, A: int):
+        """(spec, normalisation, version, the TermCost scored on the device or None) of a supported pair of
+        model and cost: the learned reward of a reward model, else the fused cheetah cost or a TermCost."""
+        spec, norm, version = _weights.extract(self.dyn_model)
+        terms = None
+        if spec.model != "reward":
+            _check_model(spec, "delta", type(self).__name__)
+            terms = _device_terms(self.cost_fn, S, A)
+            if terms is None and not is_cheetah_cost(self.cost_fn, S, A):
+                raise ValueError(f"{self._KIND}controller needs the fused cheetah cost_fn or a learned-reward "
+                                 "dyn_model")
+        return spec, norm, version, terms
+
+    def _cached(self, slot: str, spec, S, A, k, terms) -> RolloutEngine:
+        reward = spec.model == "reward"
+        eng = _cached_engine(self, "_engines", slot, S, A, spec.hidden, spec.n_layers, spec.activation,
+                             spec.layer_norm, int(self.horizon), int(k), device=_device(self),
+                             cost="reward" if reward else "terms" if terms is not None else "cheetah",
+                             model=spec.model)
         if terms is not None:
-            self._batch_engine.set_cost_terms(terms)
-        if spec.model == "reward" and self._batch_gamma != float(self.gamma):
-            self._batch_engine.set_discount(float(self.gamma))
-            self._batch_gamma = float(self.gamma)
+            eng.set_cost_terms(terms)
+        if reward:
+            eng.set_discount(float(self.gamma))
+        return eng
+
+    def _engine_for(self, spec, S, A, k_local, terms=None) -> RolloutEngine:
+        self._engine = self._cached("single", spec, S, A, k_local, terms)
+        return self._engine
+
+    def _batch_engine_for(self, spec, S: int, A: int, k_total: int, terms=None) -> RolloutEngine:
+        self._batch_engine = self._cached("batch", spec, S, A, k_total, terms)
         return self._batch_engine
+
+    def get_action(self, state):
+        S, A, K = _shape(self)
+        if K == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        if getattr(self.dyn_model, "is_ensemble", False):
+            # an EnsembleDynamicsModel (ensemble.py): its engine has RolloutEngine's planner calls, scored on the
+            # members' combined value; it refuses ranks, costs and members itself, before anything is drawn
+            from . import ensemble as _ensemble
+            state = np.asarray(state, dtype=np.float64).reshape(-1)
+            eng = _ensemble._ctrl_engine(self, S, A, K, "single")
+            mu0, sd0 = self.initial_distribution()
+            return self._solve(eng, state, mu0, sd0, self._next_seed(), K)
+        rank, ws = _dist.world(self._group)
+        if ws > 1:
+            self._refuse_ranks(ws)
+        state = np.asarray(state, dtype=np.float64).reshape(-1)
+        spec, norm, version, terms = self._model(S, A)
+        mu0, sd0 = self.initial_distribution()
+        seed = self._next_seed()
+        if ws > 1:
+            return self._sharded(rank, ws, state, spec, norm, version, terms, mu0, sd0, seed, S, A, K)
+        eng = self._engine_for(spec, S, A, K, *_opt(terms))
+        eng.set_weights(spec, norm, version)
+        return self._solve(eng, state, mu0, sd0, seed, K)
+
+    def get_actions(self, states):
+        """Batched control step: ``states`` is ``[B, S]``, one independent answer per row with
+        ``num_simulated_paths`` candidates each, all environments in one launch chain.  Every environment
+        keeps its own warm-start plan (see ``reset``); one seed is drawn per call.  Returns ``[B, A]``
+        float64; ``last_mu`` is ``[B, H, A]`` and the other ``last_*`` hold one entry per environment.  One
+        rank only."""
+        if getattr(self.dyn_model, "is_ensemble", False):
+            raise NotImplementedError(f"batched {self._KIND} over an EnsembleDynamicsModel is not built yet: "
+                                      "use get_action")
+        S, A, K = _shape(self)
+        states = self._plan_states(states, S)
+        if K == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        spec, norm, version, terms = self._model(S, A)
+        B = states.shape[0]
+        mu0, sd0 = self.batch_initial_distribution(B)
+        seed = self._next_seed()
+        eng = self._batch_engine_for(spec, S, A, B * K, *_opt(terms))
+        eng.set_weights(spec, norm, version)
+        return self._solve_batch(eng, states, mu0, sd0, seed, K)
 
 
 class MPCcontroller(Controller):
@@ -254,9 +406,7 @@ class MPCcontroller(Controller):
         self._device = device
         self._group = process_group
         self._engine: Optional[RolloutEngine] = None
-        self._engine_key = None
         self._fast = None                       # get_action's repeat-call fast path (see there)
-        self._traj_buf = None
         # diagnostics of the last call (not part of the reference API)
         self.last_cost = None
         self.last_index = None
@@ -272,27 +422,16 @@ class MPCcontroller(Controller):
         return np_action_paths
 
     # ------------------------------------------------------------------ engine
-    def _dims(self):
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        return S, A
+    def _cached(self, slot: str, spec, S, A, k, cost: str, terms) -> RolloutEngine:
+        eng = _cached_engine(self, "_engines", slot, S, A, spec.hidden, spec.n_layers, spec.activation,
+                             spec.layer_norm, int(self.horizon), int(k), device=_device(self), cost=cost)
+        if terms is not None:
+            eng.set_cost_terms(terms)
+        return eng
 
     def _engine_for(self, spec, S, A, k_local, fused, terms=None) -> RolloutEngine:
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev, fused, terms is not None)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
-                                         int(self.horizon), int(k_local), device=dev,
-                                         cost="cheetah" if fused else "terms" if terms is not None else "none")
-            self._engine.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                           np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._engine_key = key
-            self._traj_buf = None
-        if terms is not None:
-            self._engine.set_cost_terms(terms)
+        self._engine = self._cached("single", spec, S, A, k_local,
+                                    "cheetah" if fused else "terms" if terms is not None else "none", terms)
         return _attach_comm(self, self._engine, fused)
 
     def _next_seed(self) -> int:
@@ -319,10 +458,7 @@ class MPCcontroller(Controller):
                     self.last_cost, self.last_index = res.best_cost, res.best_index
                     return res.first_action
             self._fast = None
-        S, A = self._dims()
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")   # controllers.py:85 at H=0
+        S, A, K = _shape(self)
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         rank, ws = _dist.world(self._group)
         lo, hi = _dist.shard_range(K, rank, ws)
@@ -398,10 +534,7 @@ class MPCcontroller(Controller):
             from . import ensemble as _ensemble
             return _ensemble.mpc_get_actions(self, states)
         _batch_rng_check(self.rng)
-        S, A = self._dims()
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        S, A, K = _shape(self)
         states = _batch_states(states, S, self._group)
         spec, norm, version = _weights.extract(self.dyn_model)
         if spec.model != "delta":
@@ -412,21 +545,8 @@ class MPCcontroller(Controller):
         seed = self._next_seed()
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               states.shape[0] * K, dev, terms is not None)
-        eng = getattr(self, "_batch_engine", None)
-        if eng is None or self._batch_key != key:
-            if eng is not None:
-                eng.close()
-            eng = self._batch_engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation,
-                                                     spec.layer_norm, int(self.horizon), states.shape[0] * K,
-                                                     device=dev, cost="cheetah" if terms is None else "terms")
-            eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                  np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._batch_key = key
-        if terms is not None:
-            eng.set_cost_terms(terms)
+        self._batch_engine = eng = self._cached("batch", spec, S, A, states.shape[0] * K,
+                                                "cheetah" if terms is None else "terms", terms)
         eng.set_weights(spec, norm, version)
         res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
         self.last_costs, self.last_cost, self.last_index = res.costs, res.best_cost, res.best_index
@@ -519,7 +639,6 @@ class MPCcontrollerPolicyNet(Controller):
         self._device = device
         self._group = process_group
         self._engine = None
-        self._engine_key = None
         self._fast = None                       # get_action's repeat-call fast path
         self.last_cost = None
         self.last_index = None
@@ -535,22 +654,11 @@ class MPCcontrollerPolicyNet(Controller):
         return np_action_paths
 
     def _engine_for(self, spec, pspec, S, A, k_local) -> RolloutEngine:
-        dev = _default_device() if self._device is None else self._device
-        mode = "stochastic" if self.self_exp else "explore"
-        key = (S, A, spec.model, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(self.horizon),
-               int(k_local), dev, pspec.hidden, pspec.n_layers, mode)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            reward = spec.model == "reward"
-            self._engine = RolloutEngine(S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
-                                         int(self.horizon), int(k_local), device=dev,
-                                         cost="reward" if reward else "cheetah", model=spec.model,
-                                         policy_hidden=pspec.hidden, policy_layers=pspec.n_layers,
-                                         policy_mode=mode)
-            self._engine.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                           np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._engine_key = key
+        self._engine = _cached_engine(
+            self, "_engines", "single", S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
+            int(self.horizon), int(k_local), device=_device(self),
+            cost="reward" if spec.model == "reward" else "cheetah", model=spec.model, policy_hidden=pspec.hidden,
+            policy_layers=pspec.n_layers, policy_mode="stochastic" if self.self_exp else "explore")
         return _attach_comm(self, self._engine)
 
     _MODEL = "delta"     # NNDynamicsModel + cheetah cost, argmin
@@ -579,11 +687,7 @@ class MPCcontrollerPolicyNet(Controller):
                     return res.first_action
                 self._seed_rng.unread(seed)                      # (nothing drawn: the slow path draws it)
             self._fast = None
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        S, A, K = _shape(self)
         reward = self._MODEL == "reward"
         if not reward and not is_cheetah_cost(self.cost_fn, S, A):
             raise ValueError("MPCcontrollerPolicyNet on the engine needs the fused cheetah cost_fn")
@@ -683,8 +787,6 @@ class MPCcontrollerReward(Controller):
         self._device = device
         self._group = process_group
         self._engine: Optional[RolloutEngine] = None
-        self._engine_key = None
-        self._gamma_set = None
         self.last_reward = None
         self.last_index = None
         self.last_rewards = None
@@ -700,30 +802,19 @@ class MPCcontrollerReward(Controller):
         np_action_paths = np.reshape(np_action_paths, [self.horizon, self.num_simulated_paths, -1])
         return np_action_paths
 
+    def _cached(self, slot: str, spec, S, A, k) -> RolloutEngine:
+        eng = _cached_engine(self, "_engines", slot, S, A, spec.hidden, 2, "tanh", spec.layer_norm,
+                             int(self.horizon), int(k), device=_device(self), cost="reward", model="reward")
+        eng.set_discount(float(self.gamma))
+        return eng
+
     def _engine_for(self, spec, S, A, k_local) -> RolloutEngine:
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.hidden, spec.layer_norm, int(self.horizon), int(k_local), dev)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = RolloutEngine(S, A, spec.hidden, 2, "tanh", spec.layer_norm, int(self.horizon),
-                                         int(k_local), device=dev, cost="reward", model="reward")
-            self._engine.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                           np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._engine_key = key
-            self._gamma_set = None
-        if self._gamma_set != float(self.gamma):
-            self._engine.set_discount(float(self.gamma))
-            self._gamma_set = float(self.gamma)
+        self._engine = self._cached("single", spec, S, A, k_local)
         return _attach_comm(self, self._engine)
 
     # controllers.py:121-158
     def get_action(self, state):
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        S, A, K = _shape(self)
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         rank, ws = _dist.world(self._group)
         lo, hi = _dist.shard_range(K, rank, ws)
@@ -757,33 +848,14 @@ class MPCcontrollerReward(Controller):
         (one seed per call), all environments in one launch chain (``RolloutEngine.get_actions``).
         ``rng="device"`` on one rank only."""
         _batch_rng_check(self.rng)
-        S = int(math.prod(self.env.observation_space.shape))
-        A = len(self.env.action_space.high)
-        K = int(self.num_simulated_paths)
-        if self.horizon < 1:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+        S, A, K = _shape(self)
         states = _batch_states(states, S, self._group)
         spec, norm, version = _weights.extract(self.dyn_model)
         _check_model(spec, "reward", type(self).__name__)
         seed = int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
         if K == 0:
             raise ValueError("attempt to get argmax of an empty sequence")
-        dev = _default_device() if self._device is None else self._device
-        key = (S, A, spec.hidden, spec.layer_norm, int(self.horizon), states.shape[0] * K, dev)
-        eng = getattr(self, "_batch_engine", None)
-        if eng is None or self._batch_key != key:
-            if eng is not None:
-                eng.close()
-            eng = self._batch_engine = RolloutEngine(S, A, spec.hidden, 2, "tanh", spec.layer_norm,
-                                                     int(self.horizon), states.shape[0] * K, device=dev,
-                                                     cost="reward", model="reward")
-            eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                  np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._batch_key = key
-            self._batch_gamma = None
-        if self._batch_gamma != float(self.gamma):
-            eng.set_discount(float(self.gamma))
-            self._batch_gamma = float(self.gamma)
+        self._batch_engine = eng = self._cached("batch", spec, S, A, states.shape[0] * K)
         eng.set_weights(spec, norm, version)
         res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
         self.last_rewards, self.last_reward, self.last_index = res.costs, res.best_cost, res.best_index
@@ -886,18 +958,9 @@ class MCTScontrollerPolicyNetReward(Controller):
         return np_action_paths
 
     def _engine_for(self, stage, spec, pspec, S, A, K, H, mode, dev) -> RolloutEngine:
-        key = (S, A, spec.hidden, spec.layer_norm, pspec.hidden, pspec.n_layers, int(K), int(H), mode, dev)
-        eng, old = self._engines.get(stage, (None, None))
-        if eng is None or old != key:
-            if eng is not None:
-                eng.close()
-            eng = RolloutEngine(S, A, spec.hidden, 2, "tanh", spec.layer_norm, int(H), int(K), device=dev,
-                                cost="reward", model="reward", policy_hidden=pspec.hidden,
-                                policy_layers=pspec.n_layers, policy_mode=mode)
-            eng.set_action_bounds(np.asarray(self.env.action_space.low, dtype=np.float64),
-                                  np.asarray(self.env.action_space.high, dtype=np.float64))
-            self._engines[stage] = (eng, key)
-        return eng
+        return _cached_engine(self, "_engines", stage, S, A, spec.hidden, 2, "tanh", spec.layer_norm, int(H), int(K),
+                              device=dev, cost="reward", model="reward", policy_hidden=pspec.hidden,
+                              policy_layers=pspec.n_layers, policy_mode=mode)
 
     # controllers.py:397-457
     def get_action(self, state):
@@ -909,7 +972,7 @@ class MCTScontrollerPolicyNetReward(Controller):
         spec, norm, version = _weights.extract(self.dyn_model)
         _check_model(spec, "reward", type(self).__name__)
         pspec, pversion = _policy.extract(self.policy_net)
-        dev = _default_device() if self._device is None else self._device
+        dev = _device(self)
         tdev = torch.device("cuda", dev)
         stream = torch.cuda.current_stream(tdev).cuda_stream
         if N == 0:
@@ -961,6 +1024,6 @@ class MCTScontrollerPolicyNetReward(Controller):
         return action_1s[best_action1_idx]
 
     def close(self):
-        for eng, _ in self._engines.values():
+        for _, eng in self._engines.values():
             eng.close()
         self._engines = {}

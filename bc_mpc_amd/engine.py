@@ -190,7 +190,80 @@ def _engine_config(state_dim: int, action_dim: int, hidden: int, n_layers: int, 
     return cfg, precision, team_try
 
 
-class RolloutEngine:
+class _EngineCalls:
+    """What RolloutEngine and ensemble.EnsembleEngine share: the host state of a fresh handle, the argument checks
+    and the single-plan CEM / MPPI calls, which differ between the two only in the C entry point (``_CEM`` /
+    ``_MPPI``).  The class provides ``_lib``, ``_h``, ``state_dim``, ``action_dim``, ``horizon``, ``num_paths``."""
+    _CEM, _MPPI = "bcmpc_cem_get_action", "bcmpc_mppi_get_action"
+
+    def _fresh(self) -> None:
+        """The wrapper's host state for a handle nothing has been set on yet."""
+        self._keep = []
+        self._wver = None
+        self._pol = None
+        self._gamma = None          # the discount the library holds (set_discount); None: never set
+        self.comm = None
+        self._mt_fast = None        # get_action_numpy_stream's prepared ctypes arguments
+        self._ga_fast = None        # get_action's (device actions, no cost vector) prepared ctypes arguments
+        self.cost_terms = None      # the TermCost of a cost="terms" engine (set_cost_terms)
+
+    def _state(self, state) -> np.ndarray:
+        st = _f64(state).reshape(-1)
+        if st.shape[0] != self.state_dim:
+            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
+        return st
+
+    def _actions(self, actions, dims: str = "(H, K, A)"):
+        """``actions`` as the kernels' ``[H, num_paths, A]`` f64 array and its pointer; (None, None): device Philox."""
+        if actions is None:
+            return None, None
+        actions = _f64(actions)
+        if actions.shape != (self.horizon, self.num_paths, self.action_dim):
+            raise ValueError(f"actions shape {actions.shape} != {dims} = "
+                             f"{(self.horizon, self.num_paths, self.action_dim)}")
+        return actions, _dp(actions)
+
+    def _step_result(self, res, costs=None) -> StepResult:
+        return StepResult(int(res.best_index), float(res.best_cost),
+                          np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
+
+    # ------------------------------------------------------------------ CEM / MPPI, one plan
+    def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
+                       seed: int) -> Tuple[StepResult, np.ndarray, np.ndarray]:
+        """All CEM iterations on this device (bcmpc_cem_get_action; an ensemble: bcmpc_ensemble_cem_get_action,
+        the elites of every iteration chosen by the combined value).  ``mu``/``sigma`` are ``[H, A]``; returns
+        (result with best_index = iteration*K + candidate, mu', sigma')."""
+        st = self._state(state)
+        shape = (self.horizon, self.action_dim)
+        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
+        s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
+        p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
+        res = _lib.Result()
+        _lib.check(getattr(self._lib, self._CEM)(self._h, _dp(st), ctypes.byref(p),
+                                                 ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
+                                                 ctypes.byref(res)))
+        return self._step_result(res), m, s
+
+    def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
+                        seed: int) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
+        """``iterations`` rounds of CEM-style rollout + MPPI update on this device (bcmpc_mppi_get_action; an
+        ensemble: bcmpc_ensemble_mppi_get_action, the softmin weights from the combined value; DESIGN.md "MPPI").
+        ``mu``/``sigma`` are ``[H, A]``; returns (the best single candidate over all rounds, best_index =
+        iteration*K + candidate; the updated plan mu', whose row 0 is the action to apply; the last round's
+        statistics).  sigma is not modified."""
+        st = self._state(state)
+        shape = (self.horizon, self.action_dim)
+        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
+        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
+        p = _lib.Mppi(int(iterations), float(temperature), 0)
+        res, stats = _lib.Result(), _lib.MppiStats()
+        _lib.check(getattr(self._lib, self._MPPI)(self._h, _dp(st), ctypes.byref(p),
+                                                  ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
+                                                  ctypes.byref(res), ctypes.byref(stats)))
+        return self._step_result(res), m, stats
+
+
+class RolloutEngine(_EngineCalls):
     """Owns one bcmpc_engine (one device, one candidate shard of size K)."""
 
     def __init__(self, state_dim: int, action_dim: int, hidden: int, n_layers: int,
@@ -228,13 +301,7 @@ class RolloutEngine:
         self.layer_norm, self.horizon, self.num_paths = bool(layer_norm), horizon, num_paths
         self.device, self.cost, self.model = device, cost, model
         self.policy_hidden, self.policy_layers, self.policy_mode = policy_hidden, policy_layers, policy_mode
-        self._keep = []
-        self._wver = None
-        self._pol = None
-        self.comm = None
-        self._mt_fast = None        # get_action_numpy_stream's prepared ctypes arguments
-        self._ga_fast = None        # get_action's (device actions, no cost vector) prepared ctypes arguments
-        self.cost_terms = None      # the TermCost of a cost="terms" engine (set_cost_terms)
+        self._fresh()
 
     # ------------------------------------------------------------------ weights
     def set_weights(self, spec: MLPSpec, normalization: Sequence, version: int) -> None:
@@ -323,8 +390,13 @@ class RolloutEngine:
         return out
 
     def set_discount(self, gamma: float) -> None:
-        """MPCcontrollerReward.gamma (controllers.py:139): step h's reward is scaled by gamma**h."""
-        _lib.check(self._lib.bcmpc_set_discount(self._h, ctypes.c_double(float(gamma))))
+        """MPCcontrollerReward.gamma (controllers.py:139): step h's reward is scaled by gamma**h.  Idempotent on
+        the value: the library is told once per change (and once on a fresh engine)."""
+        gamma = float(gamma)
+        if gamma == self._gamma:
+            return
+        _lib.check(self._lib.bcmpc_set_discount(self._h, ctypes.c_double(gamma)))
+        self._gamma = gamma
 
     @property
     def weights_version(self) -> int:
@@ -400,23 +472,14 @@ class RolloutEngine:
             if rc:
                 _lib.check(rc)
             return StepResult(res.best_index, res.best_cost, first.copy(), None)
-        st = _f64(state).reshape(-1)
-        if st.shape[0] != self.state_dim:
-            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
-        act_p = None
-        if actions is not None:
-            actions = _f64(actions)
-            if actions.shape != (self.horizon, self.num_paths, self.action_dim):
-                raise ValueError(f"actions shape {actions.shape} != (H, K, A) = "
-                                 f"{(self.horizon, self.num_paths, self.action_dim)}")
-            act_p = _dp(actions)
+        st = self._state(state)
+        actions, act_p = self._actions(actions)
         res = _lib.Result()
         costs = np.empty(self.num_paths, dtype=np.float64) if return_costs else None
         _lib.check(self._lib.bcmpc_get_action(
             self._h, _dp(st), act_p, ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
             ctypes.byref(res), _dp(costs) if costs is not None else None))
-        return StepResult(int(res.best_index), float(res.best_cost),
-                          np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
+        return self._step_result(res, costs)
 
     def _n_envs(self, n_envs: int) -> int:
         n_envs = int(n_envs)
@@ -438,13 +501,7 @@ class RolloutEngine:
         if st.ndim != 2 or st.shape[1] != self.state_dim:
             raise ValueError(f"states shape {st.shape} != (B, S) = (B, {self.state_dim})")
         B = self._n_envs(st.shape[0])
-        act_p = None
-        if actions is not None:
-            actions = _f64(actions)
-            if actions.shape != (self.horizon, self.num_paths, self.action_dim):
-                raise ValueError(f"actions shape {actions.shape} != (H, B*K, A) = "
-                                 f"{(self.horizon, self.num_paths, self.action_dim)}")
-            act_p = _dp(actions)
+        actions, act_p = self._actions(actions, "(H, B*K, A)")
         res = (_lib.Result * B)()
         costs = np.empty(self.num_paths, dtype=np.float64) if return_costs else None
         _lib.check(self._lib.bcmpc_get_actions_batch(
@@ -516,9 +573,7 @@ class RolloutEngine:
                 return None
             bg, key_p, pos_p = mt
             if return_costs:
-                s = _f64(state).reshape(-1)
-                if s.shape[0] != self.state_dim:
-                    raise ValueError(f"state has {s.shape[0]} dims, expected {self.state_dim}")
+                s = self._state(state)
                 res = _lib.Result()
                 costs = np.empty(self.num_paths, dtype=np.float64)
                 with bg.lock:
@@ -526,8 +581,7 @@ class RolloutEngine:
                         self._h, _dp(s), key_p, pos_p, _dp(bounds[0]), _dp(bounds[1]), ctypes.c_int64(k_global),
                         ctypes.c_int64(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.byref(res),
                         _dp(costs)))
-                return StepResult(int(res.best_index), float(res.best_cost),
-                                  np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
+                return self._step_result(res, costs)
             # the per-env-step call (no cost vector): ctypes arguments built once per (generator, bounds,
             # shard, seed) and reused -- the state goes into an engine-owned buffer, the first action is
             # copied out of a NumPy view on the result record (~6 us of Python per call less)
@@ -557,9 +611,7 @@ class RolloutEngine:
         st = np.random.get_state()
         lo = np.asarray(low, dtype=np.float64)
         hi = np.asarray(high, dtype=np.float64)
-        s = _f64(state).reshape(-1)
-        if s.shape[0] != self.state_dim:
-            raise ValueError(f"state has {s.shape[0]} dims, expected {self.state_dim}")
+        s = self._state(state)
         key = np.array(st[1], dtype=np.uint32)
         pos = ctypes.c_int32(int(st[2]))
         res = _lib.Result()
@@ -570,8 +622,7 @@ class RolloutEngine:
             ctypes.byref(res),
             _dp(costs) if costs is not None else None))
         np.random.set_state((st[0], key, pos.value, st[3], st[4]))
-        return StepResult(int(res.best_index), float(res.best_cost),
-                          np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
+        return self._step_result(res, costs)
 
     def numpy_stream_draw(self, low, high, k_global: int, cand_offset: int = 0) -> np.ndarray:
         """This engine's shard ``[:, cand_offset:cand_offset + K]`` of the array
@@ -622,24 +673,6 @@ class RolloutEngine:
             ctypes.c_void_p(stream)))
 
     # ------------------------------------------------------------------ CEM
-    def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
-                       seed: int) -> Tuple[StepResult, np.ndarray, np.ndarray]:
-        """All CEM iterations on this device (bcmpc_cem_get_action).  ``mu``/``sigma`` are
-        ``[H, A]``; returns (result with best_index = iteration*K + candidate, mu', sigma')."""
-        st = _f64(state).reshape(-1)
-        if st.shape[0] != self.state_dim:
-            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
-        shape = (self.horizon, self.action_dim)
-        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
-        s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
-        p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
-        res = _lib.Result()
-        _lib.check(self._lib.bcmpc_cem_get_action(self._h, _dp(st), ctypes.byref(p),
-                                                  ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                  ctypes.byref(res)))
-        return (StepResult(int(res.best_index), float(res.best_cost),
-                           np.array(res.first_action[: self.action_dim], dtype=np.float64)), m, s)
-
     def cem_rollout_async(self, d_state: int, d_mu: int, d_sigma: int, seed: int, iteration: int,
                           cand_offset: int, k_global: int, d_costs: int, d_result: Optional[int], merge: bool,
                           stream: Optional[int] = None) -> None:
@@ -666,26 +699,6 @@ class RolloutEngine:
             int(iteration), float(alpha), ctypes.c_void_p(d_mu), ctypes.c_void_p(d_sigma), ctypes.c_void_p(stream)))
 
     # ------------------------------------------------------------------ MPPI
-    def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
-                        seed: int) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
-        """``iterations`` rounds of CEM-style rollout + MPPI update on this device
-        (bcmpc_mppi_get_action; DESIGN.md "MPPI").  ``mu``/``sigma`` are ``[H, A]``; returns (the best
-        single candidate over all rounds, best_index = iteration*K + candidate; the updated plan mu',
-        whose row 0 is the action to apply; the last round's statistics).  sigma is not modified."""
-        st = _f64(state).reshape(-1)
-        if st.shape[0] != self.state_dim:
-            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
-        shape = (self.horizon, self.action_dim)
-        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
-        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
-        p = _lib.Mppi(int(iterations), float(temperature), 0)
-        res, stats = _lib.Result(), _lib.MppiStats()
-        _lib.check(self._lib.bcmpc_mppi_get_action(self._h, _dp(st), ctypes.byref(p),
-                                                   ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                   ctypes.byref(res), ctypes.byref(stats)))
-        return (StepResult(int(res.best_index), float(res.best_cost),
-                           np.array(res.first_action[: self.action_dim], dtype=np.float64)), m, stats)
-
     def mppi_update_async(self, d_costs: int, m: int, cand_offset: int, seed: int, iteration: int,
                           temperature: float, d_mu: int, d_sigma: int, d_stats: int,
                           stream: Optional[int] = None) -> None:

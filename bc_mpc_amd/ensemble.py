@@ -22,12 +22,16 @@ import ctypes
 import math
 import random
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from .engine import (BatchResult, MLPSpec, RolloutEngine, StepResult, _dp, _engine_config, _f64)
+from . import distributed as _dist
+from . import weights as _weights
+from .controllers import _batch_rng_check, _batch_states, _cached_engine, _device, _device_terms, _shape
+from .cost_functions import is_cheetah_cost
+from .engine import BatchResult, MLPSpec, RolloutEngine, StepResult, _dp, _engine_config, _EngineCalls, _f64
 
 RULES = ("mean", "mean_std", "worst")
 MAX_MEMBERS = _lib.MAX_MEMBERS
@@ -92,13 +96,7 @@ class _Member(RolloutEngine):
                      "num_paths", "device", "cost", "precision"):
             setattr(self, name, getattr(owner, name))
         self.model, self.policy_hidden, self.policy_layers, self.policy_mode = "delta", 0, 0, "explore"
-        self._keep = []
-        self._wver = None
-        self._pol = None
-        self.comm = None
-        self._mt_fast = None
-        self._ga_fast = None
-        self.cost_terms = None
+        self._fresh()
 
     def close(self) -> None:
         self._ga_fast = None
@@ -106,10 +104,12 @@ class _Member(RolloutEngine):
         self._h = None
 
 
-class EnsembleEngine:
+class EnsembleEngine(_EngineCalls):
     """Owns one bcmpc_ensemble: ``n_members`` engines of one configuration (hence one kernel layout) on one
     device.  The constructor arguments after ``n_members`` are RolloutEngine's (no policy, ``cost`` "cheetah"
-    or "terms", the delta model)."""
+    or "terms", the delta model); ``cem_get_action`` / ``mppi_get_action`` are RolloutEngine's too, on the
+    ensemble's entry points."""
+    _CEM, _MPPI = "bcmpc_ensemble_cem_get_action", "bcmpc_ensemble_mppi_get_action"
 
     def __init__(self, n_members: int, state_dim: int, action_dim: int, hidden: int, n_layers: int,
                  activation: str, layer_norm: bool, horizon: int, num_paths: int, device: int = 0,
@@ -158,21 +158,6 @@ class EnsembleEngine:
         self.rule, self.kappa = rule, float(kappa)
 
     # ------------------------------------------------------------------ calls
-    def _state(self, state) -> np.ndarray:
-        st = _f64(state).reshape(-1)
-        if st.shape[0] != self.state_dim:
-            raise ValueError(f"state has {st.shape[0]} dims, expected {self.state_dim}")
-        return st
-
-    def _actions(self, actions):
-        if actions is None:
-            return None, None
-        actions = _f64(actions)
-        if actions.shape != (self.horizon, self.num_paths, self.action_dim):
-            raise ValueError(f"actions shape {actions.shape} != (H, K, A) = "
-                             f"{(self.horizon, self.num_paths, self.action_dim)}")
-        return actions, _dp(actions)
-
     def get_action(self, state, actions: Optional[np.ndarray] = None, seed: int = 0, cand_offset: int = 0,
                    return_costs: bool = False, return_member_costs: bool = False) -> EnsembleStepResult:
         """bcmpc_ensemble_get_action: every candidate scored by every member, the argmin over ``v``."""
@@ -211,36 +196,6 @@ class EnsembleEngine:
                                    rec[:, 2:2 + self.action_dim].copy(),
                                    v.reshape(B, -1) if v is not None else None,
                                    mc.reshape(self.n_members, B, -1) if mc is not None else None)
-
-    def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
-                       seed: int) -> Tuple[StepResult, np.ndarray, np.ndarray]:
-        """bcmpc_ensemble_cem_get_action; arguments and results as RolloutEngine.cem_get_action."""
-        st = self._state(state)
-        shape = (self.horizon, self.action_dim)
-        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
-        s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
-        p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
-        res = _lib.Result()
-        _lib.check(self._lib.bcmpc_ensemble_cem_get_action(self._h, _dp(st), ctypes.byref(p),
-                                                           ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                           ctypes.byref(res)))
-        return (StepResult(int(res.best_index), float(res.best_cost),
-                           np.array(res.first_action[: self.action_dim], dtype=np.float64)), m, s)
-
-    def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
-                        seed: int) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
-        """bcmpc_ensemble_mppi_get_action; arguments and results as RolloutEngine.mppi_get_action."""
-        st = self._state(state)
-        shape = (self.horizon, self.action_dim)
-        m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
-        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
-        p = _lib.Mppi(int(iterations), float(temperature), 0)
-        res, stats = _lib.Result(), _lib.MppiStats()
-        _lib.check(self._lib.bcmpc_ensemble_mppi_get_action(self._h, _dp(st), ctypes.byref(p),
-                                                            ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                            ctypes.byref(res), ctypes.byref(stats)))
-        return (StepResult(int(res.best_index), float(res.best_cost),
-                           np.array(res.first_action[: self.action_dim], dtype=np.float64)), m, stats)
 
     def reduce_async(self, d_member_costs: int, ld: int, n_members: int, K: int, rule: str, kappa: float,
                      d_out: int, stream: Optional[int] = None) -> None:
@@ -396,12 +351,9 @@ def is_ensemble(dyn_model) -> bool:
 
 
 def _ctrl_engine(ctrl, S: int, A: int, k_total: int, slot: str) -> EnsembleEngine:
-    """The controller's EnsembleEngine for (shape, K), rebuilt when either changes; the members' weights, the
-    cost terms and the model's rule are brought up to date on every call (each a no-op when unchanged)."""
-    from . import distributed as _dist
-    from . import weights as _weights
-    from .controllers import _default_device, _device_terms
-    from .cost_functions import is_cheetah_cost
+    """The controller's EnsembleEngine for (shape, K) in ``ctrl._ens_engines[slot]`` (``controllers._cached_engine``);
+    the members' weights, the cost terms and the model's rule are brought up to date on every call (each a no-op
+    when unchanged)."""
     model = ctrl.dyn_model
     _, ws = _dist.world(ctrl._group)
     if ws > 1:
@@ -416,21 +368,9 @@ def _ctrl_engine(ctrl, S: int, A: int, k_total: int, slot: str) -> EnsembleEngin
     if any(s[0].model != "delta" for s in specs):
         raise TypeError("EnsembleDynamicsModel members must be NNDynamicsModel nets (reward-model ensembles "
                         "are not covered)")
-    dev = _default_device() if ctrl._device is None else ctrl._device
-    key = (len(specs), S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm, int(ctrl.horizon),
-           int(k_total), dev, terms is not None)
-    engines = ctrl.__dict__.setdefault("_ens_engines", {})
-    hit = engines.get(slot)
-    if hit is None or hit[0] != key:
-        if hit is not None:
-            hit[1].close()
-        eng = EnsembleEngine(len(specs), S, A, spec.hidden, spec.n_layers, spec.activation, spec.layer_norm,
-                             int(ctrl.horizon), int(k_total), device=dev,
-                             cost="cheetah" if terms is None else "terms")
-        eng.set_action_bounds(np.asarray(ctrl.env.action_space.low, dtype=np.float64),
-                              np.asarray(ctrl.env.action_space.high, dtype=np.float64))
-        engines[slot] = hit = (key, eng)
-    eng = hit[1]
+    eng = _cached_engine(ctrl, "_ens_engines", slot, len(specs), S, A, spec.hidden, spec.n_layers, spec.activation,
+                         spec.layer_norm, int(ctrl.horizon), int(k_total), make=EnsembleEngine, device=_device(ctrl),
+                         cost="cheetah" if terms is None else "terms")
     if terms is not None:
         eng.set_cost_terms(terms)
     for i, (s, norm, version) in enumerate(specs):
@@ -458,10 +398,7 @@ def mpc_get_action(ctrl, state):
     """MPCcontroller.get_action on an EnsembleDynamicsModel.  ``rng="numpy"``: the reference's one
     ``np.random.uniform`` draw, made on the host and uploaded once as the explicit action array of every
     member; ``rng="device"``: Philox in the kernels, one seed per call."""
-    S, A = ctrl._dims()
-    K = int(ctrl.num_simulated_paths)
-    if ctrl.horizon < 1:
-        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    S, A, K = _shape(ctrl)
     state = np.asarray(state, dtype=np.float64).reshape(-1)
     if K == 0:
         if ctrl.rng == "numpy":
@@ -487,12 +424,8 @@ def mpc_get_action(ctrl, state):
 
 def mpc_get_actions(ctrl, states):
     """MPCcontroller.get_actions on an EnsembleDynamicsModel (``rng="device"``, one rank)."""
-    from .controllers import _batch_rng_check, _batch_states
     _batch_rng_check(ctrl.rng)
-    S, A = ctrl._dims()
-    K = int(ctrl.num_simulated_paths)
-    if ctrl.horizon < 1:
-        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    S, A, K = _shape(ctrl)
     states = _batch_states(states, S, ctrl._group)
     seed = ctrl._next_seed()
     if K == 0:
@@ -505,43 +438,3 @@ def mpc_get_actions(ctrl, states):
     ctrl.last_cost, ctrl.last_index = res.best_cost, res.best_index
     _diagnose(ctrl, res.member_costs, res.best_index - np.arange(B) * K)
     return res.first_action
-
-
-def _plan_prologue(ctrl):
-    S = int(math.prod(ctrl.env.observation_space.shape))
-    A = len(ctrl.env.action_space.high)
-    K = int(ctrl.num_simulated_paths)
-    if ctrl.horizon < 1:
-        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
-    if K == 0:
-        raise ValueError("attempt to get argmin of an empty sequence")
-    return S, A, K
-
-
-def cem_get_action(ctrl, state):
-    """CEMcontroller.get_action on an EnsembleDynamicsModel: the elites of every iteration come from ``v``."""
-    S, A, K = _plan_prologue(ctrl)
-    state = np.asarray(state, dtype=np.float64).reshape(-1)
-    eng = _ctrl_engine(ctrl, S, A, K, "single")
-    mu0, sd0 = ctrl.initial_distribution()
-    seed = int(ctrl._seed_rng.randint(0, 2**62, dtype=np.int64))
-    res, mu, sd = eng.cem_get_action(state, mu0, sd0, ctrl.iterations, min(ctrl.n_elite, K), ctrl.alpha, seed)
-    ctrl._mu = mu
-    ctrl.last_mu, ctrl.last_sigma = mu, sd
-    ctrl.last_cost, ctrl.last_position = res.best_cost, res.best_index
-    return res.first_action
-
-
-def mppi_get_action(ctrl, state):
-    """MPPIcontroller.get_action on an EnsembleDynamicsModel: the softmin weights come from ``v``."""
-    S, A, K = _plan_prologue(ctrl)
-    state = np.asarray(state, dtype=np.float64).reshape(-1)
-    eng = _ctrl_engine(ctrl, S, A, K, "single")
-    mu0, sd0 = ctrl.initial_distribution()
-    seed = int(ctrl._seed_rng.randint(0, 2**62, dtype=np.int64))
-    res, mu, stats = eng.mppi_get_action(state, mu0, sd0, ctrl.iterations, ctrl.temperature, seed)
-    ctrl._mu = mu
-    ctrl.last_mu = mu
-    ctrl.last_cost, ctrl.last_position = res.best_cost, res.best_index
-    ctrl.last_ess, ctrl.last_stats = float(stats.ess), stats
-    return mu[0].copy()

@@ -264,3 +264,103 @@ def test_vectorised_select_matches_the_pairwise_order(seed):
             want = r
     got = dd.select(recs)
     assert np.array_equal(got, want, equal_nan=True)
+
+
+# ------------------------------------------------------------------ the controllers' engine cache
+def _recording_engine(log):
+    """RolloutEngine with its constructor and its library replaced: every C entry a setter reaches is logged as
+    (engine number, entry name, first scalar argument or None)."""
+    from bc_mpc_amd.engine import RolloutEngine
+
+    class Lib:
+        def __init__(self, n):
+            self.n = n
+
+        def __getattr__(self, name):
+            def entry(handle, *args):
+                log.append((self.n, name, getattr(args[0], "value", None) if args else None))
+                return 0
+            return entry
+
+    class Engine(RolloutEngine):
+        built = 0
+
+        def __init__(self, *args, **kwargs):
+            Engine.built += 1
+            self.n, self.args, self.kwargs = Engine.built, args, kwargs
+            self._lib, self._h, self.device = Lib(self.n), object(), kwargs.get("device", 0)
+            self._fresh()
+            log.append((self.n, "build", None))
+
+        def close(self):
+            log.append((self.n, "close", None))
+            self._h = None
+
+        def __del__(self):
+            pass
+    return Engine
+
+
+@pytest.mark.parametrize("cls", ["MPCcontrollerReward", "CEMcontroller", "MPPIcontroller"])
+def test_engine_cache_builds_per_key_and_sets_the_discount_per_value(monkeypatch, cls):
+    """controllers._cached_engine behind _engine_for: one build per constructor-argument set, the old engine
+    closed on a change, the bounds applied once per build; set_discount reaches the library once per distinct
+    value and once on every new engine."""
+    import bc_mpc_amd
+    from bc_mpc_amd import controllers as C
+    from oracle import mpc_oracle as orc
+    log = []
+    monkeypatch.setattr(C, "RolloutEngine", _recording_engine(log))
+    dyn = orc.NumpyRewardDynamics(orc.synthetic_reward_weights(20, 6, 64), orc.synthetic_normalization(reward=True))
+    spec = ww.extract(dyn)[0]
+    ctrl = getattr(bc_mpc_amd, cls)(_Env(), dyn, 3, None, 8, gamma=1.0)
+
+    def took(call):
+        del log[:]
+        call()
+        return [(n, name, v) for n, name, v in log if name != "bcmpc_engine_set_comm"]
+    first = took(lambda: ctrl._engine_for(spec, 20, 6, 8))
+    assert first == [(1, "build", None), (1, "bcmpc_set_action_bounds", None), (1, "bcmpc_set_discount", 1.0)]
+    e1 = ctrl._engine
+    assert e1.args == (20, 6, 64, 2, "tanh", False, 3, 8) and e1.kwargs["cost"] == e1.kwargs["model"] == "reward"
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 8)) == [] and ctrl._engine is e1
+    ctrl.gamma = 0.9                                    # the discount alone: the engine stays
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 8)) == [(1, "bcmpc_set_discount", 0.9)]
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 8)) == [] and ctrl._engine is e1
+    # K, then the horizon: the old engine is closed, the new one gets the bounds and the (unchanged) discount
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 16)) == [
+        (1, "close", None), (2, "build", None), (2, "bcmpc_set_action_bounds", None), (2, "bcmpc_set_discount", 0.9)]
+    assert e1._h is None and ctrl._engine.n == 2
+    ctrl.horizon = 4
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 16)) == [
+        (2, "close", None), (3, "build", None), (3, "bcmpc_set_action_bounds", None), (3, "bcmpc_set_discount", 0.9)]
+    ctrl.gamma = 1.0
+    assert took(lambda: ctrl._engine_for(spec, 20, 6, 16)) == [(3, "bcmpc_set_discount", 1.0)]
+    # the batched slot is a cache of its own
+    if cls != "MPCcontrollerReward":
+        assert ctrl._batch_engine is None
+        assert took(lambda: ctrl._batch_engine_for(spec, 20, 6, 32))[0] == (4, "build", None)
+        assert took(lambda: ctrl._batch_engine_for(spec, 20, 6, 32)) == [] and ctrl._batch_engine.n == 4
+        assert ctrl._engine.n == 3 and ctrl._engine._h is not None
+
+
+def test_cached_engine_keys_on_the_constructor_arguments(monkeypatch):
+    from bc_mpc_amd import controllers as C
+    log = []
+    monkeypatch.setattr(C, "RolloutEngine", _recording_engine(log))
+
+    class Ctrl:
+        env = _Env()
+    c = Ctrl()
+    a = C._cached_engine(c, "_engines", "single", 20, 6, 64, device=0, cost="cheetah")
+    assert C._cached_engine(c, "_engines", "single", 20, 6, 64, device=0, cost="cheetah") is a
+    assert C._cached_engine(c, "_engines", "single", 20, 6, 64, cost="cheetah", device=0) is a
+    b = C._cached_engine(c, "_engines", "batch", 20, 6, 64, device=0, cost="cheetah")   # another slot
+    assert b is not a and a._h is not None
+    t = C._cached_engine(c, "_engines", "single", 20, 6, 64, device=0, cost="terms")    # a keyword changed
+    assert t is not a and a._h is None and b._h is not None
+    made = []
+    e = C._cached_engine(c, "_other", "single", 3, 20, make=lambda *x, **k: made.append((x, k)) or C.RolloutEngine())
+    assert made == [((3, 20), {})] and c._other["single"] == (((3, 20), {}), e) and c._engines["single"][1] is t
+    assert [x[1] for x in log].count("build") == 4 and [x[1] for x in log].count("bcmpc_set_action_bounds") == 4
+    assert [x[1] for x in log].count("close") == 1
