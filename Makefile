@@ -8,21 +8,23 @@ LIB      := bc_mpc_amd/libbcmpc.so
 # every other one a kernel unit (.hip); OBJ in link order
 HOSTOBJ  := capi mt_draw planners
 CXXOBJ   := mt19937 mt_jump
-OBJ      := $(patsubst %,build/%.o,rollout rollout_grp rollout_x3 rollout_x3_plain rollout_team cem mppi batch \
+OBJ      := $(patsubst %,build/%.o,rollout rollout_grp rollout_x3 rollout_x3_plain rollout_pp rollout_team cem mppi batch \
               plan_batch term_cost ensemble fit $(HOSTOBJ) $(CXXOBJ) mt_device comm)
 # header dependencies come from the compiler (build/*.d): a header rebuilds exactly the objects that include it
 DEPFLAGS := -MMD -MP
 
 all: $(LIB)
 
-# the split kernel in two units (X3_PART in rollout_x3.hip), each with the scheduler that measured best
-# (profiles/r01_sched_ilp_ab.txt, profiles/r01_sched_part2_ab.txt): the plain tanh delta net with
-# iterative-ILP (-1..2% kernel time at cfg3/cfg4), the policy / reward / relu-LN kernels with max-ILP
+# the split kernels in three units, each with the scheduler that measured best
+# (profiles/r01_sched_ilp_ab.txt, profiles/r01_sched_part2_ab.txt): the plain tanh delta net
+# (rollout_x3_plain) with iterative-ILP (-1..2% kernel time at cfg3/cfg4); the policy / reward / relu-LN /
+# single-pass kernels (rollout_x3) and the two pipelined kernels (rollout_pp) with max-ILP
 # (-0.6..1.7%; iterative-ILP spills the policy+reward kernel, +10%)
 X3ILP    ?= -mllvm -amdgpu-sched-strategy=iterative-ilp
 X3P2     ?= -mllvm -amdgpu-sched-strategy=max-ilp
-build/rollout_x3.o:       EXTRA = $(X3P2) -DX3_PART=2
-build/rollout_x3_plain.o: EXTRA = $(X3ILP) -DX3_PART=1
+build/rollout_x3.o:       EXTRA = $(X3P2)
+build/rollout_pp.o:       EXTRA = $(X3P2)
+build/rollout_x3_plain.o: EXTRA = $(X3ILP)
 
 # the team kernels with the iterative ILP scheduler: ppo_defaults -2.4 us, ppo_mpc_default -5.5 us, run.sh
 # recipe -4.8 us per call against the default (max-ilp +2.5..+21 us, iterative-minreg +0..+24 us;
@@ -33,10 +35,6 @@ build/rollout_team.o:     EXTRA = $(TEAMSCHED)
 HIPCOMPILE = $(strip $(HIPCC) $(HIPFLAGS) $(EXTRA) $(DEPFLAGS) -c $< -o $@)
 
 build/%.o: $(SRC)/%.hip
-	@mkdir -p build
-	$(HIPCOMPILE)
-
-build/rollout_x3_plain.o: $(SRC)/rollout_x3.hip
 	@mkdir -p build
 	$(HIPCOMPILE)
 

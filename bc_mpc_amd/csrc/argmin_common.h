@@ -1,5 +1,5 @@
 // argmin_common.h -- the np.argmin result record (controllers.py:82-85), shared by the
-// two-launch argmin (rollout.hip) and the split kernel's fused tail (rollout_x3.hip).
+// two-launch argmin (rollout.hip) and the split kernels' fused tails (rollout_x3.h, rollout_pp.h).
 #pragma once
 #include "device_common.h"
 #include "kernels.h"

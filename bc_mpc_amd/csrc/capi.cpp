@@ -49,7 +49,7 @@ void pack_out_rows(const float* W, int in, int out, int Tin, const int* rowmap, 
             }
 }
 
-// Split-f16 kernel (rollout_x3.hip): W [in][out] scaled by sw, every element as
+// Split-f16 kernel (rollout_x3.h): W [in][out] scaled by sw, every element as
 // hi = f16(w), lo = f16(w - hi), in fragment order [ws][p][j][hi|lo][lane][i],
 // t = ws*TWp + j: lane's 8 halves of tile t, k-step p are W[k][n] with
 // n = 16t + (lane&15), k = 32p + 16(i>>2) + 4(lane>>4) + (i&3) -- the k order in

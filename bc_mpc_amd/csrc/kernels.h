@@ -224,6 +224,8 @@ bool x3_pp3_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);
 size_t x3_pp3_lds(int hidden_padded, int state_dim, int action_dim);
 bool x3_pp3_args_ok(const RolloutArgs& a, int hidden_padded);
 hipError_t launch_rollout_pp3(const RolloutArgs& a, int hidden_padded, hipStream_t st);
+// (rollout_pp: what launch_rollout_x3_f16 runs when a.x3_pp is set)
+hipError_t launch_rollout_pp(const RolloutArgs& a, int hidden_padded, hipStream_t st);
 hipError_t launch_rollout_x3(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
 hipError_t launch_rollout_x3_f16(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
 // rollout_team.hip; kind: 0 the plain delta net, 1 + fused policy, 2 the reward net (+ policy)

@@ -1,4 +1,4 @@
-// split_common.h -- helpers shared by the split-f16 rollout kernels (rollout_x3.hip,
+// split_common.h -- helpers shared by the split-f16 rollout kernels (rollout_x3.h, rollout_pp.h,
 // rollout_team.hip): the hi/lo f16 operand split, the tanh epilogue on element pairs and
 // the cross-row lane exchanges.  Internal to libbcmpc.
 #pragma once
