@@ -14,10 +14,12 @@ from .mppi import MPPIcontroller
 from .cost_functions import TermCost, cheetah_cost_fn, cheetah_terms, trajectory_cost_fn
 from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
 from .ensemble import EnsembleDynamicsModel, EnsembleEngine
+from . import value
+from .value import ValueSpec
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
            "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult",
-           "EnsembleEngine", "EnsembleDynamicsModel"]
+           "EnsembleEngine", "EnsembleDynamicsModel", "ValueSpec"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

@@ -101,6 +101,22 @@ class Policy(ctypes.Structure):
 
 POLICY_MODES = {"explore": 0, "stochastic": 1}
 
+VALUE_MAX_LAYERS, VALUE_MAX_HIDDEN = 4, 256
+
+
+class ValueNet(ctypes.Structure):
+    """bcmpc_value_net: the critic of a terminal value (bc_mpc_amd/value.py ValueSpec)."""
+    _fields_ = [
+        ("kernels", ctypes.POINTER(_FP)),
+        ("biases", ctypes.POINTER(_FP)),
+        ("ob_mean", _FP),
+        ("ob_std", _FP),
+        ("n_layers", ctypes.c_int32),
+        ("hidden", ctypes.c_int32),
+        ("state_dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
 
 class Cem(ctypes.Structure):
     _fields_ = [
@@ -188,6 +204,14 @@ SIGNATURES = [
     ("bcmpc_trajectory_cost_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_terminal_value_supported", ctypes.c_int, [ctypes.POINTER(Config)]),
+    ("bcmpc_set_terminal_value", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ValueNet), ctypes.c_double, ctypes.c_uint64]),
+    ("bcmpc_terminal_value_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("bcmpc_last_terminal_values", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, _FP]),
     ("bcmpc_get_action", ctypes.c_int,
      [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
     ("bcmpc_get_actions_batch", ctypes.c_int,

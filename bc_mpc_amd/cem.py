@@ -63,9 +63,12 @@ class CEMcontroller(Planner):
                  warm_start: bool = True,
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
-                 process_group=None):
+                 process_group=None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
-                         warm_start, 0xCE5EED if seed is None else seed, device, process_group)
+                         warm_start, 0xCE5EED if seed is None else seed, device, process_group,
+                         terminal_value=terminal_value, terminal_weight=terminal_weight)
         self.elite_frac = float(elite_frac)
         self._n_elite = n_elite
         self.alpha = float(alpha)
@@ -79,6 +82,7 @@ class CEMcontroller(Planner):
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        self._note_planner_value(eng, res.best_index, K)
         return self._publish(res.best_cost, res.best_index, res.first_action, mu, sd)
 
     def _sharded(self, rank, ws, state, spec, norm, version, terms, mu0, sd0, seed, S, A, K):
@@ -100,6 +104,7 @@ class CEMcontroller(Planner):
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu, self.last_sigma = mu, sd
         self.last_cost, self.last_position = res.best_cost, res.best_index

@@ -44,6 +44,7 @@ import numpy as np
 
 from . import distributed as _dist
 from . import policy as _policy
+from . import value as _value
 from . import weights as _weights
 from .cost_functions import TermCost, is_cheetah_cost, trajectory_cost_fn
 from .engine import RolloutEngine
@@ -199,7 +200,56 @@ def _cached_engine(ctrl, store: str, slot: str, *args, make=None, **kwargs):
     return hit[1]
 
 
-class Planner(Controller):
+class _TerminalValue:
+    """The controllers' ``terminal_value=`` / ``terminal_weight=`` (value.py): a container ``value.extract`` reads
+    (or None), applied to the engine of every call after the cache lookup -- an idempotent setter, never a cache
+    key, so a new weight or a new version of the net rebuilds no engine."""
+    terminal_value = None
+    terminal_weight = -1.0
+    _tv_last = None             # (engine, local candidate indices or None) of the last call
+
+    def _init_terminal_value(self, terminal_value, terminal_weight) -> None:
+        self.terminal_value = terminal_value
+        self.terminal_weight = _value.check_weight(terminal_weight)
+        if terminal_value is not None:
+            _value.extract(terminal_value)          # a container that cannot be read fails here, not mid-episode
+
+    def _apply_terminal_value(self, eng) -> None:
+        self._tv_last = None
+        if self.terminal_value is None:
+            if getattr(eng, "terminal_value", None) is not None:    # (an engine that never held one is not asked)
+                eng.set_terminal_value(None)
+            return
+        spec, version = _value.extract(self.terminal_value)
+        if spec.state_dim != eng.state_dim:
+            raise ValueError(f"terminal_value reads {spec.state_dim} state dims, the environment has {eng.state_dim}")
+        eng.set_terminal_value(spec, _value.check_weight(self.terminal_weight), version)
+
+    def _note_terminal_value(self, eng, local_indices) -> None:
+        self._tv_last = (eng, local_indices) if self.terminal_value is not None else None
+
+    @property
+    def last_terminal_value(self):
+        """Diagnostics: the winner's ``v`` (f32) of the last call -- a float, ``[B]`` for ``get_actions``,
+        ``[E]`` (every member's value of its own final state) on an ensemble -- or None: no terminal value, or
+        a CEM / MPPI winner from an iteration before the last (the engine keeps the last iteration's values)."""
+        if self._tv_last is None or self._tv_last[1] is None:
+            return None
+        eng, idx = self._tv_last
+        members = getattr(eng, "members", None)
+        if members is not None:
+            return np.array([m.last_terminal_values(idx)[0] for m in members], dtype=np.float32)
+        v = eng.last_terminal_values(idx)
+        return float(v[0]) if np.ndim(idx) == 0 else v
+
+
+def _refuse_terminal_value(who: str, terminal_value) -> None:
+    if terminal_value is not None:
+        raise ValueError(f"{who} does not take a terminal_value: value nets over a fused policy, the reward "
+                         "model or MCTS are not covered (MPCcontroller, CEMcontroller and MPPIcontroller are)")
+
+
+class Planner(_TerminalValue, Controller):
     """What CEMcontroller (cem.py) and MPPIcontroller (mppi.py) share: a plan ``mu`` ``[H, A]`` refined over
     ``iterations`` rounds of sampling around it, warm-started from the previous call's plan; ``get_actions``
     keeps one plan per environment and the B*K-candidate engine next to ``get_action``'s own.  A subclass names
@@ -208,7 +258,8 @@ class Planner(Controller):
     _KIND = None            # "CEM" | "MPPI": the refusals' wording
 
     def __init__(self, env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
-                 warm_start, seed, device, process_group):
+                 warm_start, seed, device, process_group, terminal_value=None, terminal_weight=-1.0):
+        self._init_terminal_value(terminal_value, terminal_weight)
         self.env = env
         self.dyn_model = dyn_model
         self.horizon = horizon
@@ -295,6 +346,18 @@ class Planner(Controller):
             raise ValueError(f"states shape {states.shape} != (B, S) = (B >= 1, {S})")
         return states
 
+    def _note_planner_value(self, eng, position, K: int) -> None:
+        """``last_terminal_value``'s source: the engine keeps its LAST iteration's values, so the winner's is
+        there when its position ``iteration * K + candidate`` (batched: per environment) lies in that iteration."""
+        pos = np.asarray(position, dtype=np.int64)
+        last = (self.iterations - 1) * K
+        if (pos < last).any():
+            self._note_terminal_value(eng, None)
+        elif pos.ndim == 0:
+            self._note_terminal_value(eng, np.int64(pos - last))
+        else:
+            self._note_terminal_value(eng, pos - last + np.arange(pos.shape[0], dtype=np.int64) * K)
+
     def _next_seed(self) -> int:
         return int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
 
@@ -321,6 +384,9 @@ class Planner(Controller):
             eng.set_cost_terms(terms)
         if reward:
             eng.set_discount(float(self.gamma))
+        if reward and self.terminal_value is not None:
+            raise ValueError(f"{self._KIND}controller: terminal_value over a learned-reward dyn_model is not covered")
+        self._apply_terminal_value(eng)
         return eng
 
     def _engine_for(self, spec, S, A, k_local, terms=None) -> RolloutEngine:
@@ -378,8 +444,10 @@ class Planner(Controller):
         return self._solve_batch(eng, states, mu0, sd0, seed, K)
 
 
-class MPCcontroller(Controller):
-    """Random-shooting MPC (controllers.py:26-88) on the MI355X rollout engine."""
+class MPCcontroller(_TerminalValue, Controller):
+    """Random-shooting MPC (controllers.py:26-88) on the MI355X rollout engine.  ``terminal_value`` (a container
+    ``value.extract`` reads) and ``terminal_weight`` add ``weight * V(s_H)`` to every candidate's cost on the
+    device (value.py); with it ``rng="numpy"`` draws on the host and uploads the array."""
 
     def __init__(self,
                  env,
@@ -392,7 +460,10 @@ class MPCcontroller(Controller):
                  rng: str = "numpy",
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
-                 process_group=None):
+                 process_group=None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
+        self._init_terminal_value(terminal_value, terminal_weight)
         self.env = env
         self.dyn_model = dyn_model
         self.horizon = horizon
@@ -432,7 +503,11 @@ class MPCcontroller(Controller):
     def _engine_for(self, spec, S, A, k_local, fused, terms=None) -> RolloutEngine:
         self._engine = self._cached("single", spec, S, A, k_local,
                                     "cheetah" if fused else "terms" if terms is not None else "none", terms)
-        return _attach_comm(self, self._engine, fused)
+        # (a value engine exchanges no records inside the library: the ranks agree through the torch all-gather)
+        eng = _attach_comm(self, self._engine, fused and self.terminal_value is None)
+        if fused or terms is not None:
+            self._apply_terminal_value(eng)
+        return eng
 
     def _next_seed(self) -> int:
         src = self._seed_rng if self._seed_rng is not None else np.random
@@ -450,6 +525,7 @@ class MPCcontroller(Controller):
             # were all made by that call, so only the NumPy-stream launch remains
             if (fp[0] == (self.env, self.dyn_model, self.cost_fn, self.horizon, self.num_simulated_paths, self.rng,
                           self.keep_costs) and _weights.same_token(self.dyn_model, fp[1])
+                    and self.terminal_value is None
                     and "sample_random_actions" not in self.__dict__ and _dist.world(self._group)[1] == 1):
                 space = self.env.action_space
                 res = fp[2].get_action_numpy_stream(state, space.low, space.high, fp[3])
@@ -470,6 +546,9 @@ class MPCcontroller(Controller):
         terms = _device_terms(self.cost_fn, S, A)          # a TermCost is scored on the device, either rng
         if not fused and terms is None and self.rng != "numpy":
             raise ValueError("a non-cheetah cost_fn needs rng='numpy' (actions must exist on the host)")
+        if self.terminal_value is not None and not fused and terms is None:
+            raise ValueError("terminal_value needs a cost the device scores (the cheetah cost_fn or a TermCost): "
+                             "a host cost callable cannot be combined with it on the device")
 
         if K == 0:                                          # (the reference draws before failing)
             if self.rng == "numpy":
@@ -479,7 +558,7 @@ class MPCcontroller(Controller):
             raise ValueError("attempt to get argmin of an empty sequence")
         # the reference's draw, made by the library straight into pinned memory and uploaded step
         # by step (same values, same stream advance) unless sample_random_actions is overridden
-        if self.rng == "numpy" and fused and hi > lo and _stock_sampler(self):
+        if self.rng == "numpy" and fused and hi > lo and _stock_sampler(self) and self.terminal_value is None:
             eng = self._engine_for(spec, S, A, hi - lo, fused)
             eng.set_weights(spec, norm, version)
             res = eng.get_action_numpy_stream(state, self.env.action_space.low, self.env.action_space.high, K, lo,
@@ -510,6 +589,7 @@ class MPCcontroller(Controller):
                 res = eng.get_action(state, local, seed=seed, cand_offset=lo, return_costs=self.keep_costs)
                 valid, cost, index, first = True, res.best_cost, res.best_index, res.first_action
                 self.last_costs = res.costs
+                self._note_terminal_value(eng, np.int64(res.best_index - lo))
             else:
                 costs = self._trajectory_costs(eng, state, local)
                 i = int(np.argmin(costs))
@@ -518,6 +598,8 @@ class MPCcontroller(Controller):
 
         cost, index, first_g = _minloc(self, self._engine if valid else None, valid, cost, index, first, A)
         self.last_cost, self.last_index = cost, index
+        if not (valid and lo <= index < hi):
+            self._tv_last = None                            # (another rank's candidate won)
         if action_paths is not None:
             opt_action_path = action_paths[:, index, :]     # controllers.py:84-85
             return opt_action_path[0].copy()
@@ -548,8 +630,10 @@ class MPCcontroller(Controller):
         self._batch_engine = eng = self._cached("batch", spec, S, A, states.shape[0] * K,
                                                 "cheetah" if terms is None else "terms", terms)
         eng.set_weights(spec, norm, version)
+        self._apply_terminal_value(eng)
         res = eng.get_actions(states, None, seed=seed, return_costs=self.keep_costs)
         self.last_costs, self.last_cost, self.last_index = res.costs, res.best_cost, res.best_index
+        self._note_terminal_value(eng, np.asarray(res.best_index, dtype=np.int64))
         return res.first_action
 
     def _trajectory_costs(self, eng: RolloutEngine, state, local_actions) -> np.ndarray:
@@ -626,7 +710,10 @@ class MPCcontrollerPolicyNet(Controller):
                  *,
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
-                 process_group=None):
+                 process_group=None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
+        _refuse_terminal_value('MPCcontrollerPolicyNet', terminal_value)
         self.env = env
         self.dyn_model = dyn_model
         self.policy_net = policy_net
@@ -773,7 +860,10 @@ class MPCcontrollerReward(Controller):
                  rng: str = "env",
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
-                 process_group=None):
+                 process_group=None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
+        _refuse_terminal_value('MPCcontrollerReward', terminal_value)
         self.env = env
         self.dyn_model = dyn_model
         self.horizon = horizon
@@ -930,7 +1020,10 @@ class MCTScontrollerPolicyNetReward(Controller):
                  random_first_stage_action=False,
                  *,
                  seed: Optional[int] = None,
-                 device: Optional[int] = None):
+                 device: Optional[int] = None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
+        _refuse_terminal_value('MCTScontrollerPolicyNetReward', terminal_value)
         self.env = env
         self.dyn_model = dyn_model
         self.policy_net = policy_net

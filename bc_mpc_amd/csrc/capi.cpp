@@ -539,7 +539,8 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
-                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_tc_traj})
+                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_tc_traj,
+                    (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues})
         if (p) (void)hipFree(p);
     if (e->h_bresults) (void)hipHostFree(e->h_bresults);
     if (e->h_result) (void)hipHostFree(e->h_result);
@@ -984,6 +985,150 @@ int bcmpc_trajectory_cost_async(bcmpc_engine* e, const double* d_traj, const dou
                             (hipStream_t)stream);
 }
 
+int bcmpc_terminal_value_supported(const bcmpc_config* cfg) {
+    if (!cfg) return fail(BCMPC_ERR_ARG, "null argument");
+    if (cfg->policy_hidden > 0)
+        return fail(BCMPC_ERR_UNSUPPORTED, "terminal value: engines with a fused policy are not covered");
+    if (cfg->model == BCMPC_MODEL_REWARD || cfg->cost == BCMPC_COST_REWARD)
+        return fail(BCMPC_ERR_UNSUPPORTED, "terminal value: the reward model / BCMPC_COST_REWARD is not covered");
+    if (cfg->cost == BCMPC_COST_NONE)
+        return fail(BCMPC_ERR_UNSUPPORTED, "terminal value: a BCMPC_COST_NONE engine has no cost vector to add it to");
+    return BCMPC_OK;
+}
+
+int bcmpc_set_terminal_value(bcmpc_engine* e, const bcmpc_value_net* v, double weight, uint64_t version) {
+    // the net first, then the engine: every check before any HIP call
+    if (v) {
+        if (!v->kernels || !v->biases || !v->ob_mean || !v->ob_std) return fail(BCMPC_ERR_ARG, "value net: null argument");
+        if (v->n_layers < 1 || v->n_layers > BCMPC_VALUE_MAX_LAYERS)
+            return fail(BCMPC_ERR_ARG, "value net: n_layers must be in [1, 4]");
+        if (v->hidden < 1 || v->hidden > BCMPC_VALUE_MAX_HIDDEN)
+            return fail(BCMPC_ERR_ARG, "value net: hidden must be in [1, 256]");
+        if (v->state_dim < 1 || v->state_dim > BCMPC_MAX_STATE)
+            return fail(BCMPC_ERR_ARG, "value net: state_dim must be in [1, 32]");
+        if (v->reserved != 0) return fail(BCMPC_ERR_ARG, "value net: reserved must be zero");
+        if (!std::isfinite(weight)) return fail(BCMPC_ERR_ARG, "terminal value: weight must be finite");
+        for (int l = 0; l <= v->n_layers; ++l) {
+            if (!v->kernels[l] || !v->biases[l]) return fail(BCMPC_ERR_ARG, "value net: null argument");
+            const int in = l == 0 ? v->state_dim : v->hidden, out = l == v->n_layers ? 1 : v->hidden;
+            for (int i = 0; i < in * out; ++i)
+                if (!std::isfinite(v->kernels[l][i])) return fail(BCMPC_ERR_ARG, "value net: a kernel entry is not finite");
+            for (int i = 0; i < out; ++i)
+                if (!std::isfinite(v->biases[l][i])) return fail(BCMPC_ERR_ARG, "value net: a bias entry is not finite");
+        }
+        for (int i = 0; i < v->state_dim; ++i) {
+            if (!std::isfinite(v->ob_mean[i])) return fail(BCMPC_ERR_ARG, "value net: ob_mean must be finite");
+            if (!std::isfinite(v->ob_std[i]) || !(v->ob_std[i] > 0.f))
+                return fail(BCMPC_ERR_ARG, "value net: ob_std must be finite and > 0");
+        }
+    }
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!v) {
+        e->has_value = false;
+        e->value_version = 0;
+        if (e->fb) return bcmpc_set_terminal_value(e->fb, nullptr, 0.0, 0);
+        return BCMPC_OK;
+    }
+    const bcmpc_config& c = e->cfg;
+    if (const int rc = bcmpc_terminal_value_supported(&c)) return rc;
+    if (e->comm)
+        return fail(BCMPC_ERR_UNSUPPORTED, "terminal value: engines with a communicator attached do not exchange "
+                                           "records inside the library yet");
+    if (e->has_value && e->value_version == version) {
+        e->tv.weight = weight;
+        if (e->fb) return bcmpc_set_terminal_value(e->fb, v, weight, version);
+        return BCMPC_OK;
+    }
+    // (S is the net's: a net over another state_dim runs through bcmpc_terminal_value_async alone; the rollout
+    //  entries refuse it, rollout_impl)
+    const int L = v->n_layers, h = v->hidden, S = v->state_dim;
+    const int HP = terminal_value_padded(h), T = HP / 16, TB = std::min(T, 4);
+    // packed kernels: [2 -> T] [T -> T] x (L - 1) [T -> 1], 256 floats per fragment
+    size_t off[BCMPC_VALUE_MAX_LAYERS + 2];
+    off[0] = 0;
+    off[1] = (size_t)2 * T * 256;
+    for (int l = 1; l < L; ++l) off[l + 1] = off[l] + (size_t)T * T * 256;
+    off[L + 1] = off[L] + (size_t)T * 256;
+    std::vector<float> hw(off[L + 1]), hp((size_t)kTvParamFloats, 0.f);
+    pack_layer(v->kernels[0], S, h, 2, T, TB, hw.data() + off[0]);
+    for (int l = 1; l < L; ++l) pack_layer(v->kernels[l], h, h, T, T, TB, hw.data() + off[l]);
+    pack_layer(v->kernels[L], h, 1, T, 1, 1, hw.data() + off[L]);
+    for (int i = 0; i < S; ++i) {
+        hp[i] = v->ob_mean[i];
+        hp[32 + i] = v->ob_std[i];
+    }
+    for (int i = S; i < 32; ++i) hp[32 + i] = 1.f;
+    for (int l = 0; l < L; ++l) std::copy(v->biases[l], v->biases[l] + h, hp.begin() + 64 + (size_t)l * HP);
+    hp[64 + (size_t)L * HP] = v->biases[L][0];
+    HIP_TRY(hipSetDevice(c.device));
+    constexpr size_t kMaxW = (size_t)(2 * 16 + (BCMPC_VALUE_MAX_LAYERS - 1) * 16 * 16 + 16) * 256;
+    if (!e->d_vw) HIP_TRY(hipMalloc(&e->d_vw, kMaxW * sizeof(float)));
+    if (!e->d_vparams) HIP_TRY(hipMalloc(&e->d_vparams, (size_t)kTvParamFloats * sizeof(float)));
+    if (!e->d_vvalues)
+        HIP_TRY(hipMalloc(&e->d_vvalues, (size_t)std::max<int64_t>(1, c.num_paths) * sizeof(float)));
+    if (!e->d_tc_traj)
+        HIP_TRY(hipMalloc(&e->d_tc_traj, (size_t)(c.horizon + 1) * (size_t)std::max<int64_t>(1, c.num_paths) *
+                                             c.state_dim * sizeof(double)));
+    // (launches of the previous net on any stream of this device have to be over before its weights change)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(e->d_vw, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_vparams, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
+    TerminalValueArgs a{};
+    for (int l = 0; l <= L; ++l)
+        a.w[l] = reinterpret_cast<const float __attribute__((ext_vector_type(4)))*>(e->d_vw + off[l]);
+    a.params = e->d_vparams;
+    a.weight = weight;
+    a.S = S; a.L = L; a.HP = HP;
+    e->tv = a;
+    e->has_value = true;
+    e->value_version = version;
+    auto& hc = e->hv_copy;
+    hc.k.clear(); hc.b.clear();
+    for (int l = 0; l <= L; ++l) {
+        const int in = l == 0 ? S : h, out = l == L ? 1 : h;
+        hc.k.emplace_back(v->kernels[l], v->kernels[l] + (size_t)in * out);
+        hc.b.emplace_back(v->biases[l], v->biases[l] + out);
+    }
+    hc.mean.assign(v->ob_mean, v->ob_mean + S);
+    hc.std.assign(v->ob_std, v->ob_std + S);
+    hc.L = L; hc.hidden = h;
+    if (e->fb) return bcmpc_set_terminal_value(e->fb, v, weight, version);
+    return BCMPC_OK;
+}
+
+// one terminal-value launch on st: the engine's template plus this launch's rows and outputs
+static int terminal_value_launch(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
+                                 float* d_values, double* d_costs, hipStream_t st) {
+    TerminalValueArgs a = e->tv;
+    a.states = d_states; a.row_stride = row_stride; a.K = K;
+    a.values = d_values; a.costs = d_costs;
+    HIP_TRY(launch_terminal_value(a, st));
+    return BCMPC_OK;
+}
+
+int bcmpc_terminal_value_async(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
+                               float* d_values, double* d_costs_inout, void* stream) {
+    if (!e || !d_states) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!d_values && !d_costs_inout) return fail(BCMPC_ERR_ARG, "terminal_value needs d_values or d_costs_inout");
+    if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
+    if (!e->has_value) return fail(BCMPC_ERR_STATE, "bcmpc_set_terminal_value has not been called");
+    if (row_stride < e->tv.S) return fail(BCMPC_ERR_ARG, "row_stride must be >= the value net's state_dim");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return terminal_value_launch(e, d_states, row_stride, K, d_values, d_costs_inout, (hipStream_t)stream);
+}
+
+int bcmpc_last_terminal_values(bcmpc_engine* e, const int64_t* idx, int32_t n, float* out) {
+    if (!e || !idx || !out || n < 1) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!e->has_value || !e->d_vvalues) return fail(BCMPC_ERR_STATE, "bcmpc_set_terminal_value has not been called");
+    for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= e->cfg.num_paths) return fail(BCMPC_ERR_ARG, "candidate index outside [0, num_paths)");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < n; ++i)
+        HIP_TRY(hipMemcpy(out + i, e->d_vvalues + idx[i], sizeof(float), hipMemcpyDeviceToHost));
+    return BCMPC_OK;
+}
+
 int bcmpc_set_action_bounds(bcmpc_engine* e, const double* low, const double* high) {
     if (!e || !low || !high) return fail(BCMPC_ERR_ARG, "null argument");
     for (int j = 0; j < e->cfg.action_dim; ++j) {
@@ -1113,6 +1258,16 @@ int team_fallback(bcmpc_engine* e, bool collective) {
     if (e->has_terms) {                              // (the same shape: the launch template carries over)
         f->tc = e->tc;
         f->has_terms = true;
+    }
+    if (e->has_value && (!f->has_value || f->value_version != e->value_version || f->tv.weight != e->tv.weight)) {
+        const auto& hc = e->hv_copy;
+        std::vector<const float*> k, b;
+        for (auto& v : hc.k) k.push_back(v.data());
+        for (auto& v : hc.b) b.push_back(v.data());
+        const bcmpc_value_net vn{k.data(), b.data(), hc.mean.data(), hc.std.data(), hc.L, hc.hidden, e->tv.S, 0};
+        if (const int rc = bcmpc_set_terminal_value(f, &vn, e->tv.weight, e->value_version)) return rc;
+    } else if (!e->has_value && f->has_value) {
+        if (const int rc = bcmpc_set_terminal_value(f, nullptr, 0.0, 0)) return rc;
     }
     double lo[BCMPC_MAX_ACTION], hi[BCMPC_MAX_ACTION];
     for (int j = 0; j < e->cfg.action_dim; ++j) {
@@ -1316,7 +1471,16 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     // or the scratch), term_cost_kernel turns it into d_costs, and the ordinary argmin launch follows
     const bool terms = c.cost == BCMPC_COST_TERMS;
     if (terms && !e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
-    if (terms) d_traj = d_traj ? d_traj : e->d_tc_traj;
+    // terminal value: the rollout also writes the trajectory (beside its fused cost), terminal_value_kernel adds
+    // weight * V(traj[H][k]) to d_costs[k], and the ordinary argmin launch follows -- no fused argmin tail
+    const bool value = e->has_value;
+    if (value && e->comm)
+        return fail(BCMPC_ERR_UNSUPPORTED, "engines with a terminal value do not exchange records inside the library yet");
+    if (value && !d_costs) return fail(BCMPC_ERR_ARG, "the terminal value needs a costs buffer");
+    if (value && e->tv.S != c.state_dim)
+        return fail(BCMPC_ERR_ARG, "the value net reads " + std::to_string(e->tv.S) + " state dims, the engine has " +
+                                       std::to_string(c.state_dim));
+    if (terms || value) d_traj = d_traj ? d_traj : e->d_tc_traj;
     RolloutArgs a{};
     for (int l = 0; l < e->nwl; ++l) {
         const size_t end = l + 1 < e->nwl ? e->w_off[l + 1] : e->w_floats;
@@ -1390,7 +1554,7 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
         const char* v = std::getenv("BCMPC_TEAM_FUSED_ARGMIN");
         return !(v && v[0] == '0');
     }();
-    const bool fused = d_result && !cem && !terms &&
+    const bool fused = d_result && !cem && !terms && !value &&
                        (e->kernel == BCMPC_KERNEL_TEAM ? team_fused
                                                        : e->split && fa && fa[0] == '1');
     if (fused) {
@@ -1454,6 +1618,10 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     if (terms)
         if (const int rc = term_cost_launch(e, d_traj, d_actions, seed, cand_offset, cem ? cem->mu : nullptr,
                                             cem ? cem->sigma : nullptr, cem ? cem->iter : 0, c.num_paths, d_costs, st))
+            return rc;
+    if (value)
+        if (const int rc = terminal_value_launch(e, d_traj + (size_t)c.horizon * (size_t)c.num_paths * c.state_dim,
+                                                 c.state_dim, c.num_paths, e->d_vvalues, d_costs, st))
             return rc;
     if (record_events) HIP_TRY(hipEventRecord(e->ev[1], st));
     if (d_result && (!fused || team_skipped)) HIP_TRY(launch_argmin(m, st));
@@ -1668,6 +1836,8 @@ int bcmpc_engine_set_comm(bcmpc_engine* e, bcmpc_comm* comm) {
         return fail(BCMPC_ERR_ARG, "the exchange needs the fused objective (argmin records)");
     if (comm && e->cfg.cost == BCMPC_COST_TERMS)
         return fail(BCMPC_ERR_UNSUPPORTED, "cost-term engines do not exchange records inside the library yet");
+    if (comm && e->has_value)
+        return fail(BCMPC_ERR_UNSUPPORTED, "engines with a terminal value do not exchange records inside the library yet");
     e->comm = comm;
     return BCMPC_OK;
 }
@@ -1724,7 +1894,8 @@ int bcmpc_engine_layout(const bcmpc_engine* e, char* buf, int32_t cap) {
             else
                 std::snprintf(s, sizeof(s), "rollout_x3<%d,NC=%d,NW=%d> %s", e->HP, e->nc, e->nw, prec);
     }
-    std::snprintf(buf, (size_t)cap, "%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "");
+    std::snprintf(buf, (size_t)cap, "%s%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "",
+                  e->has_value ? "+value" : "");
     return BCMPC_OK;
 }
 

@@ -194,6 +194,20 @@ struct bcmpc_engine {
     TermCostArgs tc{};
     bool has_terms = false;
     double* d_tc_traj = nullptr;
+    // terminal value (terminal_value.hip): the launch template bcmpc_set_terminal_value builds.  The packed
+    // kernels and the parameter block are allocated once at their largest size (a captured graph keeps the
+    // addresses over a change of net); d_tc_traj, above, is allocated on first use for engines without terms
+    TerminalValueArgs tv{};
+    bool has_value = false;
+    uint64_t value_version = 0;
+    float* d_vw = nullptr;
+    float* d_vparams = nullptr;
+    float* d_vvalues = nullptr;         // [num_paths] the last launch chain's values (bcmpc_last_terminal_values)
+    struct HostValue {                  // the last net, copied (the fallback engine is set from it)
+        std::vector<std::vector<float>> k, b;
+        std::vector<float> mean, std;
+        int L = 0, hidden = 0;
+    } hv_copy;
     // team kernel: a team that could not meet (its workgroups not all resident: another process or
     // kernel holding CUs for ~1 s) makes a synchronous call rerun on this fallback engine -- the same
     // net on the split slab kernel, or the fp32 group kernel where only the team kernel takes the net

@@ -302,6 +302,24 @@ struct EnsembleReduceArgs {
 };
 hipError_t launch_ensemble_reduce(const EnsembleReduceArgs& a, hipStream_t st);
 
+// ---- terminal value (terminal_value.hip): values[k] = V(states[k]), costs[k] += weight * values[k] ----
+// params: [32] ob_mean, [32] ob_std, [L][HP] hidden biases, [16] final bias (row 0), all zero-padded.
+// w[l]: pack_layer(kernel l, Tin, Tout, TB) with Tin = 2 (layer 0) or HP / 16, Tout = HP / 16 and
+// TB = min(4, Tout) for the hidden layers, Tout = TB = 1 for the final one.
+constexpr int kTvParamFloats = 64 + BCMPC_VALUE_MAX_LAYERS * BCMPC_VALUE_MAX_HIDDEN + 16;
+struct TerminalValueArgs {
+    const float __attribute__((ext_vector_type(4)))* w[BCMPC_VALUE_MAX_LAYERS + 1];
+    const float* params;
+    const double* states;                    // row k: S doubles at states + k * row_stride
+    int64_t row_stride, K;
+    float* values;                           // [K] or nullptr
+    double* costs;                           // [K] in / out, or nullptr
+    double weight;
+    int32_t S, L, HP;                        // HP: terminal_value_padded(hidden)
+};
+int terminal_value_padded(int hidden);       // 16, 32, 64, 128 or 256 (-1: outside [1, 256])
+hipError_t launch_terminal_value(const TerminalValueArgs& a, hipStream_t st);
+
 hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);
 hipError_t launch_argmin_segments(const SegmentArgminArgs& a, hipStream_t st);
 

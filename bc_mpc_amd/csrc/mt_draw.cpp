@@ -388,6 +388,9 @@ int bcmpc_get_action_mt19937(bcmpc_engine* e, const double* state, uint32_t* mt_
     if (c.cost == BCMPC_COST_TERMS)
         return fail(BCMPC_ERR_UNSUPPORTED, "the NumPy-stream draw does not cover cost-term engines: draw on the host "
                                            "and pass the array to bcmpc_get_action");
+    if (e->has_value)
+        return fail(BCMPC_ERR_UNSUPPORTED, "the NumPy-stream draw does not cover engines with a terminal value: draw on "
+                                           "the host and pass the array to bcmpc_get_action");
     if (k_global < c.num_paths || cand_offset < 0 || cand_offset + c.num_paths > k_global)
         return fail(BCMPC_ERR_ARG, "this engine's candidates must lie inside [0, k_global)");
     if (*mt_pos < 0 || *mt_pos > 624) return fail(BCMPC_ERR_ARG, "MT19937 position out of range");

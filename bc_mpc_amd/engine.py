@@ -206,6 +206,7 @@ class _EngineCalls:
         self._mt_fast = None        # get_action_numpy_stream's prepared ctypes arguments
         self._ga_fast = None        # get_action's (device actions, no cost vector) prepared ctypes arguments
         self.cost_terms = None      # the TermCost of a cost="terms" engine (set_cost_terms)
+        self._value = None          # the terminal value the library holds (set_terminal_value)
 
     def _state(self, state) -> np.ndarray:
         st = _f64(state).reshape(-1)
@@ -441,6 +442,65 @@ class RolloutEngine(_EngineCalls):
             self._h, vp(d_traj), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
             vp(d_mu), vp(d_sigma), ctypes.c_int32(cem_iter), ctypes.c_int64(K), vp(d_costs),
             ctypes.c_void_p(stream)))
+
+    def set_terminal_value(self, spec, weight: float = -1.0, version: int = 0) -> None:
+        """The engine's terminal value (bcmpc_set_terminal_value): from now on every rollout entry scores a
+        candidate by ``cost + weight * float64(V(s_H))`` (``value.terminal_values`` is the definition).
+        ``spec``: a ``value.ValueSpec``, or None to remove it.  Idempotent: with the same ``version`` only
+        ``weight`` is passed on (no validation, packing or upload), with the same weight too nothing is."""
+        if spec is None:
+            if self._value is not None:
+                _lib.check(self._lib.bcmpc_set_terminal_value(self._h, None, ctypes.c_double(0.0), ctypes.c_uint64(0)))
+                self._value = None
+            return
+        from .value import ValueSpec, check_weight
+        weight = check_weight(weight)
+        held = self._value
+        if held is not None and held[0] == version:
+            if held[1] != weight:
+                _lib.check(self._lib.bcmpc_set_terminal_value(self._h, ctypes.byref(held[2]), ctypes.c_double(weight),
+                                                              ctypes.c_uint64(version & (2**64 - 1))))
+                self._value = (version, weight) + held[2:]
+            return
+        if not isinstance(spec, ValueSpec):
+            raise ValueError("set_terminal_value takes a bc_mpc_amd.value.ValueSpec (or None)")
+        FP = ctypes.POINTER(ctypes.c_float)
+        ks, bs = list(spec.kernels), list(spec.biases)
+        karr = (FP * len(ks))(*[k.ctypes.data_as(FP) for k in ks])
+        barr = (FP * len(bs))(*[b.ctypes.data_as(FP) for b in bs])
+        v = _lib.ValueNet(karr, barr, spec.ob_mean.ctypes.data_as(FP), spec.ob_std.ctypes.data_as(FP),
+                          spec.n_layers, spec.hidden, spec.state_dim, 0)
+        _lib.check(self._lib.bcmpc_set_terminal_value(self._h, ctypes.byref(v), ctypes.c_double(weight),
+                                                      ctypes.c_uint64(version & (2**64 - 1))))
+        self._value = (version, weight, v, spec, karr, barr)     # the struct's pointers stay valid while held here
+
+    @property
+    def terminal_value(self):
+        """(spec, weight, version) of the value set, or None."""
+        return None if self._value is None else (self._value[3], self._value[1], self._value[0])
+
+    def terminal_value_async(self, d_states: int, K: int, d_values: Optional[int] = None,
+                             d_costs: Optional[int] = None, row_stride: Optional[int] = None,
+                             stream: Optional[int] = None) -> None:
+        """The value kernel alone on device pointers (bcmpc_terminal_value_async), stream-ordered: row k of
+        ``d_states`` (the net's ``state_dim`` f64 at ``k * row_stride``, default dense) -> ``d_values[k]`` f32
+        and / or ``d_costs[k] += weight * float64(v_k)`` in place.  ``K`` need not equal ``num_paths``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_terminal_value_async(
+            self._h, vp(d_states), ctypes.c_int64((self._value[3].state_dim if self._value else self.state_dim)
+                                    if row_stride is None else row_stride),
+            ctypes.c_int64(K), vp(d_values), vp(d_costs), ctypes.c_void_p(stream)))
+
+    def last_terminal_values(self, local_indices) -> np.ndarray:
+        """f32 values of the local candidates ``local_indices`` from the engine's last launch chain
+        (bcmpc_last_terminal_values; a CEM / MPPI call: its last iteration).  Diagnostics: one small copy."""
+        idx = np.ascontiguousarray(np.asarray(local_indices, dtype=np.int64).reshape(-1))
+        out = np.empty(idx.shape[0], dtype=np.float32)
+        _lib.check(self._lib.bcmpc_last_terminal_values(
+            self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.c_int32(idx.shape[0]),
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
 
     def set_action_bounds(self, low, high) -> None:
         lo, hi = _f64(low), _f64(high)

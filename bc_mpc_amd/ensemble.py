@@ -147,6 +147,17 @@ class EnsembleEngine(_EngineCalls):
         for m in self.members:
             m.set_action_bounds(low, high)
 
+    def set_terminal_value(self, spec, weight: float = -1.0, version: int = 0) -> None:
+        """RolloutEngine.set_terminal_value on every member: each adds the value of ITS final state to its row
+        of the member costs before the reduce."""
+        for m in self.members:
+            m.set_terminal_value(spec, weight, version)
+
+    @property
+    def terminal_value(self):
+        """(spec, weight, version) of the value the members hold, or None."""
+        return self.members[0].terminal_value
+
     def set_rule(self, rule: str = "mean", kappa: float = 0.0) -> None:
         """The rule of the following calls (bcmpc_ensemble_set_rule); see ``combine``."""
         if rule not in _lib.ENSEMBLE_RULES:
@@ -376,6 +387,7 @@ def _ctrl_engine(ctrl, S: int, A: int, k_total: int, slot: str) -> EnsembleEngin
     for i, (s, norm, version) in enumerate(specs):
         eng.set_weights(i, s, norm, version)
     eng.set_rule(model.rule, model.kappa)
+    ctrl._apply_terminal_value(eng)
     return eng
 
 
@@ -417,6 +429,7 @@ def mpc_get_action(ctrl, state):
     ctrl.last_costs = res.costs if ctrl.keep_costs else None
     ctrl.last_cost, ctrl.last_index = res.best_cost, res.best_index
     _diagnose(ctrl, res.member_costs, res.best_index)
+    ctrl._note_terminal_value(eng, np.int64(res.best_index))
     if action_paths is not None:
         return action_paths[:, res.best_index, :][0].copy()
     return res.first_action
@@ -437,4 +450,5 @@ def mpc_get_actions(ctrl, states):
     ctrl.last_costs = res.costs if ctrl.keep_costs else None
     ctrl.last_cost, ctrl.last_index = res.best_cost, res.best_index
     _diagnose(ctrl, res.member_costs, res.best_index - np.arange(B) * K)
+    ctrl._note_terminal_value(eng, np.asarray(res.best_index, dtype=np.int64))
     return res.first_action

@@ -53,9 +53,12 @@ class MPPIcontroller(Planner):
                  warm_start: bool = True,
                  seed: Optional[int] = None,
                  device: Optional[int] = None,
-                 process_group=None):
+                 process_group=None,
+                 terminal_value=None,
+                 terminal_weight: float = -1.0):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
-                         warm_start, 0x3B9AC1 if seed is None else seed, device, process_group)
+                         warm_start, 0x3B9AC1 if seed is None else seed, device, process_group,
+                         terminal_value=terminal_value, terminal_weight=terminal_weight)
         if not (math.isfinite(temperature) and temperature > 0):
             raise ValueError("temperature must be finite and > 0")
         self.temperature = float(temperature)
@@ -68,6 +71,7 @@ class MPPIcontroller(Planner):
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
         res, mu, stats = eng.mppi_get_action(state, mu0, sd0, self.iterations, self.temperature, seed)
+        self._note_planner_value(eng, res.best_index, K)
         self._mu = mu
         self.last_mu = mu
         self.last_cost, self.last_position = res.best_cost, res.best_index
@@ -76,6 +80,7 @@ class MPPIcontroller(Planner):
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, stats = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed)
+        self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu = mu
         self.last_cost, self.last_position = res.best_cost, res.best_index

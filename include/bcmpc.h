@@ -276,6 +276,61 @@ int bcmpc_trajectory_cost_async(bcmpc_engine* eng, const double* d_traj, const d
                                 int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
                                 int64_t K, double* d_costs, void* stream);
 
+/* ---- Terminal value: total[k] = cost[k] + weight * (double)V(s_H[k]) ------------------------------------
+ * V is the critic the reference trains beside its policy (ppo_bc_policy.py:56-64, scope pi/vf) over the
+ * policy's obfilter:  obz = clip((f32(s) - ob_mean) / ob_std, -5, 5);  h = tanh(h W + b) per hidden layer;
+ * v = h w_final + b_final, all f32 (definition: bc_mpc_amd/value.py terminal_values).  total is one rounded
+ * f64 multiply and one rounded f64 add.  The argmin, CEM's elite selection, the MPPI weights and the ensemble
+ * rules then run on total with the rules they have on cost (a NaN total wins the argmin).  Additive to ABI 5:
+ * callers detect the feature by the symbol bcmpc_set_terminal_value. */
+#define BCMPC_VALUE_MAX_LAYERS 4     /* hidden layers of a value net */
+#define BCMPC_VALUE_MAX_HIDDEN 256   /* ... and their width          */
+typedef struct bcmpc_value_net {
+    const float* const* kernels;   /* n_layers+1 arrays [in,out] row-major (pi/vf/fc1.., final [hidden,1]) */
+    const float* const* biases;    /* n_layers+1 arrays of length out                                      */
+    const float* ob_mean;          /* state_dim (RunningMeanStd.mean, f32)                                 */
+    const float* ob_std;           /* state_dim, finite and > 0                                            */
+    int32_t n_layers;              /* hidden layers, 1 .. BCMPC_VALUE_MAX_LAYERS                           */
+    int32_t hidden;                /* their width, 1 .. BCMPC_VALUE_MAX_HIDDEN                             */
+    int32_t state_dim;             /* 1 .. 32; the rollout entries need it to equal the engine's           */
+    int32_t reserved;              /* must be zero                                                         */
+} bcmpc_value_net;
+
+/* BCMPC_OK if an engine of this config takes a terminal value, else BCMPC_ERR_UNSUPPORTED with a message:
+ * a fused policy, the reward model / BCMPC_COST_REWARD and BCMPC_COST_NONE do not.  No HIP call. */
+int bcmpc_terminal_value_supported(const bcmpc_config* cfg);
+
+/* Sets (v != NULL) or removes (v == NULL) the engine's terminal value.  Idempotent on `version`: with the
+ * version already set only `weight` is updated; a new version validates, packs the kernels into MFMA fragment
+ * order and uploads them.  The first call also allocates what the launch chain needs -- the trajectory scratch
+ * [H+1][num_paths][S] (a BCMPC_COST_TERMS engine already owns one) -- here, never inside a stream-ordered
+ * entry, so a captured graph keeps its addresses.  From then on every entry built on the rollout launch --
+ * bcmpc_get_action, bcmpc_rollout_async, the batched step, bcmpc_cem_*, bcmpc_mppi_*, the batched planners,
+ * the ensemble entries (each member adds the value of ITS final state to its row before the reduce) -- runs
+ * rollout -> (term cost) -> terminal value into the cost vector -> argmin; the fused argmin tails are off, as
+ * for cost terms.
+ * BCMPC_ERR_ARG (all checked before any HIP call, the net before the engine): v's pointers null, n_layers or
+ * hidden outside their ranges, reserved != 0, a non-finite kernel / bias / ob_mean, ob_std not finite or
+ * <= 0, weight not finite, a null engine.  A net over another state_dim than the engine's is accepted for
+ * bcmpc_terminal_value_async alone: every rollout entry answers it with BCMPC_ERR_ARG.
+ * BCMPC_ERR_UNSUPPORTED: bcmpc_terminal_value_supported's cases; a communicator attached.
+ * bcmpc_get_action_mt19937 refuses an engine with a value (draw with NumPy on the host and pass the actions). */
+int bcmpc_set_terminal_value(bcmpc_engine* eng, const bcmpc_value_net* v, double weight, uint64_t version);
+
+/* The value kernel alone, stream-ordered, allocates nothing:
+ *   d_states      : device rows of the NET's state_dim doubles, row k at d_states + k * row_stride (>= it)
+ *   d_values      : device K floats, or NULL
+ *   d_costs_inout : device K doubles, updated in place: c[k] = c[k] + weight * (double)v[k], or NULL
+ * BCMPC_ERR_ARG: null engine / d_states, both outputs NULL, K < 1, row_stride < the net's state_dim.
+ * BCMPC_ERR_STATE: no value set. */
+int bcmpc_terminal_value_async(bcmpc_engine* eng, const double* d_states, int64_t row_stride, int64_t K,
+                               float* d_values, double* d_costs_inout, void* stream);
+
+/* Diagnostics: v of local candidates idx[0..n) as the engine's LAST launch chain computed them (a CEM / MPPI
+ * call: its last iteration), after a synchronisation of the engine's stream.  BCMPC_ERR_ARG: null pointers,
+ * n < 1, an index outside [0, num_paths).  BCMPC_ERR_STATE: no value set. */
+int bcmpc_last_terminal_values(bcmpc_engine* eng, const int64_t* idx, int32_t n, float* out);
+
 /* env.action_space.low / .high (controllers.py:53). Defaults: [-1, 1]^A. */
 int bcmpc_set_action_bounds(bcmpc_engine* eng, const double* low, const double* high);
 
