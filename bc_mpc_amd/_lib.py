@@ -212,6 +212,16 @@ SIGNATURES = [
       ctypes.c_void_p]),
     ("bcmpc_last_terminal_values", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, _FP]),
+    ("bcmpc_set_termination", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(CostTerm), ctypes.c_int32, ctypes.c_double]),
+    ("bcmpc_trajectory_cost_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_terminal_value_masked_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_last_termination_steps", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("bcmpc_get_action", ctypes.c_int,
      [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
     ("bcmpc_get_actions_batch", ctypes.c_int,

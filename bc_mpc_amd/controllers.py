@@ -207,6 +207,7 @@ class _TerminalValue:
     terminal_value = None
     terminal_weight = -1.0
     _tv_last = None             # (engine, local candidate indices or None) of the last call
+    _ts_last = None             # the same for last_termination_step (a TermCost with done conditions)
 
     def _init_terminal_value(self, terminal_value, terminal_weight) -> None:
         self.terminal_value = terminal_value
@@ -215,7 +216,7 @@ class _TerminalValue:
             _value.extract(terminal_value)          # a container that cannot be read fails here, not mid-episode
 
     def _apply_terminal_value(self, eng) -> None:
-        self._tv_last = None
+        self._tv_last = self._ts_last = None
         if self.terminal_value is None:
             if getattr(eng, "terminal_value", None) is not None:    # (an engine that never held one is not asked)
                 eng.set_terminal_value(None)
@@ -227,6 +228,8 @@ class _TerminalValue:
 
     def _note_terminal_value(self, eng, local_indices) -> None:
         self._tv_last = (eng, local_indices) if self.terminal_value is not None else None
+        terms = getattr(getattr(eng, "members", [eng])[0], "cost_terms", None)
+        self._ts_last = (eng, local_indices) if terms is not None and terms.done_conditions else None
 
     @property
     def last_terminal_value(self):
@@ -241,6 +244,21 @@ class _TerminalValue:
             return np.array([m.last_terminal_values(idx)[0] for m in members], dtype=np.float32)
         v = eng.last_terminal_values(idx)
         return float(v[0]) if np.ndim(idx) == 0 else v
+
+    @property
+    def last_termination_step(self):
+        """Diagnostics: the winner's terminating step ``t`` of the last call (``cost_functions.episode_cost``; the
+        horizon: it never terminated) -- an int, ``[B]`` for ``get_actions``, ``[E]`` (every member on its own
+        trajectory) on an ensemble -- or None: the cost is no ``TermCost`` with ``done`` conditions, or a CEM /
+        MPPI winner from an iteration before the last (the same rule as ``last_terminal_value``)."""
+        if self._ts_last is None or self._ts_last[1] is None:
+            return None
+        eng, idx = self._ts_last
+        members = getattr(eng, "members", None)
+        if members is not None:
+            return np.array([m.last_termination_steps(idx)[0] for m in members], dtype=np.int32)
+        t = eng.last_termination_steps(idx)
+        return int(t[0]) if np.ndim(idx) == 0 else t
 
 
 def _refuse_terminal_value(who: str, terminal_value) -> None:
@@ -599,7 +617,7 @@ class MPCcontroller(_TerminalValue, Controller):
         cost, index, first_g = _minloc(self, self._engine if valid else None, valid, cost, index, first, A)
         self.last_cost, self.last_index = cost, index
         if not (valid and lo <= index < hi):
-            self._tv_last = None                            # (another rank's candidate won)
+            self._tv_last = self._ts_last = None            # (another rank's candidate won)
         if action_paths is not None:
             opt_action_path = action_paths[:, index, :]     # controllers.py:84-85
             return opt_action_path[0].copy()

@@ -108,17 +108,44 @@ def quadratic(index, weight, target=0.0, on="state") -> Term:
     return Term(QUADRATIC, _source(on), index, GE, weight, target)
 
 
+def done_when(index, op, value) -> Term:
+    """A done condition: the episode ends at the step whose NEXT state has ``next_state[index] op value`` (op one
+    of ``>=  >  <=  <``; a NaN compares false).  ``TermCost(terms, done=[...])`` combines its conditions with OR:
+    Hopper's ``not healthy`` is ``done_when(0, "<=", 0.7), done_when(1, ">=", 0.2), done_when(1, "<=", -0.2)``."""
+    if op not in _CMPS:
+        raise ValueError(f"op must be one of {sorted(_CMPS)}, not {op!r}")
+    return Term(THRESHOLD, NEXT_STATE, index, _CMPS[op], 0.0, value)
+
+
 class TermCost:
     """A cost built from terms, with the reference's ``cost_fn(state, action, next_state)`` signature for
     1-D (one transition) and 2-D (a batch, one row each) inputs.  Passed as ``cost_fn`` to MPCcontroller,
     CEMcontroller or MPPIcontroller it is evaluated on the device (``RolloutEngine(cost="terms")``) for any
     state size; called, it evaluates the same expressions in NumPy f64 -- the definition the kernel is
-    tested against.  Minimised; weights may be negative."""
+    tested against.  Minimised; weights may be negative.
 
-    def __init__(self, terms=()):
+    ``done``: conditions built by ``done_when`` that end a candidate's episode, ``done_cost``: a finite cost
+    added once at the terminating step.  Neither changes ``__call__`` (the per-step cost); ``episode_cost`` is the
+    definition of what the planners then minimise.  Terms plus conditions are at most 32."""
+
+    def __init__(self, terms=(), done=(), done_cost=0.0):
         self.terms = tuple(t if isinstance(t, Term) else Term(*t) for t in terms)
+        self.done_conditions = tuple(t if isinstance(t, Term) else Term(*t) for t in done)
+        self.done_cost = float(done_cost)
         if len(self.terms) > MAX_TERMS:
             raise ValueError(f"a TermCost holds at most {MAX_TERMS} terms, got {len(self.terms)}")
+        if len(self.terms) + len(self.done_conditions) > MAX_TERMS:
+            raise ValueError(f"a TermCost holds at most {MAX_TERMS} terms and done conditions together, got "
+                             f"{len(self.terms)} + {len(self.done_conditions)}")
+        if not np.isfinite(self.done_cost):
+            raise ValueError("done_cost must be finite")
+        for i, t in enumerate(self.done_conditions):
+            if t.kind != THRESHOLD or t.source != NEXT_STATE or t.cmp not in (GE, GT, LE, LT):
+                raise ValueError(f"done condition {i}: not a done_when(index, op, value) condition")
+            if t.index < 0:
+                raise ValueError(f"done condition {i}: negative index {t.index}")
+            if not np.isfinite(t.param) or t.weight != 0.0:
+                raise ValueError(f"done condition {i}: the value must be finite (and the weight 0)")
         for i, t in enumerate(self.terms):
             if t.kind not in (THRESHOLD, DIFF, LINEAR, QUADRATIC):
                 raise ValueError(f"term {i}: unknown kind {t.kind}")
@@ -136,7 +163,11 @@ class TermCost:
                 raise ValueError(f"term {i}: a progress term's dt must not be 0")
 
     def key(self):
-        return self.terms
+        """What identifies the cost: the terms alone without ``done`` (as before there was one), else also the
+        conditions and ``done_cost`` (by its bits: -0.0 is not 0.0)."""
+        if not self.done_conditions:
+            return self.terms
+        return (self.terms, self.done_conditions, self.done_cost.hex())
 
     def validate(self, state_dim: int, action_dim: int) -> None:
         """Every index inside the state / the action of this task (the engine checks the same)."""
@@ -144,12 +175,28 @@ class TermCost:
             lim = action_dim if t.source == ACTION else state_dim
             if t.index >= lim:
                 raise ValueError(f"term {i}: index {t.index} outside [0, {lim})")
+        for i, t in enumerate(self.done_conditions):
+            if t.index >= state_dim:
+                raise ValueError(f"done condition {i}: index {t.index} outside [0, {state_dim})")
+
+    def done(self, next_state):
+        """Whether the episode ends on reaching ``next_state`` (``[..., S]`` -> bool ``[...]``): the OR of the
+        conditions, a NaN comparing false; all False without conditions."""
+        ns = np.asarray(next_state, dtype=np.float64)
+        out = np.zeros(ns.shape[:-1], dtype=bool)
+        with np.errstate(invalid="ignore"):
+            for t in self.done_conditions:
+                out = out | _CMP_FN[t.cmp](ns[..., t.index], t.param)
+        return out
 
     def __len__(self):
         return len(self.terms)
 
     def __repr__(self):
-        return f"TermCost({list(map(tuple, self.terms))})"
+        if not self.done_conditions:
+            return f"TermCost({list(map(tuple, self.terms))})"
+        return (f"TermCost({list(map(tuple, self.terms))}, done={list(map(tuple, self.done_conditions))}, "
+                f"done_cost={self.done_cost!r})")
 
     def __call__(self, state, action, next_state):
         s, a, ns = (np.asarray(x, dtype=np.float64) for x in (state, action, next_state))
@@ -167,6 +214,35 @@ class TermCost:
                 d = x - t.param
                 acc = acc + t.weight * (d * d)
         return acc if acc.ndim else float(acc)
+
+
+def episode_cost(term_cost, states, actions, next_states):
+    """THE definition of a ``TermCost`` with ``done`` over a horizon (csrc/term_cost.hip is tested against it bit
+    for bit): ``states`` / ``next_states`` ``[H, K, S]``, ``actions`` ``[H, K, A]`` ->
+    ``(costs [K] f64, term_step [K] int32)``.  For every candidate
+
+        total = 0.0; t = H
+        for h in 0 .. H-1:
+            total = total + c_h                      # the terminating step is still paid, as gym pays it
+            if term_cost.done(next_states[h]):  total = total + done_cost; t = h; break
+
+    each operation one f64 operation in this order.  ``t == H`` exactly where the candidate never terminated.
+    Without conditions this is ``trajectory_cost_fn(term_cost, ...)`` bit for bit and ``t == H`` everywhere."""
+    H = len(actions)
+    shape = np.shape(states)[1:-1]
+    total = np.zeros(shape, dtype=np.float64)
+    step = np.full(shape, H, dtype=np.int32)
+    alive = np.ones(shape, dtype=bool)
+    dc = np.float64(term_cost.done_cost)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for h in range(H):
+            c = term_cost(states[h], actions[h], next_states[h])
+            total = np.where(alive, total + c, total)
+            d = alive & term_cost.done(next_states[h])
+            total = np.where(d, total + dc, total)
+            step = np.where(d, np.int32(h), step).astype(np.int32)
+            alive = alive & ~d
+    return total, step
 
 
 def cheetah_terms() -> TermCost:

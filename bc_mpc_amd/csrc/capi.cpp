@@ -540,7 +540,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
                     (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_tc_traj,
-                    (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues})
+                    (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues, (void*)e->d_tc_steps})
         if (p) (void)hipFree(p);
     if (e->h_bresults) (void)hipHostFree(e->h_bresults);
     if (e->h_result) (void)hipHostFree(e->h_result);
@@ -898,35 +898,36 @@ int bcmpc_first_actions(bcmpc_engine* e, double* out) {
     return BCMPC_OK;
 }
 
-int bcmpc_set_cost_terms(bcmpc_engine* e, const bcmpc_cost_term* terms, int32_t n) {
-    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
-    const bcmpc_config& c = e->cfg;
-    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "cost terms need an engine created with BCMPC_COST_TERMS");
-    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of cost terms must be in [0, 32]");
-    if (n > 0 && !terms) return fail(BCMPC_ERR_ARG, "null argument");
+// one cost term's checks (bcmpc_set_cost_terms; a done condition passes them too, then its own)
+static int check_cost_term(const bcmpc_config& c, const bcmpc_cost_term& T, const std::string& at) {
+    if (T.kind < BCMPC_TERM_THRESHOLD || T.kind > BCMPC_TERM_QUADRATIC) return fail(BCMPC_ERR_ARG, at + "unknown kind");
+    if (T.source < BCMPC_SRC_STATE || T.source > BCMPC_SRC_ACTION) return fail(BCMPC_ERR_ARG, at + "unknown source");
+    if (T.kind == BCMPC_TERM_THRESHOLD && (T.cmp < BCMPC_CMP_GE || T.cmp > BCMPC_CMP_LT))
+        return fail(BCMPC_ERR_ARG, at + "unknown cmp");
+    if (T.kind == BCMPC_TERM_DIFF && T.source != BCMPC_SRC_STATE)
+        return fail(BCMPC_ERR_ARG, at + "a DIFF term's source must be STATE");
+    const int lim = T.source == BCMPC_SRC_ACTION ? c.action_dim : c.state_dim;
+    if (T.index < 0 || T.index >= lim)
+        return fail(BCMPC_ERR_ARG, at + "index " + std::to_string(T.index) + " outside [0, " + std::to_string(lim) + ")");
+    if (!std::isfinite(T.weight) || !std::isfinite(T.param))
+        return fail(BCMPC_ERR_ARG, at + "weight and param must be finite");
+    if (T.kind == BCMPC_TERM_DIFF && T.param == 0.0) return fail(BCMPC_ERR_ARG, at + "a DIFF term's param must not be 0");
+    return BCMPC_OK;
+}
+
+// the launch template of checked cost terms and done conditions (the conditions follow the terms in
+// TermCostArgs::terms).  The slots: every (state dim) the terms and the conditions read, then every (action) --
+// term_cost.hip wants the actions last
+static TermCostArgs digest_terms(const bcmpc_config& c, const std::vector<bcmpc_cost_term>& terms,
+                                 const std::vector<bcmpc_cost_term>& conds, double done_cost) {
     TermCostArgs a{};
-    // the slots: every (state dim) the terms read, then every (action) -- term_cost.hip wants the actions last
+    const int n = (int)terms.size(), nall = n + (int)conds.size();
     int slot_of[2][BCMPC_MAX_STATE];
     for (auto& row : slot_of)
         for (int& v : row) v = -1;
     for (int pass = 0; pass < 2; ++pass)
-        for (int t = 0; t < n; ++t) {
-            const bcmpc_cost_term& T = terms[t];
-            const std::string at = "cost term " + std::to_string(t) + ": ";
-            if (pass == 0) {
-                if (T.kind < BCMPC_TERM_THRESHOLD || T.kind > BCMPC_TERM_QUADRATIC) return fail(BCMPC_ERR_ARG, at + "unknown kind");
-                if (T.source < BCMPC_SRC_STATE || T.source > BCMPC_SRC_ACTION) return fail(BCMPC_ERR_ARG, at + "unknown source");
-                if (T.kind == BCMPC_TERM_THRESHOLD && (T.cmp < BCMPC_CMP_GE || T.cmp > BCMPC_CMP_LT))
-                    return fail(BCMPC_ERR_ARG, at + "unknown cmp");
-                if (T.kind == BCMPC_TERM_DIFF && T.source != BCMPC_SRC_STATE)
-                    return fail(BCMPC_ERR_ARG, at + "a DIFF term's source must be STATE");
-                const int lim = T.source == BCMPC_SRC_ACTION ? c.action_dim : c.state_dim;
-                if (T.index < 0 || T.index >= lim)
-                    return fail(BCMPC_ERR_ARG, at + "index " + std::to_string(T.index) + " outside [0, " + std::to_string(lim) + ")");
-                if (!std::isfinite(T.weight) || !std::isfinite(T.param))
-                    return fail(BCMPC_ERR_ARG, at + "weight and param must be finite");
-                if (T.kind == BCMPC_TERM_DIFF && T.param == 0.0) return fail(BCMPC_ERR_ARG, at + "a DIFF term's param must not be 0");
-            }
+        for (int t = 0; t < nall; ++t) {
+            const bcmpc_cost_term& T = t < n ? terms[t] : conds[t - n];
             const int is_act = T.source == BCMPC_SRC_ACTION ? 1 : 0;
             if (is_act != pass) continue;
             int& sl = slot_of[is_act][T.index];
@@ -948,19 +949,80 @@ int bcmpc_set_cost_terms(bcmpc_engine* e, const bcmpc_cost_term* terms, int32_t 
             }
         }
     a.n_terms = n;
+    a.n_done = (int32_t)conds.size();
+    a.done_cost = done_cost;
     a.H = c.horizon; a.S = c.state_dim; a.A = c.action_dim;
-    e->tc = a;
+    return a;
+}
+
+int bcmpc_set_cost_terms(bcmpc_engine* e, const bcmpc_cost_term* terms, int32_t n) {
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    const bcmpc_config& c = e->cfg;
+    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "cost terms need an engine created with BCMPC_COST_TERMS");
+    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of cost terms must be in [0, 32]");
+    if (n > 0 && !terms) return fail(BCMPC_ERR_ARG, "null argument");
+    for (int t = 0; t < n; ++t)
+        if (const int rc = check_cost_term(c, terms[t], "cost term " + std::to_string(t) + ": ")) return rc;
+    // (every entry adds at most one slot, so the slots fit whenever the entries do)
+    if (n + (int)e->tc_conds.size() > BCMPC_MAX_COST_TERMS)
+        return fail(BCMPC_ERR_ARG, "cost terms plus done conditions must be at most 32 (" + std::to_string(n) + " + " +
+                                       std::to_string(e->tc_conds.size()) + ")");
+    e->tc_terms.assign(terms, terms + n);
+    e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost);
     e->has_terms = true;
     if (e->fb) return bcmpc_set_cost_terms(e->fb, terms, n);
+    return BCMPC_OK;
+}
+
+int bcmpc_set_termination(bcmpc_engine* e, const bcmpc_cost_term* conds, int32_t n, double done_cost) {
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    const bcmpc_config& c = e->cfg;
+    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "termination needs an engine created with BCMPC_COST_TERMS");
+    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of done conditions must be in [0, 32]");
+    if (n > 0 && !conds) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!std::isfinite(done_cost)) return fail(BCMPC_ERR_ARG, "done_cost must be finite");
+    for (int t = 0; t < n; ++t) {
+        const bcmpc_cost_term& T = conds[t];
+        const std::string at = "done condition " + std::to_string(t) + ": ";
+        if (T.kind != BCMPC_TERM_THRESHOLD) return fail(BCMPC_ERR_ARG, at + "the kind must be THRESHOLD");
+        if (T.source != BCMPC_SRC_NEXT_STATE) return fail(BCMPC_ERR_ARG, at + "the source must be NEXT_STATE");
+        if (const int rc = check_cost_term(c, T, at)) return rc;
+        if (T.weight != 0.0) return fail(BCMPC_ERR_ARG, at + "the weight must be 0");
+    }
+    if (n + (int)e->tc_terms.size() > BCMPC_MAX_COST_TERMS)
+        return fail(BCMPC_ERR_ARG, "cost terms plus done conditions must be at most 32 (" +
+                                       std::to_string(e->tc_terms.size()) + " + " + std::to_string(n) + ")");
+    if (n > 0 && !e->d_tc_steps) {
+        HIP_TRY(hipSetDevice(c.device));
+        HIP_TRY(hipMalloc(&e->d_tc_steps, (size_t)std::max<int64_t>(1, c.num_paths) * sizeof(int32_t)));
+    }
+    e->tc_conds.assign(conds, conds + n);
+    e->done_cost = n > 0 ? done_cost : 0.0;
+    e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost);
+    if (e->fb) return bcmpc_set_termination(e->fb, conds, n, done_cost);
+    return BCMPC_OK;
+}
+
+int bcmpc_last_termination_steps(bcmpc_engine* e, const int64_t* idx, int32_t n, int32_t* out) {
+    if (!e || !idx || !out || n < 1) return fail(BCMPC_ERR_ARG, "null argument");
+    if (e->tc_conds.empty() || !e->d_tc_steps) return fail(BCMPC_ERR_STATE, "bcmpc_set_termination has not been called");
+    for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= e->cfg.num_paths) return fail(BCMPC_ERR_ARG, "candidate index outside [0, num_paths)");
+    const bcmpc_engine* src = e->steps_on_fb && e->fb && e->fb->d_tc_steps ? e->fb : e;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+    for (int i = 0; i < n; ++i)
+        HIP_TRY(hipMemcpy(out + i, src->d_tc_steps + idx[i], sizeof(int32_t), hipMemcpyDeviceToHost));
     return BCMPC_OK;
 }
 
 // one term-cost launch on st: the engine's template plus this launch's trajectory, action source and K
 static int term_cost_launch(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
                             int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
-                            int64_t K, double* d_costs, hipStream_t st) {
+                            int64_t K, double* d_costs, int32_t* d_term_step, hipStream_t st) {
     TermCostArgs a = e->tc;
     a.traj = d_traj; a.actions = d_actions; a.costs = d_costs;
+    a.term_step = d_term_step;                           // (read by the DONE instances only)
     a.cem_mu = d_mu; a.cem_sigma = d_sigma; a.cem_iter = cem_iter;
     a.seed = seed; a.cand_offset = cand_offset; a.K = K;
     for (int j = 0; j < e->cfg.action_dim; ++j) {
@@ -971,9 +1033,10 @@ static int term_cost_launch(bcmpc_engine* e, const double* d_traj, const double*
     return BCMPC_OK;
 }
 
-int bcmpc_trajectory_cost_async(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
-                                int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
-                                int64_t K, double* d_costs, void* stream) {
+int bcmpc_trajectory_cost_steps_async(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
+                                      int64_t cand_offset, const double* d_mu, const double* d_sigma,
+                                      int32_t cem_iter, int64_t K, double* d_costs, int32_t* d_term_step,
+                                      void* stream) {
     if (!e || !d_traj || !d_costs) return fail(BCMPC_ERR_ARG, "null argument");
     if (e->cfg.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "trajectory_cost needs an engine created with BCMPC_COST_TERMS");
     if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
@@ -981,8 +1044,15 @@ int bcmpc_trajectory_cost_async(bcmpc_engine* e, const double* d_traj, const dou
     if (cem_iter < 0 || cem_iter >= (1 << 22)) return fail(BCMPC_ERR_ARG, "cem_iter must be in [0, 2^22)");
     if (!e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    return term_cost_launch(e, d_traj, d_actions, seed, cand_offset, d_mu, d_sigma, cem_iter, K, d_costs,
+    return term_cost_launch(e, d_traj, d_actions, seed, cand_offset, d_mu, d_sigma, cem_iter, K, d_costs, d_term_step,
                             (hipStream_t)stream);
+}
+
+int bcmpc_trajectory_cost_async(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
+                                int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
+                                int64_t K, double* d_costs, void* stream) {
+    return bcmpc_trajectory_cost_steps_async(e, d_traj, d_actions, seed, cand_offset, d_mu, d_sigma, cem_iter, K,
+                                             d_costs, nullptr, stream);
 }
 
 int bcmpc_terminal_value_supported(const bcmpc_config* cfg) {
@@ -1098,23 +1168,32 @@ int bcmpc_set_terminal_value(bcmpc_engine* e, const bcmpc_value_net* v, double w
 
 // one terminal-value launch on st: the engine's template plus this launch's rows and outputs
 static int terminal_value_launch(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
-                                 float* d_values, double* d_costs, hipStream_t st) {
+                                 float* d_values, double* d_costs, const int32_t* d_term_step, int32_t horizon,
+                                 hipStream_t st) {
     TerminalValueArgs a = e->tv;
     a.states = d_states; a.row_stride = row_stride; a.K = K;
     a.values = d_values; a.costs = d_costs;
+    a.term_step = d_term_step; a.horizon = horizon;
     HIP_TRY(launch_terminal_value(a, st));
     return BCMPC_OK;
 }
 
-int bcmpc_terminal_value_async(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
-                               float* d_values, double* d_costs_inout, void* stream) {
+int bcmpc_terminal_value_masked_async(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
+                                      float* d_values, double* d_costs_inout, const int32_t* d_term_step,
+                                      int32_t horizon, void* stream) {
     if (!e || !d_states) return fail(BCMPC_ERR_ARG, "null argument");
     if (!d_values && !d_costs_inout) return fail(BCMPC_ERR_ARG, "terminal_value needs d_values or d_costs_inout");
     if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
     if (!e->has_value) return fail(BCMPC_ERR_STATE, "bcmpc_set_terminal_value has not been called");
     if (row_stride < e->tv.S) return fail(BCMPC_ERR_ARG, "row_stride must be >= the value net's state_dim");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    return terminal_value_launch(e, d_states, row_stride, K, d_values, d_costs_inout, (hipStream_t)stream);
+    return terminal_value_launch(e, d_states, row_stride, K, d_values, d_costs_inout, d_term_step, horizon,
+                                 (hipStream_t)stream);
+}
+
+int bcmpc_terminal_value_async(bcmpc_engine* e, const double* d_states, int64_t row_stride, int64_t K,
+                               float* d_values, double* d_costs_inout, void* stream) {
+    return bcmpc_terminal_value_masked_async(e, d_states, row_stride, K, d_values, d_costs_inout, nullptr, 0, stream);
 }
 
 int bcmpc_last_terminal_values(bcmpc_engine* e, const int64_t* idx, int32_t n, float* out) {
@@ -1257,8 +1336,13 @@ int team_fallback(bcmpc_engine* e, bool collective) {
         if (const int rc = bcmpc_set_discount(f, e->gamma)) return rc;
     if (e->has_terms) {                              // (the same shape: the launch template carries over)
         f->tc = e->tc;
+        f->tc_terms = e->tc_terms;
         f->has_terms = true;
     }
+    f->tc_conds = e->tc_conds;                       // (a synchronous call: the fallback's step buffer may be made here)
+    f->done_cost = e->done_cost;
+    if (!f->tc_conds.empty() && !f->d_tc_steps)
+        HIP_TRY(hipMalloc(&f->d_tc_steps, (size_t)std::max<int64_t>(1, f->cfg.num_paths) * sizeof(int32_t)));
     if (e->has_value && (!f->has_value || f->value_version != e->value_version || f->tv.weight != e->tv.weight)) {
         const auto& hc = e->hv_copy;
         std::vector<const float*> k, b;
@@ -1277,6 +1361,7 @@ int team_fallback(bcmpc_engine* e, bool collective) {
     if (const int rc = bcmpc_set_action_bounds(f, lo, hi)) return rc;
     f->timing = e->timing;
     ++e->team_reruns;
+    e->steps_on_fb = true;                           // (bcmpc_last_termination_steps: the rerun's steps)
     return BCMPC_OK;
 }
 
@@ -1481,6 +1566,10 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
         return fail(BCMPC_ERR_ARG, "the value net reads " + std::to_string(e->tv.S) + " state dims, the engine has " +
                                        std::to_string(c.state_dim));
     if (terms || value) d_traj = d_traj ? d_traj : e->d_tc_traj;
+    // termination: term_cost_kernel leaves every candidate's terminating step in the engine's buffer and
+    // terminal_value_kernel adds the value only where that step is the horizon (the candidate is alive)
+    int32_t* const d_steps = terms && e->tc.n_done > 0 ? e->d_tc_steps : nullptr;
+    e->steps_on_fb = false;
     RolloutArgs a{};
     for (int l = 0; l < e->nwl; ++l) {
         const size_t end = l + 1 < e->nwl ? e->w_off[l + 1] : e->w_floats;
@@ -1617,11 +1706,13 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     }
     if (terms)
         if (const int rc = term_cost_launch(e, d_traj, d_actions, seed, cand_offset, cem ? cem->mu : nullptr,
-                                            cem ? cem->sigma : nullptr, cem ? cem->iter : 0, c.num_paths, d_costs, st))
+                                            cem ? cem->sigma : nullptr, cem ? cem->iter : 0, c.num_paths, d_costs,
+                                            d_steps, st))
             return rc;
     if (value)
         if (const int rc = terminal_value_launch(e, d_traj + (size_t)c.horizon * (size_t)c.num_paths * c.state_dim,
-                                                 c.state_dim, c.num_paths, e->d_vvalues, d_costs, st))
+                                                 c.state_dim, c.num_paths, e->d_vvalues, d_costs, d_steps, c.horizon,
+                                                 st))
             return rc;
     if (record_events) HIP_TRY(hipEventRecord(e->ev[1], st));
     if (d_result && (!fused || team_skipped)) HIP_TRY(launch_argmin(m, st));
@@ -1894,8 +1985,8 @@ int bcmpc_engine_layout(const bcmpc_engine* e, char* buf, int32_t cap) {
             else
                 std::snprintf(s, sizeof(s), "rollout_x3<%d,NC=%d,NW=%d> %s", e->HP, e->nc, e->nw, prec);
     }
-    std::snprintf(buf, (size_t)cap, "%s%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "",
-                  e->has_value ? "+value" : "");
+    std::snprintf(buf, (size_t)cap, "%s%s%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "",
+                  e->has_value ? "+value" : "", e->tc_conds.empty() ? "" : "+done");
     return BCMPC_OK;
 }
 

@@ -194,6 +194,13 @@ struct bcmpc_engine {
     TermCostArgs tc{};
     bool has_terms = false;
     double* d_tc_traj = nullptr;
+    // termination (bcmpc_set_termination): the cost terms and done conditions as given -- tc is digested from both,
+    // by whichever setter was called last -- and the launch chains' termination steps [num_paths], allocated by
+    // the setter (a captured graph keeps the address).  steps_on_fb: the last synchronous call reran on fb
+    std::vector<bcmpc_cost_term> tc_terms, tc_conds;
+    double done_cost = 0.0;
+    int32_t* d_tc_steps = nullptr;
+    bool steps_on_fb = false;
     // terminal value (terminal_value.hip): the launch template bcmpc_set_terminal_value builds.  The packed
     // kernels and the parameter block are allocated once at their largest size (a captured graph keeps the
     // addresses over a change of net); d_tc_traj, above, is allocated on first use for engines without terms

@@ -289,6 +289,11 @@ struct TermCostArgs {
     uint32_t slot_word[BCMPC_MAX_COST_TERMS / 4];   // (filled by launch_term_cost) the two arrays, a byte per slot
     double low[BCMPC_MAX_ACTION], high[BCMPC_MAX_ACTION];   // action bounds (regenerated actions)
     TermDev terms[BCMPC_MAX_COST_TERMS];     // by value: 32 x 32 bytes, no per-launch upload
+    // termination (cost_functions.episode_cost): terms[n_terms .. n_terms + n_done) are the done conditions
+    // (THRESHOLD on NEXT_STATE, a state slot each, ORed); n_terms + n_done <= BCMPC_MAX_COST_TERMS
+    int32_t n_done;
+    double done_cost;                        // added once, at the terminating step
+    int32_t* term_step;                      // [K] the terminating step, H: never; or nullptr (n_done > 0 only)
 };
 hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);
 
@@ -303,6 +308,7 @@ struct EnsembleReduceArgs {
 hipError_t launch_ensemble_reduce(const EnsembleReduceArgs& a, hipStream_t st);
 
 // ---- terminal value (terminal_value.hip): values[k] = V(states[k]), costs[k] += weight * values[k] ----
+// (with term_step: the add only for a candidate that never terminated; values[k] is written regardless)
 // params: [32] ob_mean, [32] ob_std, [L][HP] hidden biases, [16] final bias (row 0), all zero-padded.
 // w[l]: pack_layer(kernel l, Tin, Tout, TB) with Tin = 2 (layer 0) or HP / 16, Tout = HP / 16 and
 // TB = min(4, Tout) for the hidden layers, Tout = TB = 1 for the final one.
@@ -316,6 +322,8 @@ struct TerminalValueArgs {
     double* costs;                           // [K] in / out, or nullptr
     double weight;
     int32_t S, L, HP;                        // HP: terminal_value_padded(hidden)
+    const int32_t* term_step;                // [K] or nullptr: the cost add only where term_step[k] == horizon
+    int32_t horizon;
 };
 int terminal_value_padded(int hidden);       // 16, 32, 64, 128 or 256 (-1: outside [1, 256])
 hipError_t launch_terminal_value(const TerminalValueArgs& a, hipStream_t st);

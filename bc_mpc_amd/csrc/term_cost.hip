@@ -26,9 +26,18 @@
 // Action slots: a[h][k][j] from the explicit [H][K][A] array, prefetched like a state dim, or regenerated
 // per trip with the functions the rollout kernels call (rng_action / cem_action at global index
 // cand_offset + k).  A cost without an ACTION term has no action slot and never runs Philox.
+//
+// Termination (the DONE instances; cost_functions.episode_cost is the definition): done conditions are further
+// TermDev entries after the cost terms -- thresholds on the next state, combined with OR.  In a trip a condition
+// sets bit u of a per-lane flag word instead of adding to acc[u]; the fold after the trip pays a step only while
+// the candidate is alive and, on a flagged step, adds done_cost once, notes the step and pays nothing after it.
+// The padded steps of the last trip (scored on the repeated row) neither pay nor terminate.  Dead lanes ride
+// along to the end of the walk: a wave that leaves once all of its lanes are dead measured no faster.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <cmath>
 
 #include "../../include/bcmpc.h"
 #include "kernels.h"
@@ -56,7 +65,7 @@ __device__ __forceinline__ double term_div(double a, double b, double r, bool fa
     return __ddiv_rn(a, b);
 }
 
-template <int ND, int PF, bool REGEN>
+template <int ND, int PF, bool REGEN, bool DONE>
 __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArgs a) {
     constexpr int R = PF + 1;                            // LDS ring: row r lives in rows[r % R]
     __shared__ double rows[R][ND][kTermLanes];
@@ -105,11 +114,14 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
 
     // The terms are uniform, one 32-byte scalar load each: term t + 1 (term 0 of the next trip after the
     // last) is requested before term t is evaluated.
-    const int nt = a.n_terms;
+    const int nc = a.n_terms;                            // the cost terms; the done conditions follow them
+    const int nt = DONE ? nc + a.n_done : nc;
     TermDev cur = a.terms[0];
     int tn = 0;
 
     double total = 0.0;
+    bool dead = false;                                   // (DONE) the candidate has terminated, at step tstep
+    int tstep = H;
 #pragma unroll 1
     for (int h0 = 0; h0 < H; h0 += PF) {
         // rows h0 + 1 .. h0 + PF arrive and go to the ring; their registers take the next trip's rows
@@ -139,6 +151,7 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
         double acc[PF];
 #pragma unroll
         for (int u = 0; u < PF; ++u) acc[u] = 0.0;
+        uint32_t flags = 0;                              // (DONE) bit u: a condition holds on step h0 + u's s'
 #pragma unroll 1
         for (int t = 0; t < nt; ++t) {
             tn = tn + 1 < nt ? tn + 1 : 0;
@@ -148,7 +161,15 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
             const int sl = (int)(T.meta >> 8);
             const int nx = (T.meta >> 4) & 1u;           // NEXT_STATE: the value of row h + 1
             const double w = T.weight, p = T.param;
-            if (kind == BCMPC_TERM_DIFF) {
+            if (DONE && t >= nc) {
+#pragma unroll
+                for (int u = 0; u < PF; ++u) {
+                    const double x = rows[pos(u + 1)][sl][lane];
+                    const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
+                                   : cmp == BCMPC_CMP_LE ? x <= p : x < p;
+                    flags |= (hit ? 1u : 0u) << u;
+                }
+            } else if (kind == BCMPC_TERM_DIFF) {
                 const bool fast = (T.meta >> 5) & 1u;
 #pragma unroll
                 for (int u = 0; u < PF; ++u) {
@@ -176,10 +197,23 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
             }
         }
 #pragma unroll
-        for (int u = 0; u < PF; ++u)
-            if (h0 + u < H) total = __dadd_rn(total, acc[u]);
+        for (int u = 0; u < PF; ++u) {
+            if (DONE) {
+                if (!dead && h0 + u < H) {
+                    total = __dadd_rn(total, acc[u]);    // the terminating step is still paid
+                    if ((flags >> u) & 1u) {
+                        total = __dadd_rn(total, a.done_cost);
+                        dead = true;
+                        tstep = h0 + u;
+                    }
+                }
+            } else if (h0 + u < H) {
+                total = __dadd_rn(total, acc[u]);
+            }
+        }
     }
     a.costs[k] = total;
+    if (DONE && a.term_step) a.term_step[k] = tstep;
 }
 
 template <int ND, int PF>
@@ -189,8 +223,15 @@ hipError_t launch_t(TermCostArgs a, hipStream_t st) {
     const bool regen = !a.actions && a.n_state_slots < a.n_slots;     // Philox only where an ACTION term needs it
     const int64_t blocks = (a.K + kTermLanes - 1) / kTermLanes;
     if (blocks > INT32_MAX) return hipErrorInvalidValue;
-    if (regen) hipLaunchKernelGGL((term_cost_kernel<ND, PF, true>), dim3((unsigned)blocks), dim3(kTermLanes), 0, st, a);
-    else hipLaunchKernelGGL((term_cost_kernel<ND, PF, false>), dim3((unsigned)blocks), dim3(kTermLanes), 0, st, a);
+    const dim3 grid((unsigned)blocks), block(kTermLanes);
+    if (a.n_done > 0) {                                  // termination: the DONE instances, a family of their own
+        if (regen) hipLaunchKernelGGL((term_cost_kernel<ND, PF, true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((term_cost_kernel<ND, PF, false, true>), grid, block, 0, st, a);
+    } else if (regen) {
+        hipLaunchKernelGGL((term_cost_kernel<ND, PF, true, false>), grid, block, 0, st, a);
+    } else {
+        hipLaunchKernelGGL((term_cost_kernel<ND, PF, false, false>), grid, block, 0, st, a);
+    }
     return hipGetLastError();
 }
 
@@ -200,14 +241,17 @@ hipError_t launch_t(TermCostArgs a, hipStream_t st) {
 // doubles (64 VGPRs) of prefetch registers in every instance
 hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st) {
     if (!a.traj || !a.costs || a.K < 1 || a.H < 1 || a.S < 1 || a.S > BCMPC_MAX_STATE || a.A < 1 ||
-        a.A > BCMPC_MAX_ACTION || a.n_terms < 0 || a.n_terms > BCMPC_MAX_COST_TERMS || a.n_slots < 0 ||
-        a.n_slots > a.n_terms || a.n_state_slots < 0 || a.n_state_slots > a.n_slots)
+        a.A > BCMPC_MAX_ACTION || a.n_terms < 0 || a.n_done < 0 || a.n_terms + a.n_done > BCMPC_MAX_COST_TERMS ||
+        a.n_slots < 0 || a.n_slots > a.n_terms + a.n_done || a.n_state_slots < 0 || a.n_state_slots > a.n_slots ||
+        !std::isfinite(a.done_cost))
         return hipErrorInvalidValue;
     for (int i = 0; i < a.n_slots; ++i)
         if ((a.slot_action[i] != 0) != (i >= a.n_state_slots) || a.slot_index[i] >= (a.slot_action[i] ? a.A : a.S))
             return hipErrorInvalidValue;
-    for (int t = 0; t < a.n_terms; ++t)
+    for (int t = 0; t < a.n_terms + a.n_done; ++t)
         if ((int)(a.terms[t].meta >> 8) >= a.n_slots) return hipErrorInvalidValue;
+    for (int t = a.n_terms; t < a.n_terms + a.n_done; ++t)      // a done condition reads a state slot
+        if ((int)(a.terms[t].meta >> 8) >= a.n_state_slots) return hipErrorInvalidValue;
     if (a.n_slots <= 4) return launch_t<4, 8>(a, st);
     if (a.n_slots <= 8) return launch_t<8, 4>(a, st);
     if (a.n_slots <= 16) return launch_t<16, 2>(a, st);

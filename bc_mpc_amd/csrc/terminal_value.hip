@@ -2,9 +2,10 @@
 //
 // v[k] = V(states[k]) for the critic the reference trains beside its policy (ppo_bc_policy.py:56-64, pi/vf):
 //   obz = clip((f32(s) - ob_mean) / ob_std, -5, 5);  h = tanh(h W + b) x L;  v = h w_final + b_final
-// and, in the same launch, costs[k] = costs[k] + weight * (double)v[k] -- the stage between "cost vector" and
-// "argmin / select / update" of an engine with a value set (capi.cpp rollout_impl).  The definition is
-// bc_mpc_amd/value.py terminal_values; obz is bit-identical to it (one f64 -> f32 conversion, one f32 subtract,
+// and, in the same launch, costs[k] = costs[k] + weight * (double)v[k] (with termination steps given: only where
+// term_step[k] == horizon, the candidate that never terminated; values[k] is written either way) -- the stage
+// between "cost vector" and "argmin / select / update" of an engine with a value set (capi.cpp rollout_impl).
+// The definition is bc_mpc_amd/value.py terminal_values; obz is bit-identical to it (one f64 -> f32 conversion, one f32 subtract,
 // one correctly rounded f32 divide, a clip by compares so that NaN stays NaN), the dense layers are f32 fma
 // chains on v_mfma_f32_16x16x4_f32 with tanh_fast (device_common.h), no f16 anywhere.
 //
@@ -123,7 +124,9 @@ __global__ __launch_bounds__(kTvWaves * 64) void terminal_value_kernel(const Ter
     if (valid && q == 0) {                                   // row 0 of the final tile: lane group 0, r = 0
         const float v = o[0][0];
         if (a.values) a.values[cand] = v;
-        if (a.costs) a.costs[cand] = __dadd_rn(a.costs[cand], __dmul_rn(a.weight, (double)v));
+        // (a terminated candidate has no future return: its total is left as it is, not "+ weight * 0")
+        if (a.costs && (!a.term_step || a.term_step[cand] == a.horizon))
+            a.costs[cand] = __dadd_rn(a.costs[cand], __dmul_rn(a.weight, (double)v));
     }
 }
 

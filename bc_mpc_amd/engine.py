@@ -414,30 +414,54 @@ class RolloutEngine(_EngineCalls):
     def set_cost_terms(self, term_cost) -> None:
         """The objective of a ``cost="terms"`` engine (bcmpc_set_cost_terms): a ``cost_functions.TermCost``
         (or an iterable of its terms).  Every rollout entry raises until this has been called; calling it
-        again replaces the list for the next launch."""
+        again replaces the list for the next launch.  A ``TermCost`` with ``done`` conditions also sets the
+        engine's termination (bcmpc_set_termination), one without removes it; idempotent on ``key()``."""
         from .cost_functions import TermCost
         tc = term_cost if isinstance(term_cost, TermCost) else TermCost(term_cost)
         if self.cost_terms is not None and tc.key() == self.cost_terms.key():
             return
         tc.validate(self.state_dim, self.action_dim)
-        arr = (_lib.CostTerm * max(1, len(tc.terms)))()
-        for dst, t in zip(arr, tc.terms):
-            dst.kind, dst.source, dst.index, dst.cmp = t.kind, t.source, t.index, t.cmp
-            dst.weight, dst.param = t.weight, t.param
-        _lib.check(self._lib.bcmpc_set_cost_terms(self._h, arr, ctypes.c_int32(len(tc.terms))))
+
+        def pack(terms):
+            arr = (_lib.CostTerm * max(1, len(terms)))()
+            for dst, t in zip(arr, terms):
+                dst.kind, dst.source, dst.index, dst.cmp = t.kind, t.source, t.index, t.cmp
+                dst.weight, dst.param = t.weight, t.param
+            return arr, ctypes.c_int32(len(terms))
+
+        # the terms, then the termination (the library holds both to one budget of 32 entries: the conditions
+        # it still has from the previous cost go first when the new terms would not fit beside them)
+        held = self.cost_terms.done_conditions if self.cost_terms is not None else ()
+        if len(tc.terms) + len(held) > _lib.MAX_COST_TERMS:
+            _lib.check(self._lib.bcmpc_set_termination(self._h, None, ctypes.c_int32(0), ctypes.c_double(0.0)))
+            self.cost_terms, held = None, ()
+        _lib.check(self._lib.bcmpc_set_cost_terms(self._h, *pack(tc.terms)))
+        self.cost_terms = None                  # (until both calls have succeeded: the next call sends all again)
+        if tc.done_conditions or held:
+            _lib.check(self._lib.bcmpc_set_termination(self._h, *pack(tc.done_conditions),
+                                                       ctypes.c_double(tc.done_cost)))
         self.cost_terms = tc
 
     def trajectory_cost_async(self, d_traj: int, K: int, d_costs: int, d_actions: Optional[int] = None,
                               seed: int = 0, cand_offset: int = 0, d_mu: Optional[int] = None,
                               d_sigma: Optional[int] = None, cem_iter: int = 0,
-                              stream: Optional[int] = None) -> None:
+                              stream: Optional[int] = None, d_term_step: Optional[int] = None) -> None:
         """The term-cost kernel alone on device pointers (bcmpc_trajectory_cost_async), stream-ordered:
         ``d_traj`` ``[H+1, K, S]`` f64 -> ``d_costs`` ``[K]`` f64 under the terms of set_cost_terms.  ACTION
         terms read ``d_actions`` ``[H, K, A]``, or, when it is None, the actions the rollout kernels draw
         for (``seed``, ``cand_offset + k``): the Philox shooting draw, or the CEM / MPPI sample of
-        ``cem_iter`` from ``d_mu`` / ``d_sigma`` ``[H, A]``.  ``K`` need not equal ``num_paths``."""
+        ``cem_iter`` from ``d_mu`` / ``d_sigma`` ``[H, A]``.  ``K`` need not equal ``num_paths``.  A cost with
+        ``done`` conditions is scored as ``cost_functions.episode_cost`` defines; ``d_term_step`` (``[K]`` int32)
+        then receives every candidate's terminating step, H where it never terminated
+        (bcmpc_trajectory_cost_steps_async)."""
         stream = self.stream if stream is None else stream
         vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        if d_term_step:
+            _lib.check(self._lib.bcmpc_trajectory_cost_steps_async(
+                self._h, vp(d_traj), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
+                vp(d_mu), vp(d_sigma), ctypes.c_int32(cem_iter), ctypes.c_int64(K), vp(d_costs), vp(d_term_step),
+                ctypes.c_void_p(stream)))
+            return
         _lib.check(self._lib.bcmpc_trajectory_cost_async(
             self._h, vp(d_traj), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
             vp(d_mu), vp(d_sigma), ctypes.c_int32(cem_iter), ctypes.c_int64(K), vp(d_costs),
@@ -481,16 +505,24 @@ class RolloutEngine(_EngineCalls):
 
     def terminal_value_async(self, d_states: int, K: int, d_values: Optional[int] = None,
                              d_costs: Optional[int] = None, row_stride: Optional[int] = None,
-                             stream: Optional[int] = None) -> None:
+                             stream: Optional[int] = None, d_term_step: Optional[int] = None,
+                             horizon: Optional[int] = None) -> None:
         """The value kernel alone on device pointers (bcmpc_terminal_value_async), stream-ordered: row k of
         ``d_states`` (the net's ``state_dim`` f64 at ``k * row_stride``, default dense) -> ``d_values[k]`` f32
-        and / or ``d_costs[k] += weight * float64(v_k)`` in place.  ``K`` need not equal ``num_paths``."""
+        and / or ``d_costs[k] += weight * float64(v_k)`` in place.  ``K`` need not equal ``num_paths``.  With
+        ``d_term_step`` (``[K]`` int32) the add is made only where ``d_term_step[k] == horizon`` (default: the
+        engine's), ``value.add_to_costs``'s gated form (bcmpc_terminal_value_masked_async)."""
         stream = self.stream if stream is None else stream
         vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        stride = ctypes.c_int64((self._value[3].state_dim if self._value else self.state_dim)
+                                if row_stride is None else row_stride)
+        if d_term_step:
+            _lib.check(self._lib.bcmpc_terminal_value_masked_async(
+                self._h, vp(d_states), stride, ctypes.c_int64(K), vp(d_values), vp(d_costs), vp(d_term_step),
+                ctypes.c_int32(self.horizon if horizon is None else horizon), ctypes.c_void_p(stream)))
+            return
         _lib.check(self._lib.bcmpc_terminal_value_async(
-            self._h, vp(d_states), ctypes.c_int64((self._value[3].state_dim if self._value else self.state_dim)
-                                    if row_stride is None else row_stride),
-            ctypes.c_int64(K), vp(d_values), vp(d_costs), ctypes.c_void_p(stream)))
+            self._h, vp(d_states), stride, ctypes.c_int64(K), vp(d_values), vp(d_costs), ctypes.c_void_p(stream)))
 
     def last_terminal_values(self, local_indices) -> np.ndarray:
         """f32 values of the local candidates ``local_indices`` from the engine's last launch chain
@@ -500,6 +532,17 @@ class RolloutEngine(_EngineCalls):
         _lib.check(self._lib.bcmpc_last_terminal_values(
             self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.c_int32(idx.shape[0]),
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def last_termination_steps(self, local_indices) -> np.ndarray:
+        """int32 terminating steps (H: never) of the local candidates ``local_indices`` from the engine's last
+        launch chain (bcmpc_last_termination_steps; a CEM / MPPI call: its last iteration), on an engine whose
+        ``TermCost`` has ``done`` conditions.  Diagnostics: one small copy."""
+        idx = np.ascontiguousarray(np.asarray(local_indices, dtype=np.int64).reshape(-1))
+        out = np.empty(idx.shape[0], dtype=np.int32)
+        _lib.check(self._lib.bcmpc_last_termination_steps(
+            self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.c_int32(idx.shape[0]),
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return out
 
     def set_action_bounds(self, low, high) -> None:

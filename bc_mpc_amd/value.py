@@ -14,7 +14,8 @@ policy head.  ``terminal_values`` below is THE definition, as ``TermCost.__call_
   cannot be bit-equal to BLAS; the accuracy bars are ``error_bound`` (per candidate, derived) and the RMS
   against ``terminal_values_seq32`` (strictly sequential f32 dot products), both measured against
   ``terminal_values_f64``.
-* ``add_to_costs``: one rounded f64 multiply and one rounded f64 add, no contraction.
+* ``add_to_costs``: one rounded f64 multiply and one rounded f64 add, no contraction; with the termination steps
+  of a ``TermCost`` with ``done`` only for the candidates that never terminated.
 
 The controllers default ``weight`` to -1.0: a value is a return, a cost is minus a reward.  A discount is the
 caller's: pass ``-gamma**H``.
@@ -180,10 +181,20 @@ def error_bound(spec: ValueSpec, obz32) -> np.ndarray:
     return e[:, 0]
 
 
-def add_to_costs(costs, values, weight: float) -> np.ndarray:
-    """total = cost + weight * float64(v): one rounded f64 multiply, one rounded f64 add."""
+def add_to_costs(costs, values, weight: float, term_step=None, horizon=None) -> np.ndarray:
+    """total = cost + weight * float64(v): one rounded f64 multiply, one rounded f64 add.
+
+    ``term_step`` (with ``horizon``; ``cost_functions.episode_cost``'s second result): the add is made only where
+    ``term_step == horizon``, the candidates that never terminated.  A terminated episode has no future return:
+    its total is left untouched -- not ``+ weight * 0``, which would turn a ``-0.0`` into ``+0.0``."""
+    costs = np.asarray(costs, dtype=np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
-        return np.asarray(costs, dtype=np.float64) + np.float64(weight) * np.asarray(values, dtype=np.float32).astype(np.float64)
+        total = costs + np.float64(weight) * np.asarray(values, dtype=np.float32).astype(np.float64)
+    if term_step is None:
+        return total
+    if horizon is None:
+        raise ValueError("add_to_costs: term_step needs the horizon")
+    return np.where(np.asarray(term_step) == int(horizon), total, costs)
 
 
 def check_weight(weight) -> float:

@@ -259,7 +259,8 @@ int bcmpc_set_discount(bcmpc_engine* eng, double gamma);
 /* The cost of a BCMPC_COST_TERMS engine (BCMPC_ERR_ARG on any other): n terms, 0 <= n <=
  * BCMPC_MAX_COST_TERMS, copied.  n == 0: every cost is 0 and index 0 wins.  BCMPC_ERR_ARG: unknown kind /
  * source / cmp, index outside the state (ACTION: the action), a DIFF whose source is not STATE, weight or
- * param not finite, a DIFF param of 0.  Every rollout entry of such an engine returns BCMPC_ERR_STATE
+ * param not finite, a DIFF param of 0, more than BCMPC_MAX_COST_TERMS entries together with the done conditions
+ * the engine holds (bcmpc_set_termination).  Every rollout entry of such an engine returns BCMPC_ERR_STATE
  * before this call.  May be called again between launches (the next launch uses the new list). */
 int bcmpc_set_cost_terms(bcmpc_engine* eng, const bcmpc_cost_term* terms, int32_t n);
 
@@ -330,6 +331,48 @@ int bcmpc_terminal_value_async(bcmpc_engine* eng, const double* d_states, int64_
  * call: its last iteration), after a synchronisation of the engine's stream.  BCMPC_ERR_ARG: null pointers,
  * n < 1, an index outside [0, num_paths).  BCMPC_ERR_STATE: no value set. */
 int bcmpc_last_terminal_values(bcmpc_engine* eng, const int64_t* idx, int32_t n, float* out);
+
+/* ---- Episode termination for cost terms (definition: bc_mpc_amd/cost_functions.py episode_cost) ------------
+ *   total = 0; t = H
+ *   for h in 0 .. H-1:  total = total + c_h;  if any condition holds on s_{h+1}: total = total + done_cost;
+ *                                                                             t = h; stop
+ * every operation one rounded f64 operation, in this order; the terminating step is still paid.  With a
+ * terminal value set, total = total + weight * (double)V(s_H) only where t == H; a terminated candidate's total
+ * is left untouched.  The argmin, CEM's elite selection, the MPPI weights and the ensemble rules then run on
+ * total as before; every ensemble member terminates on its own trajectory.  Additive to ABI 5: callers detect
+ * the feature by the symbol bcmpc_set_termination.
+ *
+ * bcmpc_set_termination: n done conditions, ORed, copied; n == 0 removes termination.  A condition is a
+ * bcmpc_cost_term of kind BCMPC_TERM_THRESHOLD and source BCMPC_SRC_NEXT_STATE with a valid cmp, an index
+ * inside the state, a finite param and weight 0 (a NaN compares false).  done_cost is finite and added once, at
+ * the terminating step.  Cost terms plus conditions are at most BCMPC_MAX_COST_TERMS: whichever of
+ * bcmpc_set_cost_terms and bcmpc_set_termination is called second checks it.  The call allocates the engine's
+ * termination-step buffer int32 [num_paths] -- here, never inside a stream-ordered entry, so a captured graph
+ * keeps its addresses -- and from then on every entry built on the rollout launch applies the conditions.
+ * BCMPC_ERR_ARG (every check before any HIP call): a null engine, not a BCMPC_COST_TERMS engine, n outside
+ * [0, 32], any of the above violated, the budget exceeded. */
+int bcmpc_set_termination(bcmpc_engine* eng, const bcmpc_cost_term* conds, int32_t n, double done_cost);
+
+/* bcmpc_trajectory_cost_async plus d_term_step: device K int32, candidate k's terminating step in [0, H], H
+ * exactly when it never terminated; may be NULL.  On an engine without termination nothing is written to it.
+ * bcmpc_trajectory_cost_async itself applies the engine's termination to d_costs and writes no steps. */
+int bcmpc_trajectory_cost_steps_async(bcmpc_engine* eng, const double* d_traj, const double* d_actions,
+                                      uint64_t seed, int64_t cand_offset, const double* d_mu,
+                                      const double* d_sigma, int32_t cem_iter, int64_t K, double* d_costs,
+                                      int32_t* d_term_step, void* stream);
+
+/* bcmpc_terminal_value_async plus the gate: with d_term_step (device K int32) the cost add is made only where
+ * d_term_step[k] == horizon; elsewhere d_costs_inout[k] keeps its bits.  d_values[k] is written regardless.
+ * d_term_step == NULL: bcmpc_terminal_value_async, bit for bit. */
+int bcmpc_terminal_value_masked_async(bcmpc_engine* eng, const double* d_states, int64_t row_stride, int64_t K,
+                                      float* d_values, double* d_costs_inout, const int32_t* d_term_step,
+                                      int32_t horizon, void* stream);
+
+/* Diagnostics: the terminating steps of local candidates idx[0..n) from the engine's LAST launch chain (a CEM /
+ * MPPI call: its last iteration; a team engine's rerun: the fallback's), after a synchronisation of the
+ * engine's stream.  BCMPC_ERR_ARG: null pointers, n < 1, an index outside [0, num_paths).  BCMPC_ERR_STATE: no
+ * termination set. */
+int bcmpc_last_termination_steps(bcmpc_engine* eng, const int64_t* idx, int32_t n, int32_t* out);
 
 /* env.action_space.low / .high (controllers.py:53). Defaults: [-1, 1]^A. */
 int bcmpc_set_action_bounds(bcmpc_engine* eng, const double* low, const double* high);
