@@ -151,6 +151,15 @@ class Mppi(ctypes.Structure):
     ]
 
 
+class Sampling(ctypes.Structure):
+    """bcmpc_sampling: the planners' sampling distribution (bc_mpc_amd/sampling.py); zeros are the default."""
+    _fields_ = [
+        ("rho", ctypes.c_double),
+        ("keep_elites", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 class MppiStats(ctypes.Structure):
     """One MPPI update's statistics (bcmpc_mppi_stats); no valid candidate: 0, 0, NaN, 0."""
     _fields_ = [
@@ -285,6 +294,25 @@ SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
       ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p]),
+    ("bcmpc_cem_get_action_s", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.c_uint64, _DP, _DP,
+      ctypes.POINTER(Result)]),
+    ("bcmpc_mppi_get_action_s", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.c_uint64, _DP, _DP,
+      ctypes.POINTER(Result), ctypes.POINTER(MppiStats)]),
+    ("bcmpc_cem_get_actions_batch_s", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.c_uint64,
+      ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result), _DP]),
+    ("bcmpc_mppi_get_actions_batch_s", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.c_uint64,
+      ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result), ctypes.POINTER(MppiStats), _DP]),
+    ("bcmpc_plan_sample_corr_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_plan_keep_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+      ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_ensemble_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_ensemble_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_ensemble_size", ctypes.c_int, [ctypes.c_void_p]),

@@ -44,7 +44,9 @@ class CEMcontroller(Planner):
     """Cross-entropy-method MPC on the MI355X engine (BASELINE cfg5 CEM outer loop).  ``get_action`` /
     ``get_actions`` return the first action of the best sample of all iterations; ``last_mu`` / ``last_sigma``
     hold the refitted distribution, ``last_cost`` / ``last_position`` the best sample (batched: ``[B, H, A]``
-    and ``[B]``)."""
+    and ``[B]``).  ``noise_rho`` in ``[0, 1)``: AR(1) noise over the horizon instead of independent draws;
+    ``keep_elites``: every iteration after the first starts with all elites of the one before (sampling.py,
+    DESIGN.md 9j; both are read on every call, one rank and one dynamics model only)."""
     _KIND = "CEM"
 
     def __init__(self,
@@ -65,10 +67,13 @@ class CEMcontroller(Planner):
                  device: Optional[int] = None,
                  process_group=None,
                  terminal_value=None,
-                 terminal_weight: float = -1.0):
+                 terminal_weight: float = -1.0,
+                 noise_rho: float = 0.0,
+                 keep_elites: bool = False):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0xCE5EED if seed is None else seed, device, process_group,
-                         terminal_value=terminal_value, terminal_weight=terminal_weight)
+                         terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho,
+                         keep_elites=keep_elites)
         self.elite_frac = float(elite_frac)
         self._n_elite = n_elite
         self.alpha = float(alpha)
@@ -81,7 +86,8 @@ class CEMcontroller(Planner):
         return max(1, int(round(self.elite_frac * int(self.num_simulated_paths))))
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
-        res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed,
+                                         **self._sampling_args())
         self._note_planner_value(eng, res.best_index, K)
         return self._publish(res.best_cost, res.best_index, res.first_action, mu, sd)
 
@@ -103,7 +109,8 @@ class CEMcontroller(Planner):
         return first
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
-        res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed)
+        res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed,
+                                          **self._sampling_args())
         self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu, self.last_sigma = mu, sd

@@ -44,6 +44,7 @@ import numpy as np
 
 from . import distributed as _dist
 from . import policy as _policy
+from . import sampling as _sampling
 from . import value as _value
 from . import weights as _weights
 from .cost_functions import TermCost, is_cheetah_cost, trajectory_cost_fn
@@ -274,10 +275,16 @@ class Planner(_TerminalValue, Controller):
     itself (``_KIND``), adds its constructor arguments and runs its engine call in ``_solve`` / ``_solve_batch``,
     which publish the ``last_*`` attributes, store the plan and return the action(s)."""
     _KIND = None            # "CEM" | "MPPI": the refusals' wording
+    # what is sampled (sampling.py): read on every call, never an engine constructor argument
+    noise_rho = 0.0
+    keep_elites = False
 
     def __init__(self, env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
-                 warm_start, seed, device, process_group, terminal_value=None, terminal_weight=-1.0):
+                 warm_start, seed, device, process_group, terminal_value=None, terminal_weight=-1.0, noise_rho=0.0,
+                 keep_elites=False):
         self._init_terminal_value(terminal_value, terminal_weight)
+        self.noise_rho = _sampling.check_rho(noise_rho)
+        self.keep_elites = _sampling.check_keep_elites(keep_elites)
         self.env = env
         self.dyn_model = dyn_model
         self.horizon = horizon
@@ -379,6 +386,22 @@ class Planner(_TerminalValue, Controller):
     def _next_seed(self) -> int:
         return int(self._seed_rng.randint(0, 2**62, dtype=np.int64))
 
+    def _sampling_args(self) -> dict:
+        """The engine calls' ``rho`` / ``keep_elites``, passed only when they differ from the defaults (the call
+        at the defaults is the call it has always been, also on an engine double of the earlier signature)."""
+        rho, keep = _sampling.check_rho(self.noise_rho), _sampling.check_keep_elites(self.keep_elites)
+        kw = {}
+        if rho != 0.0:
+            kw["rho"] = rho
+        if keep:
+            kw["keep_elites"] = True
+        return kw
+
+    def _refuse_sampling(self, where: str) -> None:
+        """Correlated noise and elite carry-over run on one engine of one rank; raised before a seed is drawn."""
+        if self._sampling_args():
+            raise NotImplementedError(f"{self._KIND}controller: noise_rho / keep_elites are not built {where}")
+
     def _model(self, S: int, A: int):
         """(spec, normalisation, version, the TermCost scored on the device or None) of a supported pair of
         model and cost: the learned reward of a reward model, else the fused cheetah cost or a TermCost."""
@@ -423,6 +446,7 @@ class Planner(_TerminalValue, Controller):
             # an EnsembleDynamicsModel (ensemble.py): its engine has RolloutEngine's planner calls, scored on the
             # members' combined value; it refuses ranks, costs and members itself, before anything is drawn
             from . import ensemble as _ensemble
+            self._refuse_sampling("over an EnsembleDynamicsModel")
             state = np.asarray(state, dtype=np.float64).reshape(-1)
             eng = _ensemble._ctrl_engine(self, S, A, K, "single")
             mu0, sd0 = self.initial_distribution()
@@ -430,6 +454,7 @@ class Planner(_TerminalValue, Controller):
         rank, ws = _dist.world(self._group)
         if ws > 1:
             self._refuse_ranks(ws)
+            self._refuse_sampling(f"for more than one rank (world size {ws})")
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         spec, norm, version, terms = self._model(S, A)
         mu0, sd0 = self.initial_distribution()

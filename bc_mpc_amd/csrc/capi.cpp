@@ -539,7 +539,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
-                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_tc_traj,
+                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_keep, (void*)e->d_keep_count, (void*)e->d_tc_traj,
                     (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues, (void*)e->d_tc_steps})
         if (p) (void)hipFree(p);
     if (e->h_bresults) (void)hipHostFree(e->h_bresults);

@@ -107,6 +107,9 @@ struct bcmpc_engine {
     bcmpc_mppi_stats* d_bstats = nullptr;   // [plan_cap]
     int32_t plan_cap = 0;
     bcmpc_elite* d_belite = nullptr; size_t belite_cap = 0;   // [n_envs][n_elite] records
+    // CEM elite carry-over (plan_noise.hip): the elites' sequences [n_envs][n_elite][H][A] and their counts
+    double* d_keep = nullptr; size_t keep_cap = 0;
+    int32_t* d_keep_count = nullptr; int32_t keep_count_cap = 0;
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;
     int team_kind = 0;                  // 0 plain delta net, 1 + policy, 2 reward net (+ policy)

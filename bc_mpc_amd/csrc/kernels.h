@@ -371,4 +371,29 @@ hipError_t launch_select_batch(const SelectBatchArgs& a, hipStream_t st);
 hipError_t launch_refit_batch(const RefitBatchArgs& a, hipStream_t st);
 hipError_t launch_mppi_update_batch(const MppiBatchArgs& a, hipStream_t st);
 
+// ---- correlated sampling noise and the CEM elite carry-over (plan_noise.hip; bc_mpc_amd/sampling.py) ----
+struct PlanSampleCorrArgs {                  // PlanSampleArgs with n[h] = rho n[h-1] + c z[h] for cem_normal's z[h]
+    const double* mu;
+    const double* sigma;                     // [n_envs][H][A] each
+    const double* consts;
+    double* out;                             // [H][Ktot][A]
+    const double* keep;                      // [n_envs][n_elite][H][A] carried sequences, or nullptr: none
+    const int32_t* keep_count;               // [n_envs]: environment b's first keep_count[b] columns are copies
+    uint64_t seed;
+    int64_t cand_offset, K, Ktot;
+    int32_t iter, H, A, n_elite;
+    double rho, c;                           // c = sqrt(1 - rho^2), rounded once on the host
+};
+struct PlanKeepArgs {                        // keep[b][e] = the stored sequence of elite[b][e], e < count[b]
+    const bcmpc_elite* elite;                // [n_envs][n_elite] (select_batch's output)
+    const int32_t* count;                    // [n_envs]
+    const double* actions;                   // [H][Ktot][A], column = index - cand_offset
+    double* keep;                            // [n_envs][n_elite][H][A]
+    int32_t* keep_count;                     // [n_envs]: the leading records that name one of b's own K columns
+    int64_t cand_offset, K, Ktot;
+    int32_t n_envs, n_elite, H, A;
+};
+hipError_t launch_plan_sample_corr(const PlanSampleCorrArgs& a, hipStream_t st);
+hipError_t launch_plan_keep(const PlanKeepArgs& a, hipStream_t st);
+
 }  // namespace bcmpc

@@ -1,5 +1,5 @@
-// planners.cpp -- CEM and MPPI on the device: the single-plan chain, the batched plans (plan_batch.hip) and
-// the model ensembles.
+// planners.cpp -- CEM and MPPI on the device: the single-plan chain, the batched plans (plan_batch.hip), what
+// they sample (plan_noise.hip) and the model ensembles.
 #include "host_internal.h"
 
 using namespace bcmpc::host;
@@ -98,6 +98,20 @@ static int k_global_check(int64_t k_global, const char* prefix, int64_t K, const
     return BCMPC_OK;
 }
 
+// The sampling distribution of a planner call (bcmpc_sampling; nullptr: the default -- white noise, nothing carried)
+static bool sampling_default(const bcmpc_sampling* s) { return !s || (s->rho == 0.0 && s->keep_elites == 0); }
+static int rho_check(double rho) {
+    if (!(std::isfinite(rho) && rho >= 0.0 && rho < 1.0)) return fail(BCMPC_ERR_ARG, "rho must be finite and in [0, 1)");
+    return BCMPC_OK;
+}
+static int sampling_check(const bcmpc_sampling* s, bool mppi) {
+    if (!s) return BCMPC_OK;
+    if (const int rc = rho_check(s->rho)) return rc;
+    if (s->keep_elites != 0 && s->keep_elites != 1) return fail(BCMPC_ERR_ARG, "keep_elites must be 0 or 1");
+    if (mppi && s->keep_elites) return fail(BCMPC_ERR_ARG, "keep_elites is a CEM setting: MPPI has no elites to carry");
+    return BCMPC_OK;
+}
+
 // a synchronous planner call's input plans, kept on a team engine for the rerun after a give-up: n doubles of
 // mu, and of sigma where the call writes it back (CEM)
 struct PlanInputs {
@@ -171,6 +185,31 @@ static int plan_sample_impl(bcmpc_engine* e, const double* d_mu, const double* d
     a.seed = seed; a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
     a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
     HIP_TRY(launch_plan_sample(a, st));
+    return BCMPC_OK;
+}
+
+// d_keep / d_keep_count (both or neither): the carried sequences [n_envs][n_elite][H][A] and their counts
+static int plan_sample_corr_impl(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                 uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                 const int32_t* d_keep_count, int32_t n_elite, double* d_actions, hipStream_t st) {
+    PlanSampleCorrArgs a{};
+    a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts; a.out = d_actions;
+    a.keep = d_keep; a.keep_count = d_keep_count;
+    a.seed = seed; a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
+    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim; a.n_elite = n_elite;
+    a.rho = rho; a.c = std::sqrt(1.0 - rho * rho);
+    HIP_TRY(launch_plan_sample_corr(a, st));
+    return BCMPC_OK;
+}
+
+static int plan_keep_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, const double* d_actions,
+                          int32_t n_envs, int64_t K, int64_t cand_offset, int32_t n_elite, double* d_keep,
+                          int32_t* d_keep_count, hipStream_t st) {
+    PlanKeepArgs a{};
+    a.elite = d_elite; a.count = d_count; a.actions = d_actions; a.keep = d_keep; a.keep_count = d_keep_count;
+    a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
+    a.n_envs = n_envs; a.n_elite = n_elite; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    HIP_TRY(launch_plan_keep(a, st));
     return BCMPC_OK;
 }
 
@@ -253,6 +292,35 @@ int bcmpc_plan_sample_async(bcmpc_engine* e, const double* d_mu, const double* d
     return plan_sample_impl(e, d_mu, d_sigma, n_envs, K, seed, iteration, cand_offset, d_actions, (hipStream_t)stream);
 }
 
+int bcmpc_plan_sample_corr_async(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                 uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                 const int32_t* d_keep_count, int32_t n_elite, double* d_actions, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_mu || !d_sigma || !d_actions) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = rho_check(rho)) return rc;
+    if ((d_keep != nullptr) != (d_keep_count != nullptr))
+        return fail(BCMPC_ERR_ARG, "d_keep and d_keep_count go together (both, or both NULL)");
+    if (d_keep && n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_sample_corr_impl(e, d_mu, d_sigma, n_envs, K, seed, iteration, cand_offset, rho, d_keep, d_keep_count,
+                                 n_elite, d_actions, (hipStream_t)stream);
+}
+
+int bcmpc_plan_keep_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, const double* d_actions,
+                          int32_t n_envs, int64_t K, int64_t cand_offset, int32_t n_elite, double* d_keep,
+                          int32_t* d_keep_count, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_elite || !d_count || !d_actions || !d_keep || !d_keep_count) return fail(BCMPC_ERR_ARG, "null argument");
+    if (n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_keep_impl(e, d_elite, d_count, d_actions, n_envs, K, cand_offset, n_elite, d_keep, d_keep_count,
+                          (hipStream_t)stream);
+}
+
 int bcmpc_plan_argmin_async(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs, int64_t K,
                             int32_t iteration, int32_t merge, bcmpc_result* d_results, void* stream) {
     // (arguments first: a bad call is answered before any HIP call)
@@ -327,12 +395,35 @@ static int plan_buffers(bcmpc_engine* e, int32_t n_envs, size_t n_elite_total) {
     return BCMPC_OK;
 }
 
+// ... and the carried elites' sequences of a CEM call with carry-over
+static int keep_buffers(bcmpc_engine* e, int32_t n_envs, int32_t n_elite) {
+    const size_t need = (size_t)n_envs * (size_t)n_elite * (size_t)e->cfg.horizon * (size_t)e->cfg.action_dim;
+    if (need > e->keep_cap) {
+        if (e->d_keep) (void)hipFree(e->d_keep);
+        e->d_keep = nullptr;
+        e->keep_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_keep, need * sizeof(double)));
+        e->keep_cap = need;
+    }
+    if (n_envs > e->keep_count_cap) {
+        if (e->d_keep_count) (void)hipFree(e->d_keep_count);
+        e->d_keep_count = nullptr;
+        e->keep_count_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_keep_count, (size_t)n_envs * sizeof(int32_t)));
+        e->keep_count_cap = n_envs;
+    }
+    return BCMPC_OK;
+}
+
 // The synchronous batched planner: states and plans up, tile_states once, then per iteration plan_sample ->
 // rollout (explicit actions, per-candidate states) -> plan_argmin -> the planner's update; records and
-// plans down, one stream synchronisation.  cem != nullptr: CEM, else MPPI (mp).
+// plans down, one stream synchronisation.  cem != nullptr: CEM, else MPPI (mp).  A non-default smp (checked by
+// the caller): plan_sample_corr instead of plan_sample, and with keep_elites plan_keep behind every refit that
+// another iteration follows -- iteration it >= 1 then starts with iteration it - 1's elites.
 static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* cem,
-                            const bcmpc_mppi* mp, uint64_t seed, int64_t cand_offset, double* mu, double* sigma_io,
-                            const double* sigma_in, bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out) {
+                            const bcmpc_mppi* mp, const bcmpc_sampling* smp, uint64_t seed, int64_t cand_offset,
+                            double* mu, double* sigma_io, const double* sigma_in, bcmpc_result* out,
+                            bcmpc_mppi_stats* stats, double* costs_out) {
     const bcmpc_config& c = e->cfg;
     const int32_t iterations = cem ? cem->iterations : mp->iterations;
     const int64_t K = c.num_paths / n_envs;
@@ -342,6 +433,9 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     if (const int rc = batch_buffers(e, n_envs)) return rc;
     if (const int rc = plan_buffers(e, n_envs, cem ? (size_t)n_envs * cem->n_elite : 0)) return rc;
     if (const int rc = actions_buffer(e)) return rc;
+    const bool corr = !sampling_default(smp), carry = corr && cem && smp->keep_elites && iterations > 1;
+    if (carry)
+        if (const int rc = keep_buffers(e, n_envs, cem->n_elite)) return rc;
     if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
     const double* sigma = cem ? sigma_io : sigma_in;
     const PlanInputs inputs(e->kernel == BCMPC_KERNEL_TEAM, mu, cem ? sigma_io : nullptr, nplan);
@@ -354,7 +448,13 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     t.states = e->d_bstates; t.out = e->d_tiled; t.K = K; t.Ktot = c.num_paths; t.S = c.state_dim;
     HIP_TRY(launch_tile_states(t, st));
     for (int it = 0; it < iterations; ++it) {
-        if (const int rc = plan_sample_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset, e->d_actions, st))
+        const bool kept = carry && it > 0;
+        if (const int rc = !corr ? plan_sample_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+                                                    e->d_actions, st)
+                                 : plan_sample_corr_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+                                                         smp->rho, kept ? e->d_keep : nullptr,
+                                                         kept ? e->d_keep_count : nullptr, cem ? cem->n_elite : 0,
+                                                         e->d_actions, st))
             return rc;
         RolloutLaunch r;
         r.state = e->d_tiled; r.state_stride = c.state_dim; r.actions = e->d_actions; r.seed = seed;
@@ -372,6 +472,10 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
                                         e->d_bsigma, e->d_actions, K, cand_offset, st)
                      : mppi_update_batch_impl(e, e->d_costs, n_envs, K, cand_offset, seed, it, mp->lambda, e->d_bmu,
                                               e->d_bsigma, e->d_bstats, e->d_actions, st);
+        // the elites' sequences out of the array, before the next iteration's sampling overwrites it
+        if (rc == BCMPC_OK && carry && it + 1 < iterations)
+            rc = plan_keep_impl(e, e->d_belite, e->d_bcount, e->d_actions, n_envs, K, cand_offset, cem->n_elite,
+                                e->d_keep, e->d_keep_count, st);
         if (rc != BCMPC_OK) return rc;
     }
     if (e->timing) {
@@ -387,37 +491,52 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     if (team_failed(e)) {                              // the whole call again, from the original plans
         if (const int fr = team_fallback(e)) return fr;
         inputs.restore(mu, sigma_io);
-        return plan_get_actions(e->fb, states, n_envs, cem, mp, seed, cand_offset, mu, sigma_io, sigma_in, out, stats,
-                                costs_out);
+        return plan_get_actions(e->fb, states, n_envs, cem, mp, smp, seed, cand_offset, mu, sigma_io, sigma_in, out,
+                                stats, costs_out);
     }
     std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
     return BCMPC_OK;
 }
 
-int bcmpc_cem_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
-                                uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
-                                double* costs_out) {
+int bcmpc_cem_get_actions_batch_s(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                                  const bcmpc_sampling* sampling, uint64_t seed, int64_t cand_offset, double* mu,
+                                  double* sigma, bcmpc_result* out, double* costs_out) {
     // (arguments first: a bad call is answered before any HIP call)
     if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
     if (!e || !states || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
     if (const int rc = cem_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, false)) return rc;
     if (const int rc = batch_check(e, n_envs)) return rc;
     if (const int rc = k_global_check(p->k_global, "batched CEM", e->cfg.num_paths / n_envs, "num_paths / n_envs")) return rc;
-    return plan_get_actions(e, states, n_envs, p, nullptr, seed, cand_offset, mu, sigma, nullptr, out, nullptr,
-                            costs_out);
+    return plan_get_actions(e, states, n_envs, p, nullptr, sampling, seed, cand_offset, mu, sigma, nullptr, out,
+                            nullptr, costs_out);
+}
+
+int bcmpc_cem_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                                uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                double* costs_out) {
+    return bcmpc_cem_get_actions_batch_s(e, states, n_envs, p, nullptr, seed, cand_offset, mu, sigma, out, costs_out);
+}
+
+int bcmpc_mppi_get_actions_batch_s(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                                   const bcmpc_sampling* sampling, uint64_t seed, int64_t cand_offset, double* mu,
+                                   const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    if (const int rc = k_global_check(p->k_global, "batched MPPI", e->cfg.num_paths / n_envs, "num_paths / n_envs")) return rc;
+    return plan_get_actions(e, states, n_envs, nullptr, p, sampling, seed, cand_offset, mu, nullptr, sigma, out,
+                            stats, costs_out);
 }
 
 int bcmpc_mppi_get_actions_batch(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
                                  uint64_t seed, int64_t cand_offset, double* mu, const double* sigma, bcmpc_result* out,
                                  bcmpc_mppi_stats* stats, double* costs_out) {
-    // (arguments first: a bad call is answered before any HIP call)
-    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
-    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
-    if (const int rc = mppi_param_check(p)) return rc;
-    if (const int rc = batch_check(e, n_envs)) return rc;
-    if (const int rc = k_global_check(p->k_global, "batched MPPI", e->cfg.num_paths / n_envs, "num_paths / n_envs")) return rc;
-    return plan_get_actions(e, states, n_envs, nullptr, p, seed, cand_offset, mu, nullptr, sigma, out, stats,
-                            costs_out);
+    return bcmpc_mppi_get_actions_batch_s(e, states, n_envs, p, nullptr, seed, cand_offset, mu, sigma, out, stats,
+                                          costs_out);
 }
 
 // ---- model ensembles: E member engines, one launch chain on member 0's stream -----------
@@ -757,6 +876,33 @@ int bcmpc_mppi_get_action(bcmpc_engine* e, const double* state, const bcmpc_mppi
                                            "(v_min, W, N) partials are not combined yet)");
     if (e->PL > 0) return fail(BCMPC_ERR_UNSUPPORTED, "MPPI runs on engines without a fused policy");
     return plan_chain(e, nullptr, state, nullptr, p, seed, mu, nullptr, sigma, out, stats);
+}
+
+// The single-plan calls with a sampling distribution: the default runs plan_chain as ever (the rollout kernels
+// sample white noise themselves); anything else is the batched chain with one environment at cand_offset 0,
+// whose answer at the default equals the single call's.
+int bcmpc_cem_get_action_s(bcmpc_engine* e, const double* state, const bcmpc_cem* p, const bcmpc_sampling* sampling,
+                           uint64_t seed, double* mu, double* sigma, bcmpc_result* out) {
+    if (sampling_default(sampling)) return bcmpc_cem_get_action(e, state, p, seed, mu, sigma, out);
+    if (!e || !state || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "CEM needs a fused objective");
+    if (const int rc = cem_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, false)) return rc;
+    if (const int rc = k_global_check(p->k_global, "single-device CEM", e->cfg.num_paths)) return rc;
+    if (const int rc = batch_check(e, 1)) return rc;
+    return plan_get_actions(e, state, 1, p, nullptr, sampling, seed, 0, mu, sigma, nullptr, out, nullptr, nullptr);
+}
+
+int bcmpc_mppi_get_action_s(bcmpc_engine* e, const double* state, const bcmpc_mppi* p, const bcmpc_sampling* sampling,
+                            uint64_t seed, double* mu, const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    if (sampling_default(sampling)) return bcmpc_mppi_get_action(e, state, p, seed, mu, sigma, out, stats);
+    if (!e || !state || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "MPPI needs a fused objective");
+    if (const int rc = k_global_check(p->k_global, "single-device MPPI", e->cfg.num_paths)) return rc;
+    if (const int rc = batch_check(e, 1)) return rc;
+    return plan_get_actions(e, state, 1, nullptr, p, sampling, seed, 0, mu, nullptr, sigma, out, stats, nullptr);
 }
 
 int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, uint64_t seed,

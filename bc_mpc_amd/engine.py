@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from . import sampling as _sampling
 
 _ACT = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
 
@@ -195,6 +196,7 @@ class _EngineCalls:
     and the single-plan CEM / MPPI calls, which differ between the two only in the C entry point (``_CEM`` /
     ``_MPPI``).  The class provides ``_lib``, ``_h``, ``state_dim``, ``action_dim``, ``horizon``, ``num_paths``."""
     _CEM, _MPPI = "bcmpc_cem_get_action", "bcmpc_mppi_get_action"
+    _CEM_S, _MPPI_S = "bcmpc_cem_get_action_s", "bcmpc_mppi_get_action_s"     # (None: no such entry)
 
     def _fresh(self) -> None:
         """The wrapper's host state for a handle nothing has been set on yet."""
@@ -224,43 +226,70 @@ class _EngineCalls:
                              f"{(self.horizon, self.num_paths, self.action_dim)}")
         return actions, _dp(actions)
 
+    def _sampling(self, rho, keep_elites=False):
+        """The ``_lib.Sampling`` of a planner call's ``rho`` / ``keep_elites`` (sampling.py), or None at the
+        defaults: the call then goes to the entry point it has always gone to."""
+        rho, keep = _sampling.check_rho(rho), _sampling.check_keep_elites(keep_elites)
+        return _lib.Sampling(rho, int(keep), 0) if rho != 0.0 or keep else None
+
     def _step_result(self, res, costs=None) -> StepResult:
         return StepResult(int(res.best_index), float(res.best_cost),
                           np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
 
     # ------------------------------------------------------------------ CEM / MPPI, one plan
+    def _s_entry(self, name: Optional[str], what: str):
+        if name is None:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: correlated noise and elite carry-over are "
+                                      "not built for ensembles")
+        return getattr(self._lib, name)
+
     def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
-                       seed: int) -> Tuple[StepResult, np.ndarray, np.ndarray]:
+                       seed: int, rho: float = 0.0, keep_elites: bool = False
+                       ) -> Tuple[StepResult, np.ndarray, np.ndarray]:
         """All CEM iterations on this device (bcmpc_cem_get_action; an ensemble: bcmpc_ensemble_cem_get_action,
         the elites of every iteration chosen by the combined value).  ``mu``/``sigma`` are ``[H, A]``; returns
-        (result with best_index = iteration*K + candidate, mu', sigma')."""
+        (result with best_index = iteration*K + candidate, mu', sigma').  ``rho`` / ``keep_elites``:
+        temporally correlated noise and elite carry-over (sampling.py; bcmpc_cem_get_action_s)."""
+        smp = self._sampling(rho, keep_elites)
         st = self._state(state)
         shape = (self.horizon, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = _lib.Result()
-        _lib.check(getattr(self._lib, self._CEM)(self._h, _dp(st), ctypes.byref(p),
-                                                 ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                 ctypes.byref(res)))
+        if smp is None:
+            _lib.check(getattr(self._lib, self._CEM)(self._h, _dp(st), ctypes.byref(p),
+                                                     ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
+                                                     ctypes.byref(res)))
+        else:
+            _lib.check(self._s_entry(self._CEM_S, "cem_get_action")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp), ctypes.c_uint64(seed & (2**64 - 1)), _dp(m),
+                _dp(s), ctypes.byref(res)))
         return self._step_result(res), m, s
 
     def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
-                        seed: int) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
+                        seed: int, rho: float = 0.0) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
         """``iterations`` rounds of CEM-style rollout + MPPI update on this device (bcmpc_mppi_get_action; an
         ensemble: bcmpc_ensemble_mppi_get_action, the softmin weights from the combined value; DESIGN.md "MPPI").
         ``mu``/``sigma`` are ``[H, A]``; returns (the best single candidate over all rounds, best_index =
         iteration*K + candidate; the updated plan mu', whose row 0 is the action to apply; the last round's
-        statistics).  sigma is not modified."""
+        statistics).  sigma is not modified.  ``rho``: temporally correlated noise (sampling.py;
+        bcmpc_mppi_get_action_s)."""
+        smp = self._sampling(rho)
         st = self._state(state)
         shape = (self.horizon, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res, stats = _lib.Result(), _lib.MppiStats()
-        _lib.check(getattr(self._lib, self._MPPI)(self._h, _dp(st), ctypes.byref(p),
-                                                  ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
-                                                  ctypes.byref(res), ctypes.byref(stats)))
+        if smp is None:
+            _lib.check(getattr(self._lib, self._MPPI)(self._h, _dp(st), ctypes.byref(p),
+                                                      ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
+                                                      ctypes.byref(res), ctypes.byref(stats)))
+        else:
+            _lib.check(self._s_entry(self._MPPI_S, "mppi_get_action")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp), ctypes.c_uint64(seed & (2**64 - 1)), _dp(m),
+                _dp(s), ctypes.byref(res), ctypes.byref(stats)))
         return self._step_result(res), m, stats
 
 
@@ -835,37 +864,52 @@ class RolloutEngine(_EngineCalls):
                            costs.reshape(iterations, B, -1) if costs is not None else None)
 
     def cem_get_actions(self, states, mu, sigma, iterations: int, n_elite: int, alpha: float, seed: int,
-                        cand_offset: int = 0, return_costs: bool = False
-                        ) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+                        cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0,
+                        keep_elites: bool = False) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
         """Batched CEM (bcmpc_cem_get_actions_batch): ``states`` ``[B, S]``, ``mu`` / ``sigma``
         ``[B, H, A]``, ``K = num_paths // B`` candidates and ``n_elite`` elites per environment, columns
         as for get_actions.  Returns (records with ``best_index = iteration*K + candidate`` per
-        environment and ``costs`` ``[iterations, B, K]`` when asked for, mu' ``[B, H, A]``, sigma')."""
+        environment and ``costs`` ``[iterations, B, K]`` when asked for, mu' ``[B, H, A]``, sigma').
+        ``rho`` / ``keep_elites``: temporally correlated noise and elite carry-over (sampling.py;
+        bcmpc_cem_get_actions_batch_s)."""
+        smp = self._sampling(rho, keep_elites)
         st, B, m, s = self._plan_batch_args(states, mu, sigma, True)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = (_lib.Result * B)()
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
-        _lib.check(self._lib.bcmpc_cem_get_actions_batch(
-            self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
-            ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, _dp(costs) if costs is not None else None))
+        if smp is None:
+            _lib.check(self._lib.bcmpc_cem_get_actions_batch(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
+                ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, _dp(costs) if costs is not None else None))
+        else:
+            _lib.check(self._lib.bcmpc_cem_get_actions_batch_s(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp),
+                ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s), res,
+                _dp(costs) if costs is not None else None))
         return self._batch_result(res, B, costs, int(iterations)), m, s
 
     def mppi_get_actions(self, states, mu, sigma, iterations: int, temperature: float, seed: int,
-                         cand_offset: int = 0, return_costs: bool = False
+                         cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0
                          ) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
         """Batched MPPI (bcmpc_mppi_get_actions_batch): as cem_get_actions, with the softmin update of
         mppi_get_action per environment.  Returns (records, mu' ``[B, H, A]`` whose rows ``[b, 0]`` are the
         actions to apply, the last round's statistics as a ``[B]`` array of MPPI_STATS).  sigma is not
-        modified."""
+        modified.  ``rho``: temporally correlated noise (sampling.py; bcmpc_mppi_get_actions_batch_s)."""
+        smp = self._sampling(rho)
         st, B, m, s = self._plan_batch_args(states, mu, sigma, False)
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res = (_lib.Result * B)()
         stats = np.zeros(B, dtype=MPPI_STATS)
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
-        _lib.check(self._lib.bcmpc_mppi_get_actions_batch(
-            self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
-            ctypes.c_int64(cand_offset), _dp(m), _dp(s), res,
-            stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None))
+        d_stats, d_costs = stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None
+        if smp is None:
+            _lib.check(self._lib.bcmpc_mppi_get_actions_batch(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
+                ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, d_stats, d_costs))
+        else:
+            _lib.check(self._lib.bcmpc_mppi_get_actions_batch_s(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp),
+                ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, d_stats, d_costs))
         return self._batch_result(res, B, costs, int(iterations)), m, stats
 
     def plan_sample_async(self, d_mu: int, d_sigma: int, n_envs: int, K: int, seed: int, iteration: int,
@@ -877,6 +921,32 @@ class RolloutEngine(_EngineCalls):
         _lib.check(self._lib.bcmpc_plan_sample_async(
             self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
             int(iteration), int(cand_offset), vp(d_actions), ctypes.c_void_p(stream)))
+
+    def plan_sample_corr_async(self, d_mu: int, d_sigma: int, n_envs: int, K: int, seed: int, iteration: int,
+                               cand_offset: int, rho: float, d_actions: int, d_keep: Optional[int] = None,
+                               d_keep_count: Optional[int] = None, n_elite: int = 0,
+                               stream: Optional[int] = None) -> None:
+        """bcmpc_plan_sample_corr_async: plan_sample_async with AR(1) noise of coefficient ``rho``
+        (sampling.correlated_actions).  ``d_keep`` ``[n_envs, n_elite, H, A]`` f64 and ``d_keep_count``
+        ``[n_envs]`` i32: environment b's first ``d_keep_count[b]`` columns are copies of ``d_keep[b]``
+        (sampling.carry_elites)."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_sample_corr_async(
+            self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), int(cand_offset), float(rho), vp(d_keep), vp(d_keep_count), int(n_elite),
+            vp(d_actions), ctypes.c_void_p(stream)))
+
+    def plan_keep_async(self, d_elite: int, d_count: int, d_actions: int, n_envs: int, K: int, cand_offset: int,
+                        n_elite: int, d_keep: int, d_keep_count: int, stream: Optional[int] = None) -> None:
+        """bcmpc_plan_keep_async: the sequences of the elites ``d_elite`` ``[n_envs, n_elite]`` / ``d_count``
+        out of ``d_actions`` ``[H, n_envs*K, A]`` into ``d_keep`` ``[n_envs, n_elite, H, A]``; ``d_keep_count``
+        ``[n_envs]`` receives the number of leading records copied."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_keep_async(
+            self._h, vp(d_elite), vp(d_count), vp(d_actions), int(n_envs), int(K), int(cand_offset), int(n_elite),
+            vp(d_keep), vp(d_keep_count), ctypes.c_void_p(stream)))
 
     def plan_argmin_async(self, d_costs: int, d_actions: int, n_envs: int, K: int, iteration: int, merge: bool,
                           d_results: int, stream: Optional[int] = None) -> None:

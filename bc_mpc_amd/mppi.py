@@ -36,7 +36,9 @@ class MPPIcontroller(Planner):
     """MPPI on the MI355X engine: softmin-weighted plan update over all sampled candidates.  ``get_action`` /
     ``get_actions`` return the first step of the updated plan, ``mu'[0]``; ``last_mu`` holds the plan,
     ``last_cost`` / ``last_position`` the best single sample, ``last_ess`` / ``last_stats`` the last round's
-    statistics (batched: ``[B, H, A]``, ``[B]``, and ``last_stats`` a ``[B]`` record array)."""
+    statistics (batched: ``[B, H, A]``, ``[B]``, and ``last_stats`` a ``[B]`` record array).  ``noise_rho`` in
+    ``[0, 1)``: AR(1) noise over the horizon instead of independent draws (sampling.py; read on
+    every call, one rank and one dynamics model only)."""
     _KIND = "MPPI"
 
     def __init__(self,
@@ -55,10 +57,11 @@ class MPPIcontroller(Planner):
                  device: Optional[int] = None,
                  process_group=None,
                  terminal_value=None,
-                 terminal_weight: float = -1.0):
+                 terminal_weight: float = -1.0,
+                 noise_rho: float = 0.0):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0x3B9AC1 if seed is None else seed, device, process_group,
-                         terminal_value=terminal_value, terminal_weight=terminal_weight)
+                         terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho)
         if not (math.isfinite(temperature) and temperature > 0):
             raise ValueError("temperature must be finite and > 0")
         self.temperature = float(temperature)
@@ -70,7 +73,8 @@ class MPPIcontroller(Planner):
                                   "(v_min, W, N) partials of the weighted mean is not built yet")
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
-        res, mu, stats = eng.mppi_get_action(state, mu0, sd0, self.iterations, self.temperature, seed)
+        res, mu, stats = eng.mppi_get_action(state, mu0, sd0, self.iterations, self.temperature, seed,
+                                             **self._sampling_args())
         self._note_planner_value(eng, res.best_index, K)
         self._mu = mu
         self.last_mu = mu
@@ -79,7 +83,8 @@ class MPPIcontroller(Planner):
         return mu[0].copy()
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
-        res, mu, stats = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed)
+        res, mu, stats = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed,
+                                              **self._sampling_args())
         self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu = mu

@@ -627,6 +627,65 @@ int bcmpc_mppi_update_batch_async(bcmpc_engine* eng, const double* d_costs, int3
                                   void* stream);
 
 /* ------------------------------------------------------------------------
+ * The planners' sampling distribution (additive to ABI 5; callers detect it by the symbol
+ * bcmpc_cem_get_action_s; semantics in DESIGN.md 9j, defined bit for bit by bc_mpc_amd/sampling.py).
+ *   rho          temporally correlated noise: candidate g's action (h, j) of an iteration is
+ *                clip(mu[h][j] + sigma[h][j] * n[h]) with n[0] = z[0], n[h] = rho * n[h-1] + c * z[h],
+ *                c = sqrt(1 - rho * rho) (f64, rounded once), z[h] the independent normal the planners draw
+ *                at (seed, g, h, j, iteration); every product and sum an individually rounded f64 operation.
+ *                The variance of n[h] is 1 for every h.  0 <= rho < 1; rho == 0: the independent draw.
+ *   keep_elites  (CEM) iteration it >= 1 of an environment starts with ALL elites of iteration it - 1: its
+ *                candidate column j < count is the sequence of the j-th elite (select's order: ascending
+ *                index), columns j >= count are sampled as ever at their own Philox index.  The best
+ *                sequence of an iteration therefore survives, and the per-iteration minimum does not rise.
+ *                Nothing is carried from one call to the next.
+ * A NULL pointer or {0, 0, 0} is the default and runs exactly what the calls without _s run.  Anything else
+ * runs the batched chain (n_envs = 1, cand_offset = 0 for the single calls): plan_sample_corr instead of
+ * plan_sample and, with keep_elites, plan_keep behind every refit that another iteration follows.
+ * BCMPC_ERR_ARG (before any HIP call): rho not finite or outside [0, 1), keep_elites not 0 / 1, keep_elites on
+ * an MPPI call, and what the calls without _s refuse.  BCMPC_ERR_UNSUPPORTED: a communicator attached, a fused
+ * policy.  Ensembles have no _s entry. */
+typedef struct bcmpc_sampling {
+    double rho;
+    int32_t keep_elites;
+    int32_t reserved;
+} bcmpc_sampling;
+
+int bcmpc_cem_get_action_s(bcmpc_engine* eng, const double* state, const bcmpc_cem* params,
+                           const bcmpc_sampling* sampling, uint64_t seed, double* mu, double* sigma,
+                           bcmpc_result* out);
+int bcmpc_mppi_get_action_s(bcmpc_engine* eng, const double* state, const bcmpc_mppi* params,
+                            const bcmpc_sampling* sampling, uint64_t seed, double* mu, const double* sigma,
+                            bcmpc_result* out, bcmpc_mppi_stats* stats);
+int bcmpc_cem_get_actions_batch_s(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_cem* params,
+                                  const bcmpc_sampling* sampling, uint64_t seed, int64_t cand_offset, double* mu,
+                                  double* sigma, bcmpc_result* out, double* costs_out);
+int bcmpc_mppi_get_actions_batch_s(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_mppi* params,
+                                   const bcmpc_sampling* sampling, uint64_t seed, int64_t cand_offset, double* mu,
+                                   const double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats,
+                                   double* costs_out);
+
+/* Their building blocks (device pointers, stream-ordered, as bcmpc_plan_sample_async and its siblings).
+ *   plan_sample_corr  bcmpc_plan_sample_async with the correlated noise above.  d_keep [n_envs][n_elite][H][A]
+ *                and d_keep_count [n_envs] (both, or both NULL; n_elite is d_keep's stride and unused without
+ *                it): environment b's first min(d_keep_count[b], n_elite) columns are copied from d_keep[b]
+ *                and draw nothing.
+ *   plan_keep    d_keep[b][e][h][j] = d_actions[h][d_elite[b][e].index - cand_offset][j] for e < d_count[b]
+ *                (d_elite [n_envs][n_elite], d_count [n_envs]: bcmpc_select_batch_async's output on the costs of
+ *                d_actions, [H][n_envs * K][A]).  A record with index < 0 or a column outside environment b's
+ *                own K columns is not copied; d_keep_count[b] counts the leading records that were.  It runs
+ *                after the refit and before the next sampling overwrites d_actions.
+ * With correlated noise or carried elites, bcmpc_cem_refit_batch_async and bcmpc_mppi_update_batch_async MUST
+ * be given d_actions: their Philox fallback regenerates the independent draw, not what was rolled out. */
+int bcmpc_plan_sample_corr_async(bcmpc_engine* eng, const double* d_mu, const double* d_sigma, int32_t n_envs,
+                                 int64_t K, uint64_t seed, int32_t iteration, int64_t cand_offset, double rho,
+                                 const double* d_keep, const int32_t* d_keep_count, int32_t n_elite,
+                                 double* d_actions, void* stream);
+int bcmpc_plan_keep_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const int32_t* d_count,
+                          const double* d_actions, int32_t n_envs, int64_t K, int64_t cand_offset, int32_t n_elite,
+                          double* d_keep, int32_t* d_keep_count, void* stream);
+
+/* ------------------------------------------------------------------------
  * Model ensembles (additive to ABI 5; callers detect them by the symbol bcmpc_ensemble_create; not in
  * the reference, semantics in DESIGN.md 9g).  An ensemble holds E dynamics nets of one architecture and
  * one configuration -- E member engines of the same config, hence the same kernel layout.  Candidate k
