@@ -6,7 +6,7 @@ SRC      := bc_mpc_amd/csrc
 LIB      := bc_mpc_amd/libbcmpc.so
 # objects by how they compile: host units that see the kernels' launch headers (hipcc -x hip), plain C++ (g++),
 # every other one a kernel unit (.hip); OBJ in link order
-HOSTOBJ  := capi mt_draw planners
+HOSTOBJ  := capi engine_plan pack mt_draw planners
 CXXOBJ   := mt19937 mt_jump
 OBJ      := $(patsubst %,build/%.o,rollout rollout_grp rollout_x3 rollout_x3_plain rollout_pp rollout_team cem mppi batch \
               plan_batch plan_noise term_cost terminal_value ensemble fit $(HOSTOBJ) $(CXXOBJ) mt_device comm)

@@ -1,5 +1,6 @@
-// capi.cpp -- C ABI of libbcmpc (include/bcmpc.h): engine lifetime and kernel selection, weight packing into
-// MFMA fragment order, the rollout launch, the plain control steps, introspection (mt_draw.cpp, planners.cpp: the rest)
+// capi.cpp -- C ABI of libbcmpc (include/bcmpc.h): engine lifetime, the setters' uploads, the rollout launch, team
+// ordering and fallback, the plain control steps, introspection (engine_plan.cpp: the checks and the kernel choice;
+// pack.cpp: weight packing; mt_draw.cpp, planners.cpp: the rest)
 #include "host_internal.h"
 
 using namespace bcmpc::host;
@@ -7,94 +8,6 @@ using namespace bcmpc::host;
 namespace {
 
 thread_local std::string g_last_error;
-
-int kern_waves(int kern) {
-    return kern == BCMPC_KERNEL_GROUP8 ? 8 : kern == BCMPC_KERNEL_GROUP4 ? 4 : 1;
-}
-
-int padded_hidden(int h) {
-    for (int hp : {64, 128, 256, 512, 768, 1024})
-        if (h <= hp) return hp;
-    return -1;
-}
-
-// Dense kernel W [in][out] (tf.layers.dense layout) -> fragment order
-// [tb][u][j][lane][r], t = tb*TB + j: element W[16u + 4(lane>>4) + r][16t + (lane&15)]
-// (zero outside in x out).  See the layout note at the top of rollout.hip.
-void pack_layer(const float* W, int in, int out, int Tin, int Tout, int TB, float* dst) {
-    for (int t = 0; t < Tout; ++t) {
-        const int tb = t / TB, j = t % TB;
-        for (int u = 0; u < Tin; ++u)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int k = 16 * u + 4 * (lane >> 4) + r;
-                    const int n = 16 * t + (lane & 15);
-                    const size_t o = ((((size_t)tb * Tin + u) * TB + j) * 64 + lane) * 4 + r;
-                    dst[o] = (k < in && n < out) ? W[(size_t)k * out + n] : 0.f;
-                }
-    }
-}
-
-// Output layer of the policy: one 16-row output tile whose row n holds action
-// rowmap[n] (or zero): the host places action j at row S-16+j, i.e. in exactly
-// the lanes/registers where the dynamics' layer-0 input expects action j.
-void pack_out_rows(const float* W, int in, int out, int Tin, const int* rowmap, float* dst) {
-    for (int u = 0; u < Tin; ++u)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int r = 0; r < 4; ++r) {
-                const int k = 16 * u + 4 * (lane >> 4) + r;
-                const int c = rowmap[lane & 15];
-                const size_t o = (((size_t)u * 64) + lane) * 4 + r;
-                dst[o] = (k < in && c >= 0 && c < out) ? W[(size_t)k * out + c] : 0.f;
-            }
-}
-
-// Split-f16 kernel (rollout_x3.h): W [in][out] scaled by sw, every element as
-// hi = f16(w), lo = f16(w - hi), in fragment order [ws][p][j][hi|lo][lane][i],
-// t = ws*TWp + j: lane's 8 halves of tile t, k-step p are W[k][n] with
-// n = 16t + (lane&15), k = 32p + 16(i>>2) + 4(lane>>4) + (i&3) -- the k order in
-// which an output tile pair's accumulators ARE the next layer's B fragment.
-void pack_x3_layer(const float* W, int in, int out, int Pin, int Tout, int TWp, float sw, _Float16* dst) {
-    for (int t = 0; t < Tout; ++t) {
-        const int ws = t / TWp, j = t % TWp;
-        for (int p = 0; p < Pin; ++p)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 8; ++i) {
-                    const int k = 32 * p + 16 * (i >> 2) + 4 * (lane >> 4) + (i & 3);
-                    const int n = 16 * t + (lane & 15);
-                    const float v = (k < in && n < out) ? W[(size_t)k * out + n] * sw : 0.f;
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    const size_t o = ((((size_t)ws * Pin + p) * TWp + j) * 2 * 64 + lane) * 8 + i;
-                    dst[o] = hi;
-                    dst[o + 64 * 8] = lo;
-                }
-    }
-}
-
-// power of two s with max|W| * s in [2^11, 2^12) (1 for an all-zero kernel)
-float x3_scale(const float* W, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(W[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
-    int e = 0;
-    (void)std::frexp(mx, &e);
-    return std::ldexp(1.0f, std::max(-100, std::min(100, 12 - e)));
-}
-
-// the scale of a LayerNorm output as the next layer's f16 operand: |LN(x)_i| <= sqrt(h) |gamma_i| + |beta_i|,
-// and the power of two that keeps it below 2^12
-float ln_out_scale(const float* gamma, const float* beta, int h) {
-    float gm = 0.f, bm = 0.f;
-    for (int i = 0; i < h; ++i) {
-        gm = std::max(gm, std::fabs(gamma[i]));
-        bm = std::max(bm, std::fabs(beta[i]));
-    }
-    const float bound = std::sqrt((float)h) * gm + bm;
-    int ex = 0;
-    if (bound > 0.f && std::isfinite(bound)) (void)std::frexp(bound, &ex);
-    return std::ldexp(1.0f, std::max(-100, std::min(100, 12 - ex)));
-}
 
 }  // namespace
 
@@ -130,18 +43,6 @@ void announce_test_hook(const char* name, const char* value) {
 }
 }  // namespace bcmpc
 
-// BCMPC_SPLIT_PP: 1 forces the two-group pipelined split kernel (rollout_pp3) at any K, 0 turns it off, unset
-// leaves the choice to kernel="auto" (kSplitPpAutoCols candidate columns and more, horizon >= kSplitPpAutoMinH)
-// (the A/B that places the column threshold.  The horizon: the two-group pipeline runs 2H + 2
-//  barrier intervals for 2H segments of work, each interval 0.90 of a rollout_x3 step per 128 candidates at
-//  cfg3, so it breaks even at H = 10 and clears 3% from H = 14)
-constexpr int64_t kSplitPpAutoCols = 2048;
-constexpr int kSplitPpAutoMinH = 14;
-static int split_pp_env() {
-    const char* v = std::getenv("BCMPC_SPLIT_PP");
-    return !(v && *v) ? -1 : v[0] == '1' ? 1 : 0;
-}
-
 // (team launch ordering across streams: team_order_before / team_order_after below)
 struct TeamOrder {
     std::mutex mu;
@@ -155,284 +56,23 @@ int bcmpc::host::create_engine(const bcmpc_config* cfg, const CreateOpts& opts, 
     if (!cfg || !out) return fail(BCMPC_ERR_ARG, "null argument");
     *out = nullptr;
     const bcmpc_config& c = *cfg;
-    if (c.state_dim < 1 || c.state_dim > BCMPC_MAX_STATE) return fail(BCMPC_ERR_UNSUPPORTED, "state_dim must be in [1, 32]");
-    if (c.action_dim < 1 || c.action_dim > BCMPC_MAX_ACTION) return fail(BCMPC_ERR_UNSUPPORTED, "action_dim must be in [1, 16]");
-    if (c.state_dim + c.action_dim > BCMPC_MAX_INPUT) return fail(BCMPC_ERR_UNSUPPORTED, "state_dim + action_dim must be <= 32");
-    if (c.n_layers < 1 || c.n_layers > BCMPC_MAX_LAYERS) return fail(BCMPC_ERR_UNSUPPORTED, "n_layers must be in [1, 8]");
-    if (padded_hidden(c.hidden) < 0 || c.hidden < 1) return fail(BCMPC_ERR_UNSUPPORTED, "hidden must be in [1, 1024] in this build");
-    if (c.activation != BCMPC_ACT_TANH && c.activation != BCMPC_ACT_RELU) return fail(BCMPC_ERR_UNSUPPORTED, "activation must be tanh or relu");
-    if (c.horizon < 1) return fail(BCMPC_ERR_ARG, "horizon must be >= 1");
-    if (c.num_paths < 0) return fail(BCMPC_ERR_ARG, "num_paths must be >= 0");
-    if (c.cost != BCMPC_COST_CHEETAH && c.cost != BCMPC_COST_NONE && c.cost != BCMPC_COST_REWARD &&
-        c.cost != BCMPC_COST_TERMS)
-        return fail(BCMPC_ERR_UNSUPPORTED, "unknown cost");
-    if (c.model != BCMPC_MODEL_DELTA && c.model != BCMPC_MODEL_REWARD) return fail(BCMPC_ERR_ARG, "unknown model");
-    const bool reward = c.model == BCMPC_MODEL_REWARD;
-    if ((c.cost == BCMPC_COST_REWARD) != reward)
-        return fail(BCMPC_ERR_ARG, "the learned-reward objective and BCMPC_MODEL_REWARD go together "
-                                   "(MPCcontrollerReward needs NNDynamicsRewardModel, controllers.py:137)");
-    if (reward) {
-        if (c.n_layers != 2) return fail(BCMPC_ERR_ARG, "reward model: n_layers must be 2 (trunk + head, dynamics.py:167-174)");
-        if (c.activation != BCMPC_ACT_TANH) return fail(BCMPC_ERR_UNSUPPORTED, "reward model is tanh (dynamics.py:150)");
-        if (c.hidden > 512) return fail(BCMPC_ERR_UNSUPPORTED, "reward model: hidden must be <= 512 in this build");
-        if (c.state_dim > 31) return fail(BCMPC_ERR_UNSUPPORTED, "reward model: state_dim must be <= 31");
-    }
-    if (c.cost == BCMPC_COST_CHEETAH && c.state_dim < 18) return fail(BCMPC_ERR_UNSUPPORTED, "cheetah cost needs state_dim >= 18");
-    if (c.cost == BCMPC_COST_TERMS && c.policy_hidden > 0)
-        return fail(BCMPC_ERR_UNSUPPORTED, "cost terms: engines with a fused policy need their fused cost");
-    if (c.precision != BCMPC_PREC_FP32 && c.precision != BCMPC_PREC_SPLIT_F16 && c.precision != BCMPC_PREC_F16)
-        return fail(BCMPC_ERR_UNSUPPORTED, "precision must be FP32, SPLIT_F16 or F16");
-    // single-pass f16 (BASELINE cfg3's bf16-class GEMM): the split slab kernels' plain tanh delta net only
-    const bool f16 = c.precision == BCMPC_PREC_F16;
-    if (f16 && (reward || c.policy_hidden > 0 || c.activation != BCMPC_ACT_TANH || c.layer_norm))
-        return fail(BCMPC_ERR_UNSUPPORTED, "F16 precision: the tanh NNDynamicsModel without LayerNorm / policy only");
-    if (f16 && c.kernel != BCMPC_KERNEL_AUTO && (c.kernel < BCMPC_KERNEL_SPLIT1 || c.kernel > BCMPC_KERNEL_SPLIT4))
-        return fail(BCMPC_ERR_ARG, "F16 precision runs on the split1/split2/split4 kernels");
-    const bool split = c.precision != BCMPC_PREC_FP32;
-    // relu / LayerNorm hidden layers (per-column scales or statistics exchanged across the workgroup)
-    // on the split slab kernels: the plain delta net without a policy, hidden <= 512; beyond that only
-    // the small-K team kernel takes them (checked once the kernel is chosen, below)
-    const bool split_needs_team = split && (c.activation != BCMPC_ACT_TANH || c.layer_norm) &&
-                                  (reward || c.policy_hidden > 0 || padded_hidden(c.hidden) > 512);
-    if (split) {
-        if (reward && c.state_dim < 16)
-            return fail(BCMPC_ERR_UNSUPPORTED, "split reward engines need state_dim >= 16 (reward row in tile 1)");
-        if (c.kernel != BCMPC_KERNEL_AUTO && (c.kernel < BCMPC_KERNEL_SPLIT1 || c.kernel > BCMPC_KERNEL_TEAM))
-            return fail(BCMPC_ERR_ARG, "SPLIT_F16 precision runs on the split1/split2/split4/team kernels");
-        if (c.kernel == BCMPC_KERNEL_SPLITR)
-            return fail(BCMPC_ERR_UNSUPPORTED, "the splitr (resident-column) kernel was retired: slower than the "
-                                               "split slab kernel at every K (DESIGN.md 6.5); use auto or split4");
-    } else if (c.kernel >= BCMPC_KERNEL_SPLIT1) {
-        return fail(BCMPC_ERR_ARG, "split kernels need precision SPLIT_F16");
-    }
-    if (c.kernel == BCMPC_KERNEL_GROUP2)
-        return fail(BCMPC_ERR_UNSUPPORTED, "the group2 layout (2-wave f32 groups, A/B only, never chosen by auto) "
-                                           "was retired; use auto, group4 or group8");
+    if (const int rc = check_config(c)) return rc;      // (the config's own refusals come before any HIP call)
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (c.device < 0 || c.device >= ndev) return fail(BCMPC_ERR_ARG, "device ordinal out of range");
     HIP_TRY(hipSetDevice(c.device));
-
-    bcmpc_engine* e = new bcmpc_engine();
-    e->cfg = c;
-    e->reward = reward;
-    e->f16 = f16;
-    e->HP = reward ? std::max(128, padded_hidden(c.hidden)) : padded_hidden(c.hidden);
-    e->T = e->HP / 16;
-    // small K: one wave per block spreads candidates over more CUs
-    const int64_t waves = (c.num_paths + 15) / 16;
-    e->wpb = std::min(waves >= 4 * 256 ? 4 : 1, max_waves_per_block(e->HP, c.n_layers));
-    // auto: 4-wave groups; 8-wave groups when K is too small to give every SIMD two waves
-    int kern = c.kernel != BCMPC_KERNEL_AUTO ? c.kernel
-             : ((c.num_paths + 15) / 16 < 512 && e->T % 8 == 0 ? BCMPC_KERNEL_GROUP8 : BCMPC_KERNEL_GROUP4);
-    if (reward) {
-        // two-head net: 4-wave groups (16 head tiles per wave, spill-free at 2 waves/SIMD; the
-        // 8-wave layout needs ~135 registers and spills at 4 waves/SIMD -- measured 2.5% slower)
-        if (!split && c.kernel != BCMPC_KERNEL_AUTO && c.kernel != BCMPC_KERNEL_GROUP4 &&
-            c.kernel != BCMPC_KERNEL_GROUP8)
-            { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "reward engines run on the group4 / group8 kernels"); }
-        if (c.kernel == BCMPC_KERNEL_AUTO) kern = BCMPC_KERNEL_GROUP4;
-    }
-    if (c.policy_hidden > 0) {
-        // MPCcontrollerPolicyNet: the policy MLP is fused into the 4-wave group kernel
-        if (c.policy_hidden > 128 || c.policy_layers < 1 || c.policy_layers > BCMPC_MAX_LAYERS)
-            { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "policy: hidden must be in [1,128], layers in [1,8]"); }
-        if (c.state_dim < 16) { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "policy engines need state_dim >= 16"); }
-        if (e->HP < 128 || e->HP > (split ? 1024 : 512))
-            { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "policy engines support dynamics hidden 65..512 (split: ..1024)"); }
-        if (c.policy_mode != BCMPC_POLICY_EXPLORE && c.policy_mode != BCMPC_POLICY_STOCHASTIC)
-            { delete e; return fail(BCMPC_ERR_ARG, "unknown policy_mode"); }
-        if (!split && c.kernel != BCMPC_KERNEL_AUTO && c.kernel != BCMPC_KERNEL_GROUP4 &&
-            c.kernel != BCMPC_KERNEL_GROUP8)
-            { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "policy engines run on the group4 / group8 kernels"); }
-        if (c.kernel == BCMPC_KERNEL_AUTO) kern = BCMPC_KERNEL_GROUP4;
-        e->PHP = 128;
-        e->TP = 8;
-        e->PL = c.policy_layers;
-    }
-    // small-K team kernel (rollout_team.hip): the 2-layer delta net at hidden <= 512 (LayerNorm: <=
-    // 256), or at hidden 512 (tanh) with a fused policy of <= 2 layers and / or the reward net (the
-    // run.sh recipe), when the whole grid fits one workgroup per CU (the team members of a column wait
-    // for each other).  Auto: whenever it fits, unless BCMPC_TEAM=0
     int ncu = 0;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device);
+    EnginePlan plan;
+    if (const int rc = plan_engine(c, opts, ncu, &plan)) return rc;
+
+    bcmpc_engine* e = new bcmpc_engine(plan);
     e->ncu = ncu;
-    const int tkind = reward ? 2 : e->PL > 0 ? 1 : 0;
-    const int tmem = team_members(e->HP, tkind);
-    // (a LayerNorm over a layer split across members: only the reward net's heads, whose statistics
-    //  ride along with the output partials in the exchange -- rows 24..27, so S + 1 <= 24)
-    const bool team_shape = split && !f16 && c.n_layers == 2 && e->HP <= 512 && c.state_dim + c.action_dim <= 32 &&
-                            c.action_dim <= 15 && c.horizon <= 1022 && tmem > 0 &&
-                            !(c.layer_norm && tmem > 1 && tkind != 2) &&
-                            (tkind == 0 || (c.state_dim >= 16 && e->PL <= 2 &&
-                                            (tmem == 1 || c.activation == BCMPC_ACT_TANH))) &&
-                            !(tkind == 2 && c.layer_norm && (c.state_dim > 23 || !team_rw_ln_built()));
-    const bool team_fits = team_shape && c.num_paths > 0 && team_blocks(c.num_paths, e->HP, tkind) <= (int64_t)ncu;
-    bool use_team = c.kernel == BCMPC_KERNEL_TEAM;
-    if (use_team && !team_fits) {
-        delete e;
-        return fail(BCMPC_ERR_UNSUPPORTED, "team kernel: 2-layer net, hidden <= 512 (LayerNorm: <= 256; with a "
-                                           "policy: hidden <= 256, or 512 tanh without LayerNorm; the reward "
-                                           "net: 512, tanh, LayerNorm with S <= 23), S + A <= 32, "
-                                           "ceil(K / 128) * 8 * members workgroups <= the device's CUs");
-    }
-    if (c.kernel == BCMPC_KERNEL_AUTO && team_fits && !opts.no_team) {
-        const char* ev = std::getenv("BCMPC_TEAM");
-        use_team = !(ev && ev[0] == '0');
-    }
-    // rollout_pp3 (two 64-candidate groups pipelined over one slab): the plain 2-layer tanh delta net at hidden
-    // 512 under kernel="auto"; cost terms and ensemble members stay on rollout_x3.  Forced, it also replaces the
-    // small-K team kernel
-    const int pp3_env = split_pp_env();
-    const bool pp3_shape = split && !f16 && !reward && e->PL == 0 && c.kernel == BCMPC_KERNEL_AUTO && !opts.no_pp3 &&
-                           c.activation == BCMPC_ACT_TANH && !c.layer_norm && c.cost != BCMPC_COST_TERMS &&
-                           c.horizon >= 1 && x3_pp3_ok(e->HP, c.n_layers, c.state_dim, c.action_dim);
-    const bool pp3_forced = pp3_shape && pp3_env == 1 && c.num_paths >= 1;
-    if (pp3_forced) use_team = false;
-    if (use_team) {
-        e->split = true;
-        e->nc = 1;
-        e->kernel = BCMPC_KERNEL_TEAM;
-        e->nw = e->HP / 16 / team_layer0_tiles(e->HP, tkind);
-        e->team_kind = tkind;
-        kern = e->kernel;
-    } else if (split) {
-        // widest workgroup (most candidates per weight read) that still gives every CU work and fits LDS
-        const int64_t cols = (c.num_paths + 15) / 16;
-        int nc = c.kernel == BCMPC_KERNEL_SPLIT1 ? 1 : c.kernel == BCMPC_KERNEL_SPLIT2 ? 2
-               : c.kernel == BCMPC_KERNEL_SPLIT4 ? 4 : 0;
-        const int nwx = x3_waves(e->HP);
-        auto fits = [&](int n) {
-            return n <= nwx && n <= x3_max_nc(e->HP) && (e->PL == 0 || x3_policy_ok(e->HP, n)) &&
-                   x3_lds(e->HP, reward ? 3 : c.n_layers, n, c.action_dim, e->PL, e->PHP,
-                          (c.activation == BCMPC_ACT_RELU ? 1 : 0) | (c.layer_norm ? 2 : 0)) <= 160 * 1024;
-        };
-        int nw = nwx;
-        if (f16) {
-            // single-pass f16: the hi-only slab admits wider groups (x3_f16_layout_ok); BCMPC_F16_NC /
-            // BCMPC_F16_NW pick a layout for A/B runs
-            auto f16_fits = [&](int n, int w) {
-                return x3_f16_layout_ok(e->HP, n, w) &&
-                       x3_f16_lds(e->HP, c.n_layers, n, w, c.action_dim) <= 160 * 1024;
-            };
-            const char* en = std::getenv("BCMPC_F16_NC");
-            const char* ew = std::getenv("BCMPC_F16_NW");
-            const char* ep = std::getenv("BCMPC_F16_PP");
-            // (default at large K, where it measured ahead of the two-group 4x4 layout below on every box:
-            //  0.835-0.848 vs 0.898-0.900 ms at cfg3, profiles/r04_pp_ab.jsonl; BCMPC_F16_PP=1 forces it at any
-            //  K, =0 turns it off)
-            const bool pp_env = ep && *ep;
-            if (!(en && *en) && !(ew && *ew) && x3_pp_ok(e->HP, c.n_layers, c.state_dim, c.action_dim) &&
-                !reward && e->PL == 0 && c.activation == BCMPC_ACT_TANH && !c.layer_norm &&
-                (pp_env ? ep[0] == '1' && cols >= 8 : cols >= 4 * 512)) {
-                // the two-group pipelined kernel (rollout_pp): 128 candidates per workgroup, 4 waves per
-                // group own 8 hidden tiles each (weights packed 8 tiles per wave)
-                e->pp = true;
-                // FOLD's input range: layer 0's normalised input goes to f16 without a power-of-two scale,
-                // clamped to +-65504 (a dim normalising beyond saturates; the first tanh has saturated long
-                // before) and below 6.1e-5 subnormal (< 6e-8 absolute error); the fold check below bounds
-                // only the weights.  Pinned by tests/test_gpu_f16.py::test_f16_pp_fold_input_range
-                const char* ef = std::getenv("BCMPC_PP_FOLD");
-                e->pp_fold = !(ef && ef[0] == '0');
-                nc = 8;
-                nw = 8;
-            }
-            if (en && *en) nc = std::atoi(en);
-            if (ew && *ew) nw = std::atoi(ew);
-            if (!e->pp && nc == 0 && !(ew && *ew) && e->HP == 512 && cols >= 4 * 512 && f16_fits(4, 4)) {
-                // two 64-candidate 4-wave groups per CU: 0.90 ms at cfg3 against 0.94 (one 8-wave group of
-                // 64) and 0.91 (one of 128), three boxes (profiles/r04_f16_layouts_ab.txt)
-                nc = 4;
-                nw = 4;
-            }
-            if (nc == 0) {
-                nc = 1;
-                for (int n : {8, 4, 2})
-                    if (f16_fits(n, nw) && cols >= (int64_t)n * 256 && !(n >= 4 && e->HP <= 256)) { nc = n; break; }
-            }
-            if (!e->pp && !f16_fits(nc, nw)) {
-                delete e;
-                return fail(BCMPC_ERR_UNSUPPORTED, "F16 precision: no single-pass layout for this shape / NC / NW");
-            }
-        } else if (nc == 0) {
-            nc = 1;
-            // (hidden <= 256: 32-candidate groups, two or three workgroups per CU, measured 6-18% ahead of 64)
-            for (int n : {4, 2})
-                if (fits(n) && cols >= (int64_t)n * 256 && !(n == 4 && e->HP <= 256)) { nc = n; break; }
-            // rollout_pp3 reads rollout_x3<512, NC=4, NW=8>'s packed weights: the engine stays a split4 engine
-            if (pp3_shape && nwx == 8 && fits(4) && (pp3_forced || (pp3_env != 0 && cols >= kSplitPpAutoCols && c.horizon >= kSplitPpAutoMinH))) {
-                e->pp3 = true;
-                nc = 4;
-            }
-        }
-        if (!f16 && !fits(nc)) {
-            delete e;
-            return fail(BCMPC_ERR_UNSUPPORTED, e->PL ? "split kernel with a fused policy needs dynamics hidden 449..1024"
-                                                     : "split kernel does not fit this shape");
-        }
-        e->split = true;
-        e->nc = nc;
-        e->kernel = nc == 1 ? BCMPC_KERNEL_SPLIT1 : nc == 2 ? BCMPC_KERNEL_SPLIT2 : BCMPC_KERNEL_SPLIT4;
-        e->nw = nw;
-        kern = e->kernel;
-    }
-    if (split_needs_team && !use_team) {
-        delete e;
-        return fail(BCMPC_ERR_UNSUPPORTED, "SPLIT_F16 precision supports relu / LayerNorm nets with a policy, the "
-                                           "reward net or hidden > 512 only on the small-K team kernel (use FP32)");
-    }
-    if (kern < BCMPC_KERNEL_SOLO || kern > BCMPC_KERNEL_TEAM) { delete e; return fail(BCMPC_ERR_ARG, "unknown kernel"); }
-    const int nw = split ? e->nw : kern_waves(kern);
-    if (!split && kern != BCMPC_KERNEL_SOLO &&
-        (e->T % nw != 0 || grp_lds_bytes(e->HP, c.n_layers, nw, e->PHP, e->PL, c.model) > 160 * 1024)) {
-        if (c.kernel != BCMPC_KERNEL_AUTO) { delete e; return fail(BCMPC_ERR_UNSUPPORTED, "group kernel does not fit this shape"); }
-        kern = BCMPC_KERNEL_SOLO;
-    }
-    if (kern == BCMPC_KERNEL_SOLO && (e->wpb < 1 || e->HP > 512)) {
-        delete e;
-        return fail(BCMPC_ERR_UNSUPPORTED, "solo kernel supports hidden <= 512 and needs LDS for its slabs");
-    }
-    e->kernel = kern;
-    e->nw = nw;
-    e->pack_tb = kern == BCMPC_KERNEL_SOLO ? 4 : e->pp ? e->T / 4 : e->T / nw;   // split: output tiles per wave
-    const int L = c.n_layers, T = e->T;
-    size_t off = 0, boff = 0;
-    e->nwl = reward ? 3 : L + 1;
-    if (reward && split) {
-        // split layout: trunk, delta head hidden (dense_1), delta out (dense_2), reward head
-        // hidden (dense_3), reward out (dense_4, one 16-row tile); 512 floats = one 2-KiB fragment pair
-        const int P = T / 2;
-        e->w_off[0] = off; off += (size_t)T * 512;
-        e->w_off[1] = off; off += (size_t)T * P * 512;
-        e->w_off[2] = off; off += (size_t)2 * P * 512;
-        e->w_off[3] = off; off += (size_t)T * P * 512;
-        e->w_off[4] = off; off += (size_t)P * 512;
-        e->nwl = 5;
-        // biases: trunk | delta head | reward head | out (rows 0..S-1 dense_2, row S dense_4) | (team kernel,
-        // LayerNorm heads) the centring table [8 members][32 rows]
-        e->b_off[0] = 0; e->b_off[1] = e->HP; e->b_off[2] = 2 * e->HP; e->b_off[3] = 3 * e->HP;
-        e->b_off[4] = 3 * e->HP + 32;
-        boff = 3 * e->HP + 32 + 8 * 32;
-    } else if (reward) {
-        // [S+A -> h] trunk, [h -> 2h] both heads' hidden layers, [2h -> S+1] block-diagonal output
-        e->w_off[0] = off; off += (size_t)T * 2 * 64 * 4;
-        e->w_off[1] = off; off += (size_t)2 * T * T * 64 * 4;
-        e->w_off[2] = off; off += (size_t)2 * 2 * T * 64 * 4;
-        e->b_off[0] = 0; e->b_off[1] = e->HP; e->b_off[2] = 3 * e->HP; boff = 3 * e->HP + 32 + 8 * 32;   // (same size as the split layout)
-    } else {
-        e->w_off[0] = off; off += (size_t)T * 2 * 64 * 4;                   // [S+A -> h]
-        for (int l = 1; l < L; ++l) { e->w_off[l] = off; off += (size_t)T * T * 64 * 4; }
-        e->w_off[L] = off; off += (size_t)2 * T * 64 * 4;                   // [h -> S]
-        for (int l = 0; l < L; ++l) { e->b_off[l] = boff; boff += e->HP; }
-        e->b_off[L] = boff; boff += 32;
-    }
-    e->w_floats = off;
-    const size_t ln_floats = 2 * (size_t)(reward ? 3 : L) * e->HP;
     auto cleanup = [&](int code) { bcmpc_destroy(e); return code; };
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&e->d_w, e->w_floats * sizeof(float)) != hipSuccess ||
-        hipMalloc(&e->d_b, boff * sizeof(float)) != hipSuccess ||
-        hipMalloc(&e->d_ln, ln_floats * sizeof(float)) != hipSuccess ||
+        hipMalloc(&e->d_b, e->b_floats * sizeof(float)) != hipSuccess ||
+        hipMalloc(&e->d_ln, e->ln_floats * sizeof(float)) != hipSuccess ||
         hipMalloc(&e->d_consts, sizeof(e->h_consts)) != hipSuccess ||
         hipMalloc(&e->d_state, BCMPC_MAX_STATE * sizeof(double)) != hipSuccess ||
         hipMalloc(&e->d_costs, std::max<int64_t>(1, c.num_paths) * sizeof(double)) != hipSuccess ||
@@ -467,12 +107,7 @@ int bcmpc::host::create_engine(const bcmpc_config* cfg, const CreateOpts& opts, 
         *e->h_team_err = 0;
     }
     if (e->PL > 0) {
-        size_t poff = 0;
-        e->pw_off[0] = poff; poff += (size_t)e->TP * 2 * 64 * 4;                    // [S -> ph]
-        for (int l = 1; l < e->PL; ++l) { e->pw_off[l] = poff; poff += (size_t)e->TP * e->TP * 64 * 4; }
-        e->pw_off[e->PL] = poff; poff += (size_t)e->TP * 64 * 4;                  // [ph -> one 16-row tile]
-        e->pw_floats = poff;
-        if (hipMalloc(&e->d_pw, poff * sizeof(float)) != hipSuccess ||
+        if (hipMalloc(&e->d_pw, e->pw_floats * sizeof(float)) != hipSuccess ||
             hipMalloc(&e->d_pb, ((size_t)e->PL * e->PHP + kPolParams) * sizeof(float)) != hipSuccess ||
             hipMalloc(&e->d_first, std::max<int64_t>(1, c.num_paths) * c.action_dim * sizeof(double)) != hipSuccess) {
             g_last_error = "device allocation failed";
@@ -485,7 +120,7 @@ int bcmpc::host::create_engine(const bcmpc_config* cfg, const CreateOpts& opts, 
         g_last_error = "device allocation failed (the trajectory scratch of the cost terms)";
         return cleanup(BCMPC_ERR_HIP);
     }
-    if (reward) {
+    if (e->reward) {
         if (hipMalloc(&e->d_gpow, (size_t)c.horizon * sizeof(double)) != hipSuccess) {
             g_last_error = "device allocation failed";
             return cleanup(BCMPC_ERR_HIP);
@@ -595,7 +230,7 @@ int bcmpc_set_weights(bcmpc_engine* e, const bcmpc_weights* w, uint64_t version)
     if (!e || !w || !w->kernels || !w->biases) return fail(BCMPC_ERR_ARG, "null argument");
     if (e->has_weights && version == e->version) return BCMPC_OK;    // idempotent re-sync
     const bcmpc_config& c = e->cfg;
-    const int L = c.n_layers, S = c.state_dim, A = c.action_dim, h = c.hidden, HP = e->HP, T = e->T;
+    const int L = c.n_layers;
     if (c.layer_norm && (!w->ln_gamma || !w->ln_beta)) return fail(BCMPC_ERR_ARG, "layer_norm enabled but LN params missing");
     if (!w->mean_obs || !w->std_obs || !w->mean_action || !w->std_action || !w->mean_deltas || !w->std_deltas)
         return fail(BCMPC_ERR_ARG, "normalization stats missing");
@@ -607,212 +242,24 @@ int bcmpc_set_weights(bcmpc_engine* e, const bcmpc_weights* w, uint64_t version)
     if (c.layer_norm)
         for (int l = 0; l < NLN; ++l)
             if (!w->ln_gamma[l] || !w->ln_beta[l]) return fail(BCMPC_ERR_ARG, "null LayerNorm pointer");
+    PackedNet pk;
+    pack_weights(*e, *w, &pk);
     HIP_TRY(hipSetDevice(c.device));
-    std::vector<float> hw(e->w_floats, 0.f);
-    const int tb = e->pack_tb;
-    std::vector<float> hb(rw ? 3 * (size_t)HP + 32 + 8 * 32 : (size_t)L * HP + 32, 0.f);
-    std::vector<float> hln(2 * (size_t)NLN * HP, 0.f);
-    auto copy_ln = [&] {                              // [gamma: NLN x HP][beta: NLN x HP]
-        for (int l = 0; l < NLN && c.layer_norm; ++l) {
-            std::memcpy(hln.data() + (size_t)l * HP, w->ln_gamma[l], sizeof(float) * h);
-            std::memcpy(hln.data() + (size_t)(NLN + l) * HP, w->ln_beta[l], sizeof(float) * h);
-        }
-    };
-    if (e->split && rw) {
-        _Float16* hh = reinterpret_cast<_Float16*>(hw.data());
-        const int P = T / 2;
-        const bool ln = c.layer_norm != 0;                // (team kernel only: bcmpc_create)
-        const float s0 = x3_scale(w->kernels[0], (size_t)(S + A) * h);
-        pack_x3_layer(w->kernels[0], S + A, h, 1, T, tb, s0, hh + 2 * e->w_off[0]);
-        e->winv[0] = 1.0f / s0;
-        // the heads' input: the trunk's tanh x 2^12, or its LayerNorm output x hsc[0] (|LN(x)_i| <=
-        // sqrt(h) |gamma_i| + |beta_i|, the power of two that keeps it below 2^12)
-        float hin = 4096.0f;
-        if (ln) e->hsc[0] = hin = ln_out_scale(w->ln_gamma[0], w->ln_beta[0], h);
-        const float sd = x3_scale(w->kernels[1], (size_t)h * h), sr = x3_scale(w->kernels[3], (size_t)h * h);
-        const int tbh = e->kernel == BCMPC_KERNEL_TEAM ? team_layer1_tiles(HP, e->team_kind) : tb;   // (team: head tiles per wave)
-        pack_x3_layer(w->kernels[1], h, h, P, T, tbh, sd, hh + 2 * e->w_off[1]);
-        pack_x3_layer(w->kernels[3], h, h, P, T, tbh, sr, hh + 2 * e->w_off[3]);
-        e->winv[1] = (1.0f / sd) / hin;
-        e->winv[3] = (1.0f / sr) / hin;
-        // LayerNorm heads (rollout_team.hip HLN): out = rsqrt(var + eps) (dense_2 diag(gamma))^T (h - mean)
-        // + (dense_2^T beta + b): gamma folded into the output kernels, beta into their biases
-        std::vector<float> w2((size_t)h * S), w4((size_t)h);
-        for (int k = 0; k < h; ++k) {
-            const float gd = ln ? w->ln_gamma[1][k] : 1.0f, gr = ln ? w->ln_gamma[2][k] : 1.0f;
-            for (int n = 0; n < S; ++n) w2[(size_t)k * S + n] = w->kernels[2][(size_t)k * S + n] * gd;
-            w4[k] = w->kernels[4][k] * gr;
-        }
-        // both output kernels feed one accumulator: one scale (the smaller of the two)
-        const float so = std::min(x3_scale(w2.data(), (size_t)h * S), x3_scale(w4.data(), (size_t)h));
-        pack_x3_layer(w2.data(), h, S, P, 2, 2, so, hh + 2 * e->w_off[2]);
-        std::vector<float> wr((size_t)h * 16, 0.f);      // dense_4 at row S of the second output tile
-        for (int k = 0; k < h; ++k) wr[(size_t)k * 16 + (S - 16)] = w4[k];
-        pack_x3_layer(wr.data(), h, 16, P, 1, 1, so, hh + 2 * e->w_off[4]);
-        // (LN: the heads' normalised output carries no 2^12 -- rsqrt of the x 2^12 variance undoes it)
-        e->winv[2] = e->winv[4] = ln ? 1.0f / so : (1.0f / so) / 4096.0f;
-        std::memcpy(hb.data() + e->b_off[0], w->biases[0], sizeof(float) * h);
-        std::memcpy(hb.data() + e->b_off[1], w->biases[1], sizeof(float) * h);
-        std::memcpy(hb.data() + e->b_off[2], w->biases[3], sizeof(float) * h);
-        std::memcpy(hb.data() + e->b_off[3], w->biases[2], sizeof(float) * S);
-        hb[e->b_off[3] + S] = w->biases[4][0];
-        if (ln) {
-            for (int n = 0; n <= S; ++n) {                // b + kernel^T beta (f64 sum, one rounding)
-                double acc = n < S ? (double)w->biases[2][n] : (double)w->biases[4][0];
-                for (int k = 0; k < h; ++k)
-                    acc += n < S ? (double)w->kernels[2][(size_t)k * S + n] * (double)w->ln_beta[1][k]
-                                 : (double)w->kernels[4][k] * (double)w->ln_beta[2][k];
-                hb[e->b_off[3] + n] = (float)acc;
-            }
-            // centring table: member t's rows [64 t, 64 t + 64) of the folded, scaled output kernels
-            for (int t = 0; t < 8; ++t)
-                for (int n = 0; n <= S; ++n) {
-                    double acc = 0.0;
-                    for (int k = 64 * t; k < std::min(h, 64 * t + 64); ++k)
-                        acc += n < S ? (double)w2[(size_t)k * S + n] * so : (double)w4[k] * so;
-                    hb[e->b_off[4] + (size_t)t * 32 + n] = (float)acc;
-                }
-            std::memcpy(hln.data(), w->ln_gamma[0], sizeof(float) * h);               // trunk gamma
-            std::memcpy(hln.data() + (size_t)3 * HP, w->ln_beta[0], sizeof(float) * h);   // trunk beta
-        }
-        e->mean_reward = w->mean_reward[0];
-        e->std_reward = w->std_reward[0];
-    } else if (e->split) {
-        // same sizes as the f32 layout (4 bytes per weight: two halves)
-        _Float16* hh = reinterpret_cast<_Float16*>(hw.data());
-        const int P = T / 2;
-        // rollout_pp's folded operands: the hidden-producing layers as f16(W x 2 log2 e), unscaled, when that
-        // stays well inside f16's range (else the scaled single-pass layout of the same kernel)
-        constexpr float kTanhKh = 2.8853900817779268f;     // 2 log2(e) (split_common.h kTanhK)
-        bool fold = e->pp && e->pp_fold;
-        for (int l = 0; l < L && fold; ++l) {
-            const int in = l == 0 ? S + A : h;
-            float mx = 0.f;
-            for (size_t i = 0; i < (size_t)in * h; ++i) mx = std::max(mx, std::fabs(w->kernels[l][i]));
-            fold = std::isfinite(mx) && mx * kTanhKh < 16384.0f;
-        }
-        e->pp_fold_w = fold;
-        for (int l = 0; l <= L; ++l) {
-            const int in = l == 0 ? S + A : h, out = l == L ? S : h;
-            const float sw = fold && l < L ? kTanhKh : x3_scale(w->kernels[l], (size_t)in * out);
-            // (team kernel: layer 0 in tb = team_layer0_tiles per wave, hidden layers in team_layer1_tiles)
-            const int tbh = e->kernel == BCMPC_KERNEL_TEAM ? team_layer1_tiles(HP, e->team_kind) : tb;
-            if (l == 0) pack_x3_layer(w->kernels[0], in, out, 1, T, tb, sw, hh + 2 * e->w_off[0]);
-            else if (l < L) pack_x3_layer(w->kernels[l], in, out, P, T, tbh, sw, hh + 2 * e->w_off[l]);
-            else pack_x3_layer(w->kernels[L], in, out, P, 2, 2, sw, hh + 2 * e->w_off[L]);
-            // layer 0's input scale is per candidate (kernel); hidden inputs are tanh * 2^12, an LN
-            // output x hsc[l-1] (static), or relu x its column's power of two (undone in the kernel)
-            float in_scale = 4096.0f;
-            if (l > 0 && c.layer_norm) {
-                e->hsc[l - 1] = in_scale = ln_out_scale(w->ln_gamma[l - 1], w->ln_beta[l - 1], h);
-            } else if (l > 0 && c.activation == BCMPC_ACT_RELU) {
-                in_scale = 1.0f;
-            }
-            if (fold) in_scale = 1.0f;                     // (folded: hidden activations are tanh in [-1, 1])
-            e->winv[l] = (1.0f / sw) * (l == 0 ? 1.0f : 1.0f / in_scale);
-        }
-        for (int l = 0; l < L; ++l) std::memcpy(hb.data() + e->b_off[l], w->biases[l], sizeof(float) * h);
-        std::memcpy(hb.data() + e->b_off[L], w->biases[L], sizeof(float) * S);
-        copy_ln();
-        // the team kernel's deferred last LayerNorm (rollout_team.hip DEFER; relu + LN, T = 1): the output
-        // kernel as dense_2 diag(gamma_1), scaled by its own power of two, its inputs the activations centred
-        // on each wave's column mean (no hsc); bias row b + dense_2^T beta_1 (f64 sum, one rounding); in
-        // gamma_1's slot the per-wave row sums c_w[n] = so sum_{k in wave w} (dense_2 diag(gamma_1))[k][n]
-        e->team_defer = TEAM_DEFER && e->kernel == BCMPC_KERNEL_TEAM && e->team_kind == 0 && c.layer_norm &&
-                        c.activation == BCMPC_ACT_RELU && L == 2 && team_members(HP, e->team_kind) == 1;
-        if (e->team_defer) {
-            const int tpw = team_layer1_tiles(HP, e->team_kind), nwv = HP / 16 / tpw;
-            std::vector<float> wg((size_t)h * S);
-            for (int k = 0; k < h; ++k)
-                for (int n = 0; n < S; ++n) wg[(size_t)k * S + n] = w->kernels[L][(size_t)k * S + n] * w->ln_gamma[L - 1][k];
-            const float so = x3_scale(wg.data(), (size_t)h * S);
-            pack_x3_layer(wg.data(), h, S, P, 2, 2, so, hh + 2 * e->w_off[L]);
-            e->winv[L] = 1.0f / so;
-            for (int n = 0; n < S; ++n) {
-                double acc = w->biases[L][n];
-                for (int k = 0; k < h; ++k) acc += (double)w->kernels[L][(size_t)k * S + n] * (double)w->ln_beta[L - 1][k];
-                hb[e->b_off[L] + n] = (float)acc;
-            }
-            std::fill(hln.begin() + HP, hln.begin() + 2 * HP, 0.f);
-            for (int x = 0; x < nwv; ++x)
-                for (int n = 0; n < S; ++n) {
-                    double acc = 0.0;
-                    for (int k = 16 * tpw * x; k < std::min(h, 16 * tpw * (x + 1)); ++k) acc += (double)wg[(size_t)k * S + n];
-                    hln[(size_t)HP + x * 32 + n] = (float)(acc * so);
-                }
-        }
-    } else {
-    pack_layer(w->kernels[0], S + A, h, 2, T, tb, hw.data() + e->w_off[0]);
-    if (rw) {
-        // heads' hidden layers side by side: W1c[k][n] = dense_1 (n < HP) | dense_3 (n >= HP)
-        std::vector<float> w1((size_t)h * 2 * HP, 0.f), wo((size_t)2 * HP * 32, 0.f);
-        for (int k = 0; k < h; ++k)
-            for (int n = 0; n < h; ++n) {
-                w1[(size_t)k * 2 * HP + n] = w->kernels[1][(size_t)k * h + n];
-                w1[(size_t)k * 2 * HP + HP + n] = w->kernels[3][(size_t)k * h + n];
-            }
-        // block-diagonal output: rows [0,h) x cols [0,S) = dense_2; rows [HP,HP+h) x col S = dense_4
-        for (int k = 0; k < h; ++k) {
-            for (int n = 0; n < S; ++n) wo[(size_t)k * 32 + n] = w->kernels[2][(size_t)k * S + n];
-            wo[(size_t)(HP + k) * 32 + S] = w->kernels[4][k];
-        }
-        pack_layer(w1.data(), h, 2 * HP, T, 2 * T, 2 * T / e->nw, hw.data() + e->w_off[1]);
-        pack_layer(wo.data(), 2 * HP, 32, 2 * T, 2, 2, hw.data() + e->w_off[2]);
-        std::memcpy(hb.data(), w->biases[0], sizeof(float) * h);
-        std::memcpy(hb.data() + HP, w->biases[1], sizeof(float) * h);
-        std::memcpy(hb.data() + 2 * HP, w->biases[3], sizeof(float) * h);
-        std::memcpy(hb.data() + 3 * HP, w->biases[2], sizeof(float) * S);
-        hb[3 * HP + S] = w->biases[4][0];
-        // LN: [gamma trunk HP | delta HP | reward HP][beta ...], i.e. the heads' params side by side
-        copy_ln();
-        e->mean_reward = w->mean_reward[0];
-        e->std_reward = w->std_reward[0];
-    } else {
-        for (int l = 1; l < L; ++l) pack_layer(w->kernels[l], h, h, T, T, tb, hw.data() + e->w_off[l]);
-        pack_layer(w->kernels[L], h, S, T, 2, 2, hw.data() + e->w_off[L]);
-        for (int l = 0; l < L; ++l) std::memcpy(hb.data() + e->b_off[l], w->biases[l], sizeof(float) * h);
-        std::memcpy(hb.data() + e->b_off[L], w->biases[L], sizeof(float) * S);
-        copy_ln();
-    }
-    }
-    double* C = e->h_consts;
-    for (int i = 0; i < kConstCols; ++i) {
-        C[0 * 32 + i] = i < S ? w->mean_obs[i] : 0.0;
-        C[1 * 32 + i] = i < S ? w->std_obs[i] + 1e-10 : 1.0;       // dynamics.py:109 (std + 1e-10)
-        C[2 * 32 + i] = i < A ? w->mean_action[i] : 0.0;
-        C[3 * 32 + i] = i < A ? w->std_action[i] + 1e-10 : 1.0;    // dynamics.py:110
-        C[4 * 32 + i] = i < S ? w->mean_deltas[i] : 0.0;
-        C[5 * 32 + i] = i < S ? w->std_deltas[i] : 0.0;
-        C[8 * 32 + i] = 1.0 / C[1 * 32 + i];
-        C[9 * 32 + i] = 1.0 / C[3 * 32 + i];
-    }
-    HIP_TRY(hipMemcpyAsync(e->d_w, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_b, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_ln, hln.data(), hln.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_consts, C, sizeof(e->h_consts), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));   // host vectors die at scope exit
-    if (e->kernel == BCMPC_KERNEL_TEAM) {
-        // (the fallback engine's copy: created only if a team ever fails to meet)
-        auto& hc = e->hw_copy;
-        hc = bcmpc_engine::HostNet{};
-        const int nin[5] = {S + A, h, h, h, h}, nout[5] = {h, h, S, h, 1};   // (reward net: dense .. dense_4)
-        for (int l = 0; l < NK; ++l) {
-            const int in = rw ? nin[l] : (l == 0 ? S + A : h), out = rw ? nout[l] : (l == L ? S : h);
-            hc.k.emplace_back(w->kernels[l], w->kernels[l] + (size_t)in * out);
-            hc.b.emplace_back(w->biases[l], w->biases[l] + out);
-        }
-        hc.ln = c.layer_norm != 0;
-        if (hc.ln)
-            for (int l = 0; l < NLN; ++l) {
-                hc.g.emplace_back(w->ln_gamma[l], w->ln_gamma[l] + h);
-                hc.beta.emplace_back(w->ln_beta[l], w->ln_beta[l] + h);
-            }
-        const double* sp[8] = {w->mean_obs, w->std_obs, w->mean_action, w->std_action, w->mean_deltas,
-                               w->std_deltas, rw ? w->mean_reward : nullptr, rw ? w->std_reward : nullptr};
-        const int sn[8] = {S, S, A, A, S, S, 1, 1};
-        for (int i = 0; i < 8; ++i)
-            if (sp[i]) hc.st[i].assign(sp[i], sp[i] + sn[i]);
-    }
+    for (int row : {0, 1, 2, 3, 4, 5, 8, 9})              // (rows 6, 7: the action bounds stay)
+        std::memcpy(e->h_consts + row * kConstCols, pk.consts + row * kConstCols, sizeof(double) * kConstCols);
+    HIP_TRY(hipMemcpyAsync(e->d_w, pk.w.data(), pk.w.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_b, pk.b.data(), pk.b.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_ln, pk.ln.data(), pk.ln.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_consts, e->h_consts, sizeof(e->h_consts), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));   // the packed vectors die at scope exit
+    std::copy(std::begin(pk.winv), std::end(pk.winv), e->winv);
+    std::copy(std::begin(pk.hsc), std::end(pk.hsc), e->hsc);
+    e->pp_fold_w = pk.pp_fold_w;
+    e->team_defer = pk.team_defer;
+    e->mean_reward = pk.mean_reward;
+    e->std_reward = pk.std_reward;
+    // (the fallback engine's copy: created only if a team ever fails to meet)
+    if (e->kernel == BCMPC_KERNEL_TEAM) e->hw_copy.capture(*e, *w);
     e->version = version;
     e->has_weights = true;
     return BCMPC_OK;
@@ -824,66 +271,16 @@ int bcmpc_set_policy(bcmpc_engine* e, const bcmpc_policy* p, uint64_t version) {
     if (e->PL == 0) return fail(BCMPC_ERR_STATE, "engine was created without a policy (config.policy_hidden == 0)");
     if (e->has_policy && version == e->pol_version) { e->explore = p->explore; return BCMPC_OK; }
     const bcmpc_config& c = e->cfg;
-    const int S = c.state_dim, A = c.action_dim, ph = c.policy_hidden, PL = e->PL, TP = e->TP, PHP = e->PHP;
-    for (int l = 0; l <= PL; ++l)
+    for (int l = 0; l <= e->PL; ++l)
         if (!p->kernels[l] || !p->biases[l]) return fail(BCMPC_ERR_ARG, "null policy kernel/bias pointer");
+    PackedPolicy pk;
+    pack_policy(*e, *p, &pk);
     HIP_TRY(hipSetDevice(c.device));
-    std::vector<float> hw(e->pw_floats, 0.f);
-    int rowmap[16];
-    for (int n = 0; n < 16; ++n) {
-        const int j = n - (S - 16);                     // action j sits at output-tile row S-16+j
-        rowmap[n] = (j >= 0 && j < A) ? j : -1;
-    }
-    if (e->split) {
-        // one tile per wave (TWp = 1); same byte sizes as the f32 layout.  Input scales:
-        // obz (|z| <= 5) x 2^11, hidden tanh x 2^12
-        _Float16* hh = reinterpret_cast<_Float16*>(hw.data());
-        const int PP = PHP / 32;
-        for (int l = 0; l < PL; ++l) {
-            const int in = l == 0 ? S : ph;
-            const float sw = x3_scale(p->kernels[l], (size_t)in * ph);
-            pack_x3_layer(p->kernels[l], in, ph, l == 0 ? 1 : PP, TP, 1, sw, hh + 2 * e->pw_off[l]);
-            e->pwinv[l] = (1.0f / sw) * (l == 0 ? 1.0f / 2048.0f : 1.0f / 4096.0f);
-        }
-        std::vector<float> wo((size_t)ph * 16, 0.f);    // output kernel with its columns at rows S-16+j
-        for (int k = 0; k < ph; ++k)
-            for (int n = 0; n < 16; ++n)
-                if (rowmap[n] >= 0) wo[(size_t)k * 16 + n] = p->kernels[PL][(size_t)k * A + rowmap[n]];
-        const float sw = x3_scale(p->kernels[PL], (size_t)ph * A);
-        pack_x3_layer(wo.data(), ph, 16, PP, 1, 1, sw, hh + 2 * e->pw_off[PL]);
-        e->pwinv[PL] = (1.0f / sw) * (1.0f / 4096.0f);
-    } else {
-        const int tb = TP / e->nw;
-        pack_layer(p->kernels[0], S, ph, 2, TP, tb, hw.data() + e->pw_off[0]);
-        for (int l = 1; l < PL; ++l) pack_layer(p->kernels[l], ph, ph, TP, TP, tb, hw.data() + e->pw_off[l]);
-        pack_out_rows(p->kernels[PL], ph, A, TP, rowmap, hw.data() + e->pw_off[PL]);
-    }
-    std::vector<float> hb((size_t)PL * PHP + kPolParams, 0.f);
-    for (int l = 0; l < PL; ++l) std::memcpy(hb.data() + (size_t)l * PHP, p->biases[l], sizeof(float) * ph);
-    float* pm = hb.data() + (size_t)PL * PHP;           // [obmean 32][obstd 32][logstd 16][outbias 16]
-    for (int d = 0; d < 32; ++d) {
-        pm[d] = d < S ? p->ob_mean[d] : 0.f;
-        pm[32 + d] = d < S ? p->ob_std[d] : 1.f;
-    }
-    for (int j = 0; j < A; ++j) {
-        pm[64 + j] = p->logstd[j];
-        pm[80 + (S - 16 + j)] = p->biases[PL][j];
-    }
-    HIP_TRY(hipMemcpyAsync(e->d_pw, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_pb, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_pw, pk.w.data(), pk.w.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_pb, pk.b.data(), pk.b.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->kernel == BCMPC_KERNEL_TEAM) {               // (the fallback engine's copy)
-        auto& hc = e->hp_copy;
-        hc = bcmpc_engine::HostNet{};
-        for (int l = 0; l <= PL; ++l) {
-            const int in = l == 0 ? S : ph, out = l == PL ? A : ph;
-            hc.k.emplace_back(p->kernels[l], p->kernels[l] + (size_t)in * out);
-            hc.b.emplace_back(p->biases[l], p->biases[l] + out);
-        }
-        hc.pvec[0].assign(p->ob_mean, p->ob_mean + S);
-        hc.pvec[1].assign(p->ob_std, p->ob_std + S);
-        hc.pvec[2].assign(p->logstd, p->logstd + A);
-    }
+    std::copy(std::begin(pk.pwinv), std::end(pk.pwinv), e->pwinv);
+    if (e->kernel == BCMPC_KERNEL_TEAM) e->hp_copy.capture(*e, *p);   // (the fallback engine's copy)
     e->explore = p->explore;
     e->pol_version = version;
     e->has_policy = true;
@@ -1111,25 +508,8 @@ int bcmpc_set_terminal_value(bcmpc_engine* e, const bcmpc_value_net* v, double w
     }
     // (S is the net's: a net over another state_dim runs through bcmpc_terminal_value_async alone; the rollout
     //  entries refuse it, rollout_impl)
-    const int L = v->n_layers, h = v->hidden, S = v->state_dim;
-    const int HP = terminal_value_padded(h), T = HP / 16, TB = std::min(T, 4);
-    // packed kernels: [2 -> T] [T -> T] x (L - 1) [T -> 1], 256 floats per fragment
-    size_t off[BCMPC_VALUE_MAX_LAYERS + 2];
-    off[0] = 0;
-    off[1] = (size_t)2 * T * 256;
-    for (int l = 1; l < L; ++l) off[l + 1] = off[l] + (size_t)T * T * 256;
-    off[L + 1] = off[L] + (size_t)T * 256;
-    std::vector<float> hw(off[L + 1]), hp((size_t)kTvParamFloats, 0.f);
-    pack_layer(v->kernels[0], S, h, 2, T, TB, hw.data() + off[0]);
-    for (int l = 1; l < L; ++l) pack_layer(v->kernels[l], h, h, T, T, TB, hw.data() + off[l]);
-    pack_layer(v->kernels[L], h, 1, T, 1, 1, hw.data() + off[L]);
-    for (int i = 0; i < S; ++i) {
-        hp[i] = v->ob_mean[i];
-        hp[32 + i] = v->ob_std[i];
-    }
-    for (int i = S; i < 32; ++i) hp[32 + i] = 1.f;
-    for (int l = 0; l < L; ++l) std::copy(v->biases[l], v->biases[l] + h, hp.begin() + 64 + (size_t)l * HP);
-    hp[64 + (size_t)L * HP] = v->biases[L][0];
+    PackedValue pk;
+    pack_value_net(*v, &pk);
     HIP_TRY(hipSetDevice(c.device));
     constexpr size_t kMaxW = (size_t)(2 * 16 + (BCMPC_VALUE_MAX_LAYERS - 1) * 16 * 16 + 16) * 256;
     if (!e->d_vw) HIP_TRY(hipMalloc(&e->d_vw, kMaxW * sizeof(float)));
@@ -1141,27 +521,18 @@ int bcmpc_set_terminal_value(bcmpc_engine* e, const bcmpc_value_net* v, double w
                                              c.state_dim * sizeof(double)));
     // (launches of the previous net on any stream of this device have to be over before its weights change)
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(e->d_vw, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_vparams, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_vw, pk.w.data(), pk.w.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_vparams, pk.params.data(), pk.params.size() * sizeof(float), hipMemcpyHostToDevice));
     TerminalValueArgs a{};
-    for (int l = 0; l <= L; ++l)
-        a.w[l] = reinterpret_cast<const float __attribute__((ext_vector_type(4)))*>(e->d_vw + off[l]);
+    for (int l = 0; l <= v->n_layers; ++l)
+        a.w[l] = reinterpret_cast<const float __attribute__((ext_vector_type(4)))*>(e->d_vw + pk.off[l]);
     a.params = e->d_vparams;
     a.weight = weight;
-    a.S = S; a.L = L; a.HP = HP;
+    a.S = v->state_dim; a.L = v->n_layers; a.HP = pk.HP;
     e->tv = a;
     e->has_value = true;
     e->value_version = version;
-    auto& hc = e->hv_copy;
-    hc.k.clear(); hc.b.clear();
-    for (int l = 0; l <= L; ++l) {
-        const int in = l == 0 ? S : h, out = l == L ? 1 : h;
-        hc.k.emplace_back(v->kernels[l], v->kernels[l] + (size_t)in * out);
-        hc.b.emplace_back(v->biases[l], v->biases[l] + out);
-    }
-    hc.mean.assign(v->ob_mean, v->ob_mean + S);
-    hc.std.assign(v->ob_std, v->ob_std + S);
-    hc.L = L; hc.hidden = h;
+    e->hv_copy.capture(*v);
     if (e->fb) return bcmpc_set_terminal_value(e->fb, v, weight, version);
     return BCMPC_OK;
 }
@@ -1301,31 +672,14 @@ int team_fallback(bcmpc_engine* e, bool collective) {
     bcmpc_engine* f = e->fb;
     f->comm = collective ? e->comm : nullptr;        // (the rerun's exchange: every rank reruns)
     if (!e->fb_wset || e->fb_wver != e->version) {
-        const auto& hc = e->hw_copy;
-        std::vector<const float*> k, b, g, be;
-        for (auto& v : hc.k) k.push_back(v.data());
-        for (auto& v : hc.b) b.push_back(v.data());
-        for (auto& v : hc.g) g.push_back(v.data());
-        for (auto& v : hc.beta) be.push_back(v.data());
-        bcmpc_weights w{};
-        w.kernels = k.data(); w.biases = b.data();
-        w.ln_gamma = hc.ln ? g.data() : nullptr; w.ln_beta = hc.ln ? be.data() : nullptr;
-        w.mean_obs = hc.st[0].data(); w.std_obs = hc.st[1].data(); w.mean_action = hc.st[2].data();
-        w.std_action = hc.st[3].data(); w.mean_deltas = hc.st[4].data(); w.std_deltas = hc.st[5].data();
-        w.mean_reward = hc.st[6].empty() ? nullptr : hc.st[6].data();
-        w.std_reward = hc.st[7].empty() ? nullptr : hc.st[7].data();
+        const bcmpc_weights w = e->hw_copy.view();
         if (const int rc = bcmpc_set_weights(f, &w, e->version)) return rc;
         e->fb_wver = e->version;
         e->fb_wset = true;
     }
     if (e->PL > 0) {
         if (!e->fb_pset || e->fb_pver != e->pol_version) {
-            const auto& hc = e->hp_copy;
-            std::vector<const float*> k, b;
-            for (auto& v : hc.k) k.push_back(v.data());
-            for (auto& v : hc.b) b.push_back(v.data());
-            const bcmpc_policy p{k.data(), b.data(), hc.pvec[0].data(), hc.pvec[1].data(), hc.pvec[2].data(),
-                                 e->explore};
+            const bcmpc_policy p = e->hp_copy.view(e->explore);
             if (const int rc = bcmpc_set_policy(f, &p, e->pol_version)) return rc;
             e->fb_pver = e->pol_version;
             e->fb_pset = true;
@@ -1344,11 +698,7 @@ int team_fallback(bcmpc_engine* e, bool collective) {
     if (!f->tc_conds.empty() && !f->d_tc_steps)
         HIP_TRY(hipMalloc(&f->d_tc_steps, (size_t)std::max<int64_t>(1, f->cfg.num_paths) * sizeof(int32_t)));
     if (e->has_value && (!f->has_value || f->value_version != e->value_version || f->tv.weight != e->tv.weight)) {
-        const auto& hc = e->hv_copy;
-        std::vector<const float*> k, b;
-        for (auto& v : hc.k) k.push_back(v.data());
-        for (auto& v : hc.b) b.push_back(v.data());
-        const bcmpc_value_net vn{k.data(), b.data(), hc.mean.data(), hc.std.data(), hc.L, hc.hidden, e->tv.S, 0};
+        const bcmpc_value_net vn = e->hv_copy.view();
         if (const int rc = bcmpc_set_terminal_value(f, &vn, e->tv.weight, e->value_version)) return rc;
     } else if (!e->has_value && f->has_value) {
         if (const int rc = bcmpc_set_terminal_value(f, nullptr, 0.0, 0)) return rc;
@@ -1702,7 +1052,7 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     } else if (e->kernel == BCMPC_KERNEL_SOLO) {
         HIP_TRY(launch_rollout(a, e->HP, e->wpb, st));
     } else {
-        HIP_TRY(launch_rollout_grp(a, e->HP, kern_waves(e->kernel), st));
+        HIP_TRY(launch_rollout_grp(a, e->HP, e->nw, st));
     }
     if (terms)
         if (const int rc = term_cost_launch(e, d_traj, d_actions, seed, cand_offset, cem ? cem->mu : nullptr,

@@ -1,5 +1,5 @@
-// host_internal.h -- what the host units of libbcmpc (capi.cpp, mt_draw.cpp, planners.cpp) share: the engine, the
-// error channel, the launch helpers more than one of them calls.  Not installed; the C ABI is include/bcmpc.h.
+// host_internal.h -- what the HIP-calling host units of libbcmpc (capi.cpp, mt_draw.cpp, planners.cpp) share: the
+// engine, the error channel, the launch helpers more than one of them calls.  Not installed; the C ABI is include/bcmpc.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,33 +19,21 @@
 #include "../../include/bcmpc.h"
 #include "kernels.h"
 #include "mt19937.h"
+#include "pack.h"
 
 using namespace bcmpc;
 
-struct bcmpc_engine {
-    bcmpc_config cfg{};
-    int HP = 0, T = 0, wpb = 4;
-    int kernel = BCMPC_KERNEL_SOLO;    // resolved kernel layout
-    int nw = 1;                        // waves per group (group kernels)
-    int pack_tb = 4;                   // output tiles per packed block of layers 0..L-1
-    bool split = false;                // BCMPC_PREC_SPLIT_F16 or F16 (rollout_x3)
-    bool f16 = false;                  // BCMPC_PREC_F16: single MFMA pass
-    bool pp = false;                   // BCMPC_PREC_F16 on the two-group pipelined kernel (rollout_pp)
-    bool pp_fold = false;              // ... with the folded operands (rollout_pp<, FOLD>; BCMPC_PP_FOLD=0: off)
-    bool pp_fold_w = false;            //     active for the current weights (|W| x 2 log2 e within f16's range)
-    bool pp3 = false;                  // BCMPC_PREC_SPLIT_F16 on the two-group pipelined kernel (rollout_pp3): the
-                                       // launches it implements; the others run rollout_x3 on the same weights
-    int nc = 0;                        // split kernel: 16-candidate columns per workgroup
-    int nwl = 0;                       // packed weight layers (RolloutArgs.w entries)
+struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, packed layout -- engine_plan.h)
+    explicit bcmpc_engine(const bcmpc::host::EnginePlan& plan) : EnginePlan(plan) {}
+    // what the last bcmpc_set_weights / bcmpc_set_policy left besides the buffers (pack.h PackedNet / PackedPolicy)
+    bool pp_fold_w = false;            // rollout_pp's folded operands are active for the current weights
     float winv[BCMPC_MAX_LAYERS + 1]{};  // split kernel: 1 / operand scales per layer
     float pwinv[BCMPC_MAX_LAYERS + 1]{}; // ... and per fused-policy layer
     float hsc[BCMPC_MAX_LAYERS]{};       // split LN nets: output scale of hidden layer l
-    bool reward = false;               // BCMPC_MODEL_REWARD (NNDynamicsRewardModel)
     hipStream_t stream = nullptr;
     // device buffers
-    float* d_w = nullptr;   size_t w_floats = 0;
-    size_t w_off[BCMPC_MAX_LAYERS + 1]{};
-    float* d_b = nullptr;   size_t b_off[BCMPC_MAX_LAYERS + 1]{};
+    float* d_w = nullptr;   // [w_floats]
+    float* d_b = nullptr;   // [b_floats]
     float* d_ln = nullptr;  // [2][L][HP]
     double* d_consts = nullptr;
     double* d_state = nullptr;
@@ -112,7 +100,6 @@ struct bcmpc_engine {
     int32_t* d_keep_count = nullptr; int32_t keep_count_cap = 0;
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;
-    int team_kind = 0;                  // 0 plain delta net, 1 + policy, 2 reward net (+ policy)
     bool team_defer = false;            // the weights are packed for rollout_team's deferred last LayerNorm
     unsigned* d_team_ctl = nullptr;
     unsigned* h_team_err = nullptr;
@@ -134,8 +121,7 @@ struct bcmpc_engine {
     bool timed = false;                 // the last launch chain recorded ev[0..2]
     bool timing = false;                // bcmpc_engine_set_timing: bracket launches with HIP events
     // fused policy (MPCcontrollerPolicyNet)
-    int PHP = 0, TP = 0, PL = 0;
-    float* d_pw = nullptr;  size_t pw_floats = 0;  size_t pw_off[BCMPC_MAX_LAYERS + 1]{};
+    float* d_pw = nullptr;                          // [pw_floats]
     float* d_pb = nullptr;                          // [PL][PHP] + kPolParams
     double* d_first = nullptr;                      // [K][A] step-0 actions
     // learned reward (NNDynamicsRewardModel)
@@ -213,11 +199,7 @@ struct bcmpc_engine {
     float* d_vw = nullptr;
     float* d_vparams = nullptr;
     float* d_vvalues = nullptr;         // [num_paths] the last launch chain's values (bcmpc_last_terminal_values)
-    struct HostValue {                  // the last net, copied (the fallback engine is set from it)
-        std::vector<std::vector<float>> k, b;
-        std::vector<float> mean, std;
-        int L = 0, hidden = 0;
-    } hv_copy;
+    bcmpc::host::ValueCopy hv_copy;     // the last net, copied (the fallback engine is set from it)
     // team kernel: a team that could not meet (its workgroups not all resident: another process or
     // kernel holding CUs for ~1 s) makes a synchronous call rerun on this fallback engine -- the same
     // net on the split slab kernel, or the fp32 group kernel where only the team kernel takes the net
@@ -227,13 +209,8 @@ struct bcmpc_engine {
     bool fb_wset = false, fb_pset = false;
     uint64_t team_reruns = 0;
     bool sync_call = false;             // inside a synchronous entry point (its launches complete before it returns)
-    struct HostNet {                    // the last bcmpc_set_weights / bcmpc_set_policy, copied
-        std::vector<std::vector<float>> k, b, g, beta;
-        std::vector<double> st[8];      // mean/std obs, action, deltas, reward
-        std::vector<float> pvec[3];     // (policy) ob_mean, ob_std, logstd
-        double explore = 0.0;
-        bool ln = false;
-    } hw_copy, hp_copy;
+    bcmpc::host::WeightsCopy hw_copy;   // the last bcmpc_set_weights / bcmpc_set_policy, copied (team engines)
+    bcmpc::host::PolicyCopy hp_copy;
     double gamma = 1.0;
 };
 
@@ -241,7 +218,7 @@ struct bcmpc_engine {
 #pragma GCC visibility push(hidden)
 namespace bcmpc::host {
 
-inline int fail(int code, const std::string& msg) { return set_error(code, msg); }   // (bcmpc_last_error's text: capi.cpp)
+// (fail(code, msg), bcmpc_last_error's text: engine_plan.h; the text itself lives in capi.cpp)
 
 #define HIP_TRY(expr)                                                                     \
     do {                                                                                  \
@@ -267,10 +244,6 @@ struct SyncCall {                                   // marks a synchronous entry
     void set(bool on) const { for (size_t i = 0; i < n; ++i) m[i]->sync_call = on; }
 };
 
-struct CreateOpts {                     // bcmpc_create's internal options
-    bool no_team = false;               // never pick the team kernel (fallback engines)
-    bool no_pp3 = false;                // never pick rollout_pp3 (ensemble members)
-};
 int create_engine(const bcmpc_config* cfg, const CreateOpts& opts, bcmpc_engine** out);
 
 // one rollout launch chain (rollout_impl): a call site names what it sets

@@ -6,15 +6,11 @@
 #include <string>
 
 #include "../../include/bcmpc.h"
+#include "shapes.h"
 
 namespace bcmpc {
 
-// consts block: [10][32] doubles
-//   0 mean_obs   1 std_obs + 1e-10   2 mean_action   3 std_action + 1e-10
-//   4 mean_deltas  5 std_deltas      6 action low    7 action high
-//   8 1 / (std_obs + 1e-10)   9 1 / (std_action + 1e-10)   (correctly rounded, for div_rn)
-constexpr int kConstRows = 10;
-constexpr int kConstCols = 32;
+// (the consts block [kConstRows][kConstCols] and the host shape queries of every kernel unit: shapes.h)
 
 struct ArgminArgs {
     const double* costs;
@@ -200,46 +196,15 @@ int comm_rank(const bcmpc_comm* c);
 int comm_size(const bcmpc_comm* c);
 int comm_device(const bcmpc_comm* c);
 
-constexpr int kPolParams = 96;
-
-constexpr int kArgminParts = 256;
-int argmin_parts(int64_t K);
-
-int max_waves_per_block(int hidden_padded, int n_layers);
 hipError_t launch_rollout(const RolloutArgs& a, int hidden_padded, int waves_per_block, hipStream_t st);
-size_t grp_lds_bytes(int hidden_padded, int n_layers, int nw, int policy_hidden_padded, int policy_layers, int model);
 hipError_t launch_rollout_grp(const RolloutArgs& a, int hidden_padded, int nw, hipStream_t st);
-int x3_waves(int hidden_padded);
-int x3_max_nc(int hidden_padded);
-size_t x3_lds(int hidden_padded, int n_layers, int nc, int action_dim, int policy_layers, int policy_hidden_padded,
-              int ak = 0);
-bool x3_policy_ok(int hidden_padded, int nc);
-// single-pass f16 layouts (BCMPC_PREC_F16): the (nc, nw) pairs this build instantiates, and their LDS
-bool x3_f16_layout_ok(int hidden_padded, int nc, int nw);
-size_t x3_f16_lds(int hidden_padded, int n_layers, int nc, int nw, int action_dim);
-bool x3_pp_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);   // rollout_pp's shapes
-// split precision on the two-group pipelined kernel (rollout_pp3): its shapes, its LDS bytes, the launch
-// arguments it implements (every other launch runs rollout_x3 on the same packed weights)
-bool x3_pp3_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);
-size_t x3_pp3_lds(int hidden_padded, int state_dim, int action_dim);
+// rollout_pp3: the launch arguments it implements (every other launch runs rollout_x3 on the same packed weights)
 bool x3_pp3_args_ok(const RolloutArgs& a, int hidden_padded);
 hipError_t launch_rollout_pp3(const RolloutArgs& a, int hidden_padded, hipStream_t st);
 // (rollout_pp: what launch_rollout_x3_f16 runs when a.x3_pp is set)
 hipError_t launch_rollout_pp(const RolloutArgs& a, int hidden_padded, hipStream_t st);
 hipError_t launch_rollout_x3(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
 hipError_t launch_rollout_x3_f16(const RolloutArgs& a, int hidden_padded, int nc, hipStream_t st);
-// rollout_team.hip; kind: 0 the plain delta net, 1 + fused policy, 2 the reward net (+ policy)
-int team_members(int hidden_padded, int kind);          // workgroups per candidate column (0: unsupported)
-// the team kernel's deferred last LayerNorm (relu + LN delta net at T = 1; rollout_team.hip DEFER): the host
-// packs the output layer for it whenever the kernel takes it -- one switch for both sides
-#ifndef TEAM_DEFER
-#define TEAM_DEFER 1
-#endif
-int team_layer0_tiles(int hidden_padded, int kind);     // layer-0 tiles per wave (weight packing)
-int team_layer1_tiles(int hidden_padded, int kind);     // hidden-layer (head) tiles per wave
-int64_t team_blocks(int64_t K, int hidden_padded, int kind);
-size_t team_buf_bytes(int64_t K, int hidden_padded, int kind);
-bool team_rw_ln_built();                                // the reward net's LayerNorm heads are in this build
 hipError_t launch_rollout_team(const RolloutArgs& a, int hidden_padded, hipStream_t st);
 hipError_t launch_argmin(const ArgminArgs& a, hipStream_t st);
 hipError_t launch_select(const SelectArgs& a, hipStream_t st);
@@ -310,9 +275,8 @@ hipError_t launch_ensemble_reduce(const EnsembleReduceArgs& a, hipStream_t st);
 // ---- terminal value (terminal_value.hip): values[k] = V(states[k]), costs[k] += weight * values[k] ----
 // (with term_step: the add only for a candidate that never terminated; values[k] is written regardless)
 // params: [32] ob_mean, [32] ob_std, [L][HP] hidden biases, [16] final bias (row 0), all zero-padded.
-// w[l]: pack_layer(kernel l, Tin, Tout, TB) with Tin = 2 (layer 0) or HP / 16, Tout = HP / 16 and
+// w[l]: pack.cpp pack_layer(kernel l, Tin, Tout, TB) with Tin = 2 (layer 0) or HP / 16, Tout = HP / 16 and
 // TB = min(4, Tout) for the hidden layers, Tout = TB = 1 for the final one.
-constexpr int kTvParamFloats = 64 + BCMPC_VALUE_MAX_LAYERS * BCMPC_VALUE_MAX_HIDDEN + 16;
 struct TerminalValueArgs {
     const float __attribute__((ext_vector_type(4)))* w[BCMPC_VALUE_MAX_LAYERS + 1];
     const float* params;
@@ -325,7 +289,6 @@ struct TerminalValueArgs {
     const int32_t* term_step;                // [K] or nullptr: the cost add only where term_step[k] == horizon
     int32_t horizon;
 };
-int terminal_value_padded(int hidden);       // 16, 32, 64, 128 or 256 (-1: outside [1, 256])
 hipError_t launch_terminal_value(const TerminalValueArgs& a, hipStream_t st);
 
 hipError_t launch_tile_states(const TileStatesArgs& a, hipStream_t st);

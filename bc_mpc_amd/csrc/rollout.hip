@@ -27,7 +27,7 @@
 //   row/dim d = 16v + 4q + r (v = 0,1).
 //
 // Weights are streamed from L2 (1 KiB per wave-instruction, float4 per lane,
-// fragment order, see pack_layer in capi.cpp); all waves of a CU walk the
+// fragment order, see pack_layer in pack.cpp); all waves of a CU walk the
 // same stream, so it is shared through the CU's L1.
 
 #include <hip/hip_runtime.h>

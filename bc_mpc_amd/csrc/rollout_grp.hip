@@ -19,7 +19,7 @@
 // fixed wave order through the slab (deterministic; every wave then owns the
 // full f64 state update, wave 0 publishes cost / trajectory).
 //
-// Weights: packed [w][u][j][lane] with TB = TW (capi.cpp pack_layer), so each
+// Weights: packed [w][u][j][lane] with TB = TW (pack.cpp pack_layer), so each
 // wave walks one contiguous stream; tile j's fragment for u-step u+1 is
 // requested right after the four MFMAs that consume u-step u's (>= 4*TW-4
 // MFMAs of lead time).  Reads past the layer end return 0 (buffer range

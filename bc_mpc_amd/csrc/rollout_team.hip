@@ -30,7 +30,7 @@
 //     earlier launches never match and nothing has to be zeroed per call.  Spins are bounded:
 //     a team that cannot meet (a member never became resident) sets *team_err and finishes.
 //   * Co-residency: all T members of a team must run at once.  The host launches a team kernel
-//     only when the whole grid fits one workgroup per CU (capi.cpp); members of a column are
+//     only when the whole grid fits one workgroup per CU (engine_plan.cpp); members of a column are
 //     numbered b, b + 8, ... so they share an XCD under round-robin dispatch (speed only).
 //
 // Numerics (same bar as rollout_x3): the output layer's partial sums are added in a fixed order
@@ -313,7 +313,7 @@ __device__ __forceinline__ void epi_cols(f4 (&acc)[NTL], float f, const float* _
 }
 
 // activations of NTL tiles -> the next layer's B fragments (hi, lo): a tile pair is one 32-wide
-// k-step (capi.cpp pack_x3_layer k order); a single tile fills the half of its k-step that its
+// k-step (pack.cpp pack_x3_layer k order); a single tile fills the half of its k-step that its
 // parity selects (odd: rows 16..31), the other half is zero
 template <int NTL>
 __device__ __forceinline__ void split_tiles(const f4 (&v)[NTL], int odd, h8 (&xh)[(NTL + 1) / 2],
@@ -363,7 +363,7 @@ void rollout_team(const RolloutArgs a) {
     constexpr bool HLN = RW && LNK;                     // the reward net's LayerNorm heads (dynamics.py:165-177)
     // DEFER (relu + LayerNorm delta net at T = 1, TEAM_DEFER): the second LayerNorm moves behind the output
     // layer.  The output kernel is packed as dense_2 diag(gamma_1) (its bias + dense_2^T beta_1 in the bias
-    // row, capi.cpp), each wave feeds it its activations centred on its own column mean, and after the
+    // row, pack.cpp), each wave feeds it its activations centred on its own column mean, and after the
     // partials barrier -- which now also publishes the statistics -- the summed rows become
     // rsqrt(var + eps) (sum + sum_w (mean_w - mean) c_w), c_w = the wave's rows of the scaled, folded output
     // kernel summed (lnp + HP, [NWV][32]): one barrier and the normalisation pass fewer per step
@@ -460,7 +460,7 @@ void rollout_team(const RolloutArgs a) {
         int pw_total = 0;                                 // policy: every layer's packed bytes, copied once
         if constexpr (PHP > 0) {
             for (int l = 1; l < a.pL; ++l) pw_total += a.pwbytes[l];
-            // the policy's hidden layers 1..pL-1 (contiguous, capi.cpp pw_off): 16 f4 per thread in flight
+            // the policy's hidden layers 1..pL-1 (contiguous, engine_plan.cpp pw_off): 16 f4 per thread in flight
             const f4* src = a.pw[1];
             f4* const dst = reinterpret_cast<f4*>(const_cast<char*>(plw));
             const int n4 = pw_total / 16;
@@ -667,7 +667,7 @@ void rollout_team(const RolloutArgs a) {
         lds_barrier();                                    //  would otherwise wait behind them)
         pstamp(1);
         // ---- every weight fragment this wave uses, once (issued after the parameter barrier so the
-        //      loads stay in flight through the first step's LDS barriers) (capi.cpp: layer 0 packed with TWp = L0T,
+        //      loads stay in flight through the first step's LDS barriers) (pack.cpp: layer 0 packed with TWp = L0T,
         //      layer 1 with TWp = TPW, the output layer [0][k-step][tile]) ----
         const int voff = lane * 16;
         h8 w0h[L0T], w0l[L0T], w1h[P][TPW], w1l[P][TPW], woh[PPW][2], wol[PPW][2];
@@ -705,7 +705,7 @@ void rollout_team(const RolloutArgs a) {
                     w1l[p][j] = fload(r1, voff, ((g * P + p) * TPW + j) * 2048 + 1024);
                 }
             // (reward-head waves: tile 0 zero, tile 1 = dense_4 packed as one 16-row tile whose row S-16
-            //  feeds output row S -- capi.cpp split reward layout; the delta output weights there are 0)
+            //  feeds output row S -- pack.cpp split reward layout; the delta output weights there are 0)
             const __amdgpu_buffer_rsrc_t r2 = layer_rsrc(a.w[rw_wave ? 4 : 2], a.wbytes[rw_wave ? 4 : 2]);
 #pragma unroll
             for (int pp = 0; pp < PPW; ++pp)
@@ -1060,7 +1060,7 @@ void rollout_team(const RolloutArgs a) {
                 // LayerNorm over a head split across the team (dynamics.py:171, :177; TF1 layer_norm, eps
                 // 1e-12): tanh x 2^12, this wave's (mean, M2) over its valid rows, merged with its head's
                 // other waves in wave order (Chan) into the MEMBER's statistics; the output layer then sees
-                // h - mean_member (gamma is folded into the output weights, beta into their bias: capi.cpp),
+                // h - mean_member (gamma is folded into the output weights, beta into their bias: pack.cpp),
                 // and the team's exact (h - mean) sums are rebuilt after the exchange from the members'
                 // statistics: sum_t P_t + sum_t (mean_t - mean) rs_t, times rsqrt(var + eps)
                 const int nwr = min(max(a.hidden - 16 * TPW * g, 0), 16 * TPW);

@@ -72,7 +72,7 @@ __device__ __forceinline__ void swrite(f4* p, h8 v) { *p = __builtin_bit_cast(f4
 // undoing the operand scales; f and the biases carry the 2 log2(e) factor), tanh x 2^12 as
 // 4096 - 8192 / (1 + 2^z) (fma / add / fma as packed f32 ops, bit-identical to the scalar
 // form; exp / rcp per element), split.  The pair's accumulators are exactly one k-step B
-// fragment of the next layer (the host's k-order permutation, capi.cpp pack_x3_layer).
+// fragment of the next layer (the host's k-order permutation, pack.cpp pack_x3_layer).
 #ifndef BCMPC_EPI_PK             // 0: scalar (default: rollout_pp 0.831 -> 0.822 ms, profiles/r05_epi_scalar_ab.txt), 1: packed f32 fma / add (v_pk_*_f32)
 #define BCMPC_EPI_PK 0
 #endif

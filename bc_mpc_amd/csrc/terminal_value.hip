@@ -11,7 +11,7 @@
 //
 // Layout: the transposed MLP of rollout.hip.  A wave owns 16 candidates as MFMA columns; a layer is
 // D[neuron][cand] = W^T X with the weights as the A operand, packed once per weight version by pack_layer
-// (capi.cpp) in blocks of TB output tiles, so the accumulators of output tile t ARE the B fragments of k-steps
+// (pack.cpp) in blocks of TB output tiles, so the accumulators of output tile t ARE the B fragments of k-steps
 // 4t .. 4t + 3 of the next layer: activations never leave the lane's registers (no LDS slab: at hidden 256
 // the 16 input tiles and the 16 output tiles are 128 VGPRs of the 512 a one-wave-per-SIMD block may hold).
 // The hidden width is padded to HP = 16 T, T in {1, 2, 4, 8, 16}, with zero weights and biases; the input

@@ -28,7 +28,7 @@ KERNELS = ["solo", "group4", "group8", "split1", "split2", "split4", "team"]
 
 
 def team_ok(hidden, ln, n_layers, K, S=20, A=6):
-    """Shapes the small-K team kernel takes (capi.cpp bcmpc_create): the 2-layer delta net, hidden <= 512
+    """Shapes the small-K team kernel takes (engine_plan.cpp plan_engine): the 2-layer delta net, hidden <= 512
     (LayerNorm: <= 256), the whole grid resident (ceil(K/128)*8 workgroups x members <= 256 CUs)."""
     hp = next(p for p in (64, 128, 256, 512, 768, 1024) if hidden <= p)
     members = 4 if hp == 512 else 1
@@ -341,7 +341,7 @@ def _split_policy_ok(hidden, act, ln):
 
 
 def team_policy_ok(hidden, act, ln, K, ph, pl):
-    """Shapes the team kernel takes with a fused policy (capi.cpp bcmpc_create): <= 2 x 128 policy; dynamics
+    """Shapes the team kernel takes with a fused policy (engine_plan.cpp plan_engine): <= 2 x 128 policy; dynamics
     hidden 65..256 with any activation / LayerNorm (one workgroup per column: ceil(K/128)*8 <= 256 CUs) or
     449..512 tanh without LayerNorm (4 members per column)."""
     if ph > 128 or pl > 2 or K < 1:

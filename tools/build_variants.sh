@@ -16,7 +16,7 @@ SPLIT="rollout_x3.h rollout_pp.h rollout_x3_plain.hip rollout_x3.hip rollout_pp.
 X3=0
 if [ "${1:-}" = "-p" ]; then X3=2; shift; fi
 make -s -j8 ARCH=gfx950 >/dev/null
-HOST="capi mt_draw planners"
+HOST="capi engine_plan pack mt_draw planners"
 HOSTOBJ=""
 for u in $HOST; do
   $H -x hip -c bc_mpc_amd/csrc/$u.cpp -o build/variants/$u.o

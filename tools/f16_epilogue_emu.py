@@ -3,7 +3,7 @@
 alternative tanh epilogues, scored against the f32-grade oracle on cfg3's net (build a cheaper
 epilogue only if its +-10 penalty-flip count over 2,000 cfg3 candidates holds against today's).
 
-The emulated kernel, per step and candidate (capi.cpp pack_x3_layer, rollout_pp.h rollout_pp FOLD):
+The emulated kernel, per step and candidate (pack.cpp pack_x3_layer, rollout_pp.h rollout_pp FOLD):
 * layer-0 input [normalised state, normalised action] rounded to f16 (no operand scale, clamped to +-65504);
 * hidden-producing layers (dense, dense_1) packed f16(W * 2 log2 e), accumulated in f32 from the bias
   * 2 log2 e (f16 x f16 products are exact in f32), so the accumulator is z = 2 log2(e) y;

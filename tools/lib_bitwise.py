@@ -8,7 +8,10 @@ usage: python tools/lib_bitwise.py LIB_A LIB_B [--precision f16] [--K 65536] [--
            every output of the named synchronous entry points (ENTRIES below) at the 2 x 500 tanh net: records,
            costs, mu, sigma and MPPI statistics, each compared byte for byte.  The *_ln entries run get_action on
            LayerNorm nets (the host's LayerNorm packing: 2 x 256 relu + LN in split precision and in fp32, the
-           reward net with LayerNorm in fp32 and on the team kernel).  The *_giveup entries need a team engine:
+           reward net with LayerNorm in fp32 and on the team kernel; get_action_ln_team: the 2 x 256 relu + LN net
+           on the team kernel at K = 400, the deferred LayerNorm).  get_action_policy_*: a fused-policy engine in
+           fp32 (dynamics hidden 128) and in split precision (hidden 500), policy 2 x 64.  get_action_value:
+           get_action with a terminal value set (value net 2 x 64).  The *_giveup entries need a team engine:
            they halve K from --K until the team grid fits the device, so they may run below --K (the layout and
            num_paths of every entry are printed)
 Each build runs in its own child process (BCMPC_LIB), one after the other, under its own time limit; exit
@@ -49,13 +52,18 @@ ENTRIES = {
     "get_action_ln": (0, False, None, False, "ln"), "get_action_ln_fp32": (0, False, None, False, "ln_fp32"),
     "get_action_reward_ln": (0, False, None, False, "reward_ln"),
     "get_action_reward_ln_team": (0, False, None, False, "reward_ln_team"),
+    "get_action_ln_team": (0, False, None, False, "ln_team"),
+    "get_action_policy_fp32": (0, False, None, False, "policy_fp32"),
+    "get_action_policy_split": (0, False, None, False, "policy_split"),
+    "get_action_value": (0, False, None, False, "value"),
 }
 
 ENTRY_CHILD = r"""
 import ctypes, os, sys, numpy as np
 sys.path.insert(0, {repo!r})
 from bc_mpc_amd import ensemble
-from bc_mpc_amd.engine import MLPSpec, RolloutEngine
+from bc_mpc_amd.engine import MLPSpec, PolicySpec, RolloutEngine
+from bc_mpc_amd.value import ValueSpec
 from oracle import mpc_oracle as orc
 S, A, HID = 20, 6, 500
 K, H, B, PREC, ENTRIES, NAMES = {K}, {H}, {B}, {prec!r}, {entries!r}, {names!r}
@@ -66,11 +74,16 @@ rs = np.random.RandomState(5)
 mu0, sd0 = rs.uniform(-0.6, 0.6, (B, H, A)), rs.uniform(0.1, 0.6, (B, H, A))
 
 
-# net -> (hidden, activation, LayerNorm, reward model, precision or None: PREC, kernel or None, K or None: --K)
+# net -> (hidden, activation, LayerNorm, reward model, precision or None: PREC, kernel or None, K or None: --K
+#         [, extra: "policy" a fused 2 x 64 policy, "value" a 2 x 64 terminal value])
 NETS = {{"tanh": (HID, "tanh", False, False, None, None, None), "ln": (256, "relu", True, False, None, None, None),
         "ln_fp32": (256, "relu", True, False, "fp32", None, None),
         "reward_ln": (128, "tanh", True, True, None, None, None),
-        "reward_ln_team": (500, "tanh", True, True, None, "team", 400)}}
+        "reward_ln_team": (500, "tanh", True, True, None, "team", 400),
+        "ln_team": (256, "relu", True, False, None, "team", 400),
+        "policy_fp32": (128, "tanh", False, False, "fp32", None, None, "policy"),
+        "policy_split": (HID, "tanh", False, False, "split", None, None, "policy"),
+        "value": (HID, "tanh", False, False, None, None, None, "value")}}
 
 
 def spec(member, net="tanh"):
@@ -98,16 +111,31 @@ def flat(x):
     return out
 
 
+def value_spec(hidden=64, layers=2):
+    rs = np.random.RandomState(77)
+    dims = [S] + [hidden] * layers + [1]
+    ks = [(rs.standard_normal((i, o)) / np.sqrt(i)).astype(np.float32) for i, o in zip(dims[:-1], dims[1:])]
+    bs = [(0.1 * rs.standard_normal(o)).astype(np.float32) for o in dims[1:]]
+    return ValueSpec(ks, bs, norm[0].astype(np.float32), (norm[1] + 0.1).astype(np.float32))
+
+
 def engine(members, n, kernel=None, net="tanh"):
-    hid, act, ln, reward, prec, nkernel, nk = NETS[net]
+    hid, act, ln, reward, prec, nkernel, nk = NETS[net][:7]
+    extra = NETS[net][7] if len(NETS[net]) > 7 else None
     if net != "tanh":
         rnorm = orc.synthetic_normalization(seed=31, reward=True) if reward else norm
+        pol = dict(policy_hidden=64, policy_layers=2, policy_mode="explore") if extra == "policy" else {{}}
         eng = RolloutEngine(S, A, hid, 2, act, ln, H, nk or n, device=0, kernel=nkernel,
                             precision=None if nkernel else (prec or PREC), cost="reward" if reward else "cheetah",
-                            model="reward" if reward else "delta")
+                            model="reward" if reward else "delta", **pol)
         eng.set_weights(spec(0, net), rnorm, 1)
         if reward:
             eng.set_discount(0.95)
+        if extra == "policy":
+            p = orc.synthetic_policy(S, A, 64, 2)
+            eng.set_policy(PolicySpec(p.kernels, p.biases, p.ob_mean, p.ob_std, p.logstd), 0.25, 1)
+        if extra == "value":
+            eng.set_terminal_value(value_spec(), -0.5, 1)
         return eng
     if members:
         eng = ensemble.EnsembleEngine(members, S, A, HID, 2, "tanh", False, H, n, device=0, precision=PREC)

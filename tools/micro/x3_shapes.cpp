@@ -6,18 +6,7 @@
 #include <cstddef>
 #include <cstdio>
 
-namespace bcmpc {   // (as kernels.h declares them)
-int x3_waves(int hidden_padded);
-int x3_max_nc(int hidden_padded);
-size_t x3_lds(int hidden_padded, int n_layers, int nc, int action_dim, int policy_layers, int policy_hidden_padded,
-              int ak);
-bool x3_policy_ok(int hidden_padded, int nc);
-bool x3_f16_layout_ok(int hidden_padded, int nc, int nw);
-size_t x3_f16_lds(int hidden_padded, int n_layers, int nc, int nw, int action_dim);
-bool x3_pp_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);
-bool x3_pp3_ok(int hidden_padded, int n_layers, int state_dim, int action_dim);
-size_t x3_pp3_lds(int hidden_padded, int state_dim, int action_dim);
-}  // namespace bcmpc
+#include "../../bc_mpc_amd/csrc/shapes.h"
 
 int main() {
     using namespace bcmpc;

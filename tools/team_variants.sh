@@ -7,10 +7,10 @@ cd "$(dirname "$0")/.."
 mkdir -p build/variants
 H="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -DBCMPC_DIAG_VARIANT"
 make -s -j8 ARCH=gfx950 >/dev/null
-HOST="capi mt_draw planners"
+HOST="capi engine_plan pack mt_draw planners"
 # the in-tree build's other objects
 OBJS=$(ls build/*.o | grep -v -E "/(${HOST// /|}|rollout_team)\.o$")
-# the host units are rebuilt with each variant's flags: the host weight packing (capi.cpp) and the kernel must agree
+# the host units are rebuilt with each variant's flags: the host weight packing (pack.cpp) and the kernel must agree
 # on the compile-time switches they share (TEAM_DEFER: the output layer packed for the deferred LayerNorm or not)
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}

@@ -31,7 +31,7 @@ READING = {
 
 
 def weight_bytes(hp, L, precision):
-    """Packed fragment bytes (capi.cpp pack_x3_layer): layer 0 one k-step, hidden layers P k-steps, the
+    """Packed fragment bytes (pack.cpp pack_x3_layer): layer 0 one k-step, hidden layers P k-steps, the
     output layer 2 tiles; 2 KiB per (tile, k-step) as hi | lo, 1 KiB hi only for the single pass."""
     T, P = hp // 16, hp // 32
     frags = T + (L - 1) * T * P + 2 * P
