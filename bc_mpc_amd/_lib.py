@@ -32,6 +32,8 @@ ACT_TANH, ACT_RELU = 0, 1
 COST_CHEETAH, COST_NONE, COST_REWARD, COST_TERMS = 0, 1, 2, 3
 MAX_COST_TERMS = 32
 TERM_THRESHOLD, TERM_DIFF, TERM_LINEAR, TERM_QUADRATIC = range(4)
+TERM_RATE = 4               # bcmpc_cost_term_x alone (bcmpc_set_cost_terms_x)
+MAX_REF_CHANNELS = 16
 SRC_STATE, SRC_NEXT_STATE, SRC_ACTION = range(3)
 CMP_GE, CMP_GT, CMP_LE, CMP_LT = range(4)
 MAX_MEMBERS = 16
@@ -139,6 +141,14 @@ class CostTerm(ctypes.Structure):
     ]
 
 
+class CostTermX(ctypes.Structure):
+    """bcmpc_cost_term_x (48 bytes): a term that may name a reference channel (``ref``, -1: none) or be a RATE."""
+    _fields_ = CostTerm._fields_ + [
+        ("ref", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
 class Elite(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_double), ("index", ctypes.c_int64)]
 
@@ -231,6 +241,15 @@ SIGNATURES = [
       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     ("bcmpc_last_termination_steps", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("bcmpc_set_cost_terms_x", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(CostTermX), ctypes.c_int32, ctypes.c_int32]),
+    ("bcmpc_set_cost_inputs", ctypes.c_int, [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.c_int32, _DP, ctypes.c_int32]),
+    ("bcmpc_trajectory_cost_inputs_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_cost_input_buffers", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_get_action", ctypes.c_int,
      [ctypes.c_void_p, _DP, _DP, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(Result), _DP]),
     ("bcmpc_get_actions_batch", ctypes.c_int,

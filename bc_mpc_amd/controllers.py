@@ -138,6 +138,55 @@ def _device_terms(cost_fn, S: int, A: int):
     return None
 
 
+def _cost_inputs(ctrl, reference, previous_action, batch: bool):
+    """A call's ``reference`` / ``previous_action`` checked against the controller's cost and brought to the
+    engine's form -- ``(reference [B or 1, 1 or H, R] or None, previous_action [B or 1, A] or None)`` -- or
+    ValueError.  Called first in ``get_action`` / ``get_actions``: before any seed or ``np.random`` draw and
+    before an engine is built or touched.  The controllers do not remember their last action."""
+    cost_fn = ctrl.cost_fn
+    if reference is None and previous_action is None and not isinstance(cost_fn, TermCost):
+        return None, None
+    S, A, _ = _shape(ctrl)
+    terms = _device_terms(cost_fn, S, A)
+    n_ref = terms.n_ref if terms is not None else 0
+    who, lead = type(ctrl).__name__, "[B, " if batch else "["
+    ref = prev = None
+    if reference is None:
+        if n_ref:
+            raise ValueError(f"{who}: the cost names reference channels (n_ref = {n_ref}): pass reference=")
+    else:
+        if not n_ref:
+            raise ValueError(f"{who}: reference= needs a TermCost with ref(c) values; this cost names no channel")
+        ref = np.asarray(reference, dtype=np.float64)
+        H = int(ctrl.horizon)
+        if ref.ndim not in ((2, 3) if batch else (1, 2)) or (ref.ndim == 2 + batch and ref.shape[-2] != H):
+            raise ValueError(f"{who}: reference must be {lead}R] or {lead}H, R] with H = {H}, not {ref.shape}")
+        if ref.shape[-1] < n_ref:
+            raise ValueError(f"{who}: the reference has {ref.shape[-1]} channels, the cost names {n_ref}")
+        ref = ref.reshape((ref.shape[0] if batch else 1, -1, ref.shape[-1]))
+    if previous_action is not None:
+        if terms is None or not terms.uses_rate:
+            raise ValueError(f"{who}: previous_action= needs a TermCost with rate terms")
+        prev = np.asarray(previous_action, dtype=np.float64)
+        if prev.ndim != 1 + batch or prev.shape[-1] != A:
+            raise ValueError(f"{who}: previous_action must be {lead}A] with A = {A}, not {prev.shape}")
+        prev = prev.reshape(-1, A)
+    return ref, prev
+
+
+def _batch_inputs_check(ctrl, inputs, B: int) -> None:
+    for name, x in zip(("reference", "previous_action"), inputs):
+        if x is not None and x.shape[0] != B:
+            raise ValueError(f"{type(ctrl).__name__}: {name} is for {x.shape[0]} environments, states for {B}")
+
+
+def _send_cost_inputs(ctrl, eng, terms) -> None:
+    """The call's inputs to an engine whose cost takes them (after ``set_cost_terms``; every member of an
+    ensemble, every rank's shard engine)."""
+    if terms is not None and terms.extended:
+        eng.set_cost_inputs(*getattr(ctrl, "_inputs", (None, None)))
+
+
 def _opt(terms) -> tuple:
     """The trailing ``terms`` argument of the ``_engine_for`` methods, passed only when there is one (a
     subclass or test double that replaces ``_engine_for`` with the earlier signature keeps working)."""
@@ -423,6 +472,7 @@ class Planner(_TerminalValue, Controller):
                              model=spec.model)
         if terms is not None:
             eng.set_cost_terms(terms)
+            _send_cost_inputs(self, eng, terms)
         if reward:
             eng.set_discount(float(self.gamma))
         if reward and self.terminal_value is not None:
@@ -438,7 +488,10 @@ class Planner(_TerminalValue, Controller):
         self._batch_engine = self._cached("batch", spec, S, A, k_total, terms)
         return self._batch_engine
 
-    def get_action(self, state):
+    def get_action(self, state, reference=None, previous_action=None):
+        """``reference`` (``[R]`` or ``[H, R]``) and ``previous_action`` (``[A]``): the inputs of a ``TermCost``
+        with ``ref(c)`` values / ``rate`` terms (cost_functions.py), explicit on every call."""
+        self._inputs = _cost_inputs(self, reference, previous_action, False)
         S, A, K = _shape(self)
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
@@ -465,17 +518,20 @@ class Planner(_TerminalValue, Controller):
         eng.set_weights(spec, norm, version)
         return self._solve(eng, state, mu0, sd0, seed, K)
 
-    def get_actions(self, states):
+    def get_actions(self, states, reference=None, previous_action=None):
         """Batched control step: ``states`` is ``[B, S]``, one independent answer per row with
         ``num_simulated_paths`` candidates each, all environments in one launch chain.  Every environment
         keeps its own warm-start plan (see ``reset``); one seed is drawn per call.  Returns ``[B, A]``
         float64; ``last_mu`` is ``[B, H, A]`` and the other ``last_*`` hold one entry per environment.  One
-        rank only."""
+        rank only.  ``reference`` (``[B, R]`` or ``[B, H, R]``) and ``previous_action`` (``[B, A]``): every
+        environment's inputs of a ``TermCost`` with ``ref(c)`` values / ``rate`` terms."""
         if getattr(self.dyn_model, "is_ensemble", False):
             raise NotImplementedError(f"batched {self._KIND} over an EnsembleDynamicsModel is not built yet: "
                                       "use get_action")
+        self._inputs = _cost_inputs(self, reference, previous_action, True)
         S, A, K = _shape(self)
         states = self._plan_states(states, S)
+        _batch_inputs_check(self, self._inputs, states.shape[0])
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
         spec, norm, version, terms = self._model(S, A)
@@ -541,6 +597,7 @@ class MPCcontroller(_TerminalValue, Controller):
                              spec.layer_norm, int(self.horizon), int(k), device=_device(self), cost=cost)
         if terms is not None:
             eng.set_cost_terms(terms)
+            _send_cost_inputs(self, eng, terms)
         return eng
 
     def _engine_for(self, spec, S, A, k_local, fused, terms=None) -> RolloutEngine:
@@ -557,7 +614,10 @@ class MPCcontroller(_TerminalValue, Controller):
         return int(src.randint(0, 2**62, dtype=np.int64))
 
     # controllers.py:57-88
-    def get_action(self, state):
+    def get_action(self, state, reference=None, previous_action=None):
+        """``reference`` (``[R]`` or ``[H, R]``) and ``previous_action`` (``[A]``): the inputs of a ``TermCost``
+        with ``ref(c)`` values / ``rate`` terms (cost_functions.py), explicit on every call."""
+        self._inputs = _cost_inputs(self, reference, previous_action, False)
         if getattr(self.dyn_model, "is_ensemble", False):   # an EnsembleDynamicsModel (ensemble.py)
             from . import ensemble as _ensemble
             return _ensemble.mpc_get_action(self, state)
@@ -648,19 +708,23 @@ class MPCcontroller(_TerminalValue, Controller):
             return opt_action_path[0].copy()
         return first_g
 
-    def get_actions(self, states):
+    def get_actions(self, states, reference=None, previous_action=None):
         """Batched control step (not in the reference): ``states`` is ``[B, S]``, one independent
         random-shooting answer per row with ``num_simulated_paths`` candidates each, all rolled out in one
         launch chain (``RolloutEngine.get_actions``).  Returns ``[B, A]`` float64.  Row ``b`` is what
         ``get_action(states[b])`` returns on the Philox candidates ``b*K .. (b+1)*K`` of the call's seed
         (one seed is drawn per call, as ``get_action`` draws one).  ``rng="device"`` on one rank with the
-        fused cheetah cost or a ``TermCost`` only."""
+        fused cheetah cost or a ``TermCost`` only.  ``reference`` (``[B, R]`` or ``[B, H, R]``) and
+        ``previous_action`` (``[B, A]``): every environment's inputs of a ``TermCost`` with ``ref(c)`` values /
+        ``rate`` terms."""
+        self._inputs = _cost_inputs(self, reference, previous_action, True)
         if getattr(self.dyn_model, "is_ensemble", False):
             from . import ensemble as _ensemble
             return _ensemble.mpc_get_actions(self, states)
         _batch_rng_check(self.rng)
         S, A, K = _shape(self)
         states = _batch_states(states, S, self._group)
+        _batch_inputs_check(self, self._inputs, states.shape[0])
         spec, norm, version = _weights.extract(self.dyn_model)
         if spec.model != "delta":
             raise TypeError("MPCcontroller needs an NNDynamicsModel; use MPCcontrollerReward")

@@ -9,6 +9,8 @@ decides whether a given callable may be fused.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 
@@ -53,23 +55,57 @@ def trajectory_cost_fn(cost_fn, states, actions, next_states):
 #   progress   acc = acc + weight * ((s'[index] - s[index]) / dt)
 #   linear     acc = acc + weight * x
 #   quadratic  d = x - target; acc = acc + weight * (d * d)
-# every operation one IEEE f64 operation.  TermCost.__call__ below IS that definition (NumPy f64, elementwise,
-# term order); the kernel is tested against it bit for bit.
-THRESHOLD, DIFF, LINEAR, QUADRATIC = range(4)
+#   rate       d = a_h[index] - a_{h-1}[index]; acc = acc + weight * (d * d)
+# every operation one IEEE f64 operation.  A threshold's value and a quadratic's target may be ``ref(c)``:
+# channel c of the reference the CALL carries (row h of it at step h), read in place of the constant.
+# TermCost.__call__ below IS that definition (NumPy f64, elementwise, term order); the kernels are tested
+# against it bit for bit.
+THRESHOLD, DIFF, LINEAR, QUADRATIC, RATE = range(5)
 STATE, NEXT_STATE, ACTION = range(3)
 GE, GT, LE, LT = range(4)
 MAX_TERMS = 32
+MAX_SLOTS = 32      # what the kernel loads per row: the state dims, the actions and the channels the entries name
+MAX_REF = 16        # channels of a call's reference
 _SOURCES = {"state": STATE, "next_state": NEXT_STATE, "action": ACTION}
 _CMPS = {">=": GE, ">": GT, "<=": LE, "<": LT}
 _CMP_FN = {GE: np.greater_equal, GT: np.greater, LE: np.less_equal, LT: np.less}
 
 
+class Ref:
+    """``ref(c)``: channel c of the call's reference, where a threshold's value or a quadratic's target stands."""
+    __slots__ = ("channel",)
+
+    def __init__(self, channel):
+        c = int(channel)
+        if c != channel or c < 0 or c >= MAX_REF:
+            raise ValueError(f"a reference channel must be an integer in [0, {MAX_REF}), not {channel!r}")
+        self.channel = c
+
+    def __repr__(self):
+        return f"ref({self.channel})"
+
+
+def ref(channel) -> Ref:
+    """Placeholder for "channel ``channel`` of the call's reference": ``threshold(i, op, ref(c), w)`` and
+    ``quadratic(i, w, target=ref(c))`` read ``reference[h][c]`` at step h, whatever their ``on=``."""
+    return Ref(channel)
+
+
+def _no_ref(what, v):
+    if isinstance(v, Ref):
+        raise ValueError(f"{what} takes a constant: a reference channel stands only for a threshold's value or a "
+                         "quadratic's target")
+    return v
+
+
 class Term(tuple):
-    """One term: ``(kind, source, index, cmp, weight, param)`` (bcmpc_cost_term's fields)."""
+    """One term: ``(kind, source, index, cmp, weight, param)`` (bcmpc_cost_term's fields); a term whose param is
+    a reference channel has the channel as a seventh entry (bcmpc_cost_term_x's ``ref``)."""
     __slots__ = ()
 
-    def __new__(cls, kind, source, index, cmp, weight, param):
-        return super().__new__(cls, (int(kind), int(source), int(index), int(cmp), float(weight), float(param)))
+    def __new__(cls, kind, source, index, cmp, weight, param, ref=-1):
+        t = (int(kind), int(source), int(index), int(cmp), float(weight), float(param))
+        return super().__new__(cls, t if ref == -1 else t + (int(ref),))
 
     kind = property(lambda self: self[0])
     source = property(lambda self: self[1])
@@ -77,6 +113,7 @@ class Term(tuple):
     cmp = property(lambda self: self[3])
     weight = property(lambda self: self[4])
     param = property(lambda self: self[5])
+    ref = property(lambda self: self[6] if len(self) > 6 else -1)
 
 
 def _source(on) -> int:
@@ -89,23 +126,33 @@ def threshold(index, op, value, weight, on="state") -> Term:
     """``+ weight`` where ``x op value`` (op one of ``>=  >  <=  <``); nothing where it is false or NaN."""
     if op not in _CMPS:
         raise ValueError(f"op must be one of {sorted(_CMPS)}, not {op!r}")
+    if isinstance(value, Ref):
+        return Term(THRESHOLD, _source(on), index, _CMPS[op], weight, 0.0, value.channel)
     return Term(THRESHOLD, _source(on), index, _CMPS[op], weight, value)
 
 
 def progress(index, dt, weight=-1.0) -> Term:
     """``+ weight * ((next_state[index] - state[index]) / dt)``: with the default weight, forward velocity
     along ``index`` is rewarded (``cheetah_cost_fn``'s last line is ``progress(17, 0.01)``)."""
-    return Term(DIFF, STATE, index, GE, weight, dt)
+    return Term(DIFF, STATE, index, GE, _no_ref("progress", weight), _no_ref("progress", dt))
 
 
 def linear(index, weight, on="state") -> Term:
     """``+ weight * x``."""
-    return Term(LINEAR, _source(on), index, GE, weight, 0.0)
+    return Term(LINEAR, _source(on), index, GE, _no_ref("linear", weight), 0.0)
 
 
 def quadratic(index, weight, target=0.0, on="state") -> Term:
     """``+ weight * (x - target)**2`` (``on="action"``, target 0: one summand of ``weight * sum(a**2)``)."""
+    if isinstance(target, Ref):
+        return Term(QUADRATIC, _source(on), index, GE, weight, 0.0, target.channel)
     return Term(QUADRATIC, _source(on), index, GE, weight, target)
+
+
+def rate(index, weight) -> Term:
+    """``+ weight * (a_h[index] - a_{h-1}[index])**2``, the action-rate penalty.  ``a_{-1}`` is the call's
+    ``previous_action``; a call without one takes ``a_{-1} := a_0``."""
+    return Term(RATE, ACTION, index, GE, _no_ref("rate", weight), 0.0)
 
 
 def done_when(index, op, value) -> Term:
@@ -114,7 +161,7 @@ def done_when(index, op, value) -> Term:
     Hopper's ``not healthy`` is ``done_when(0, "<=", 0.7), done_when(1, ">=", 0.2), done_when(1, "<=", -0.2)``."""
     if op not in _CMPS:
         raise ValueError(f"op must be one of {sorted(_CMPS)}, not {op!r}")
-    return Term(THRESHOLD, NEXT_STATE, index, _CMPS[op], 0.0, value)
+    return Term(THRESHOLD, NEXT_STATE, index, _CMPS[op], 0.0, _no_ref("done_when", value))
 
 
 class TermCost:
@@ -126,7 +173,11 @@ class TermCost:
 
     ``done``: conditions built by ``done_when`` that end a candidate's episode, ``done_cost``: a finite cost
     added once at the terminating step.  Neither changes ``__call__`` (the per-step cost); ``episode_cost`` is the
-    definition of what the planners then minimise.  Terms plus conditions are at most 32."""
+    definition of what the planners then minimise.  Terms plus conditions are at most 32.
+
+    A cost with ``ref(c)`` values or ``rate`` terms takes the call's ``reference`` / ``previous_action``
+    (``__call__``, ``episode_cost``, the controllers' keywords); what its entries read per row -- state dims,
+    actions and channels, each counted once -- is at most 32 slots."""
 
     def __init__(self, terms=(), done=(), done_cost=0.0):
         self.terms = tuple(t if isinstance(t, Term) else Term(*t) for t in terms)
@@ -142,12 +193,15 @@ class TermCost:
         for i, t in enumerate(self.done_conditions):
             if t.kind != THRESHOLD or t.source != NEXT_STATE or t.cmp not in (GE, GT, LE, LT):
                 raise ValueError(f"done condition {i}: not a done_when(index, op, value) condition")
+            if t.ref != -1:
+                raise ValueError(f"done condition {i}: a done condition compares with a constant, not a reference "
+                                 "channel")
             if t.index < 0:
                 raise ValueError(f"done condition {i}: negative index {t.index}")
             if not np.isfinite(t.param) or t.weight != 0.0:
                 raise ValueError(f"done condition {i}: the value must be finite (and the weight 0)")
         for i, t in enumerate(self.terms):
-            if t.kind not in (THRESHOLD, DIFF, LINEAR, QUADRATIC):
+            if t.kind not in (THRESHOLD, DIFF, LINEAR, QUADRATIC, RATE):
                 raise ValueError(f"term {i}: unknown kind {t.kind}")
             if t.source not in (STATE, NEXT_STATE, ACTION):
                 raise ValueError(f"term {i}: unknown source {t.source}")
@@ -161,6 +215,29 @@ class TermCost:
                 raise ValueError(f"term {i}: weight and param must be finite")
             if t.kind == DIFF and t.param == 0.0:
                 raise ValueError(f"term {i}: a progress term's dt must not be 0")
+            if t.kind == RATE and t.source != ACTION:
+                raise ValueError(f"term {i}: a rate term reads the action")
+            if t.ref != -1:
+                if t.kind not in (THRESHOLD, QUADRATIC):
+                    raise ValueError(f"term {i}: a reference channel stands only for a threshold's value or a "
+                                     "quadratic's target")
+                if t.ref < 0 or t.ref >= MAX_REF:
+                    raise ValueError(f"term {i}: reference channel {t.ref} outside [0, {MAX_REF})")
+        self.n_ref = 1 + max((t.ref for t in self.terms), default=-1)
+        self.uses_rate = any(t.kind == RATE for t in self.terms)
+        entries = self.terms + self.done_conditions
+        self.n_slots = (len({t.index for t in entries if t.source != ACTION}) +
+                        len({t.index for t in entries if t.source == ACTION}) +
+                        len({t.ref for t in self.terms if t.ref != -1}))
+        if self.n_slots > MAX_SLOTS:
+            raise ValueError(f"a TermCost reads at most {MAX_SLOTS} slots per row (state dims, actions and reference "
+                             f"channels, each counted once), this one needs {self.n_slots}")
+
+    @property
+    def extended(self) -> bool:
+        """Whether the cost names a reference channel or has a rate term (the engine then takes it through
+        bcmpc_set_cost_terms_x and scores it with the kernel instances of csrc/term_cost_x.hip)."""
+        return self.n_ref > 0 or self.uses_rate
 
     def key(self):
         """What identifies the cost: the terms alone without ``done`` (as before there was one), else also the
@@ -198,27 +275,49 @@ class TermCost:
         return (f"TermCost({list(map(tuple, self.terms))}, done={list(map(tuple, self.done_conditions))}, "
                 f"done_cost={self.done_cost!r})")
 
-    def __call__(self, state, action, next_state):
+    def _reference(self, reference, batch):
+        """``reference`` broadcast to ``batch + (R,)``, or None for a cost that names no channel."""
+        if self.n_ref == 0:
+            return None
+        if reference is None:
+            raise ValueError(f"the cost names reference channels (n_ref = {self.n_ref}): a reference is needed")
+        r = np.asarray(reference, dtype=np.float64)
+        if r.ndim < 1 or r.shape[-1] < self.n_ref:
+            raise ValueError(f"the reference has {r.shape[-1] if r.ndim else 0} channels, the cost names "
+                             f"{self.n_ref}")
+        return np.broadcast_to(r, tuple(batch) + (r.shape[-1],))
+
+    def __call__(self, state, action, next_state, reference=None, previous_action=None):
+        """The per-step cost.  ``reference``: broadcastable to ``[..., R]`` (needed when the cost names a channel);
+        ``previous_action``: broadcastable to ``[..., A]``, the ``a_{h-1}`` of the rate terms (None: ``action``)."""
         s, a, ns = (np.asarray(x, dtype=np.float64) for x in (state, action, next_state))
         src = (s, ns, a)
+        r = self._reference(reference, s.shape[:-1])
+        pa = a if previous_action is None else np.broadcast_to(np.asarray(previous_action, dtype=np.float64), a.shape)
         acc = np.zeros(s.shape[:-1])
-        for t in self.terms:
-            x = src[t.source][..., t.index]
-            if t.kind == THRESHOLD:
-                acc = np.where(_CMP_FN[t.cmp](x, t.param), acc + t.weight, acc)
-            elif t.kind == DIFF:
-                acc = acc + t.weight * ((ns[..., t.index] - x) / t.param)
-            elif t.kind == LINEAR:
-                acc = acc + t.weight * x
-            else:
-                d = x - t.param
-                acc = acc + t.weight * (d * d)
+        # (a non-finite reference or action is legal data; a plain cost warns as it always did)
+        with np.errstate(invalid="ignore", over="ignore") if self.extended else contextlib.nullcontext():
+            for t in self.terms:
+                x = src[t.source][..., t.index]
+                p = t.param if t.ref == -1 else r[..., t.ref]
+                if t.kind == THRESHOLD:
+                    acc = np.where(_CMP_FN[t.cmp](x, p), acc + t.weight, acc)
+                elif t.kind == DIFF:
+                    acc = acc + t.weight * ((ns[..., t.index] - x) / t.param)
+                elif t.kind == LINEAR:
+                    acc = acc + t.weight * x
+                elif t.kind == RATE:
+                    d = x - pa[..., t.index]
+                    acc = acc + t.weight * (d * d)
+                else:
+                    d = x - p
+                    acc = acc + t.weight * (d * d)
         return acc if acc.ndim else float(acc)
 
 
-def episode_cost(term_cost, states, actions, next_states):
-    """THE definition of a ``TermCost`` with ``done`` over a horizon (csrc/term_cost.hip is tested against it bit
-    for bit): ``states`` / ``next_states`` ``[H, K, S]``, ``actions`` ``[H, K, A]`` ->
+def episode_cost(term_cost, states, actions, next_states, reference=None, previous_action=None):
+    """THE definition of a ``TermCost`` over a horizon (csrc/term_cost.hip and csrc/term_cost_x.hip are tested
+    against it bit for bit): ``states`` / ``next_states`` ``[H, K, S]``, ``actions`` ``[H, K, A]`` ->
     ``(costs [K] f64, term_step [K] int32)``.  For every candidate
 
         total = 0.0; t = H
@@ -227,16 +326,26 @@ def episode_cost(term_cost, states, actions, next_states):
             if term_cost.done(next_states[h]):  total = total + done_cost; t = h; break
 
     each operation one f64 operation in this order.  ``t == H`` exactly where the candidate never terminated.
-    Without conditions this is ``trajectory_cost_fn(term_cost, ...)`` bit for bit and ``t == H`` everywhere."""
+    Without conditions this is ``trajectory_cost_fn(term_cost, ...)`` bit for bit and ``t == H`` everywhere.
+
+    ``reference``: broadcastable to ``[H, K, R]`` -- step h reads row h, so ``[R]`` is that row repeated H times.
+    ``previous_action``: broadcastable to ``[K, A]``, the rate terms' ``a_{-1}`` (None: ``actions[0]``); step h's
+    ``a_{h-1}`` is ``actions[h-1]``."""
     H = len(actions)
     shape = np.shape(states)[1:-1]
     total = np.zeros(shape, dtype=np.float64)
     step = np.full(shape, H, dtype=np.int32)
     alive = np.ones(shape, dtype=bool)
     dc = np.float64(term_cost.done_cost)
+    ref_rows = term_cost._reference(reference, (H,) + tuple(shape))
+    acts = np.asarray(actions, dtype=np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
         for h in range(H):
-            c = term_cost(states[h], actions[h], next_states[h])
+            if ref_rows is None and not term_cost.uses_rate:
+                c = term_cost(states[h], actions[h], next_states[h])
+            else:
+                prev = acts[h - 1] if h > 0 else (acts[0] if previous_action is None else previous_action)
+                c = term_cost(states[h], acts[h], next_states[h], None if ref_rows is None else ref_rows[h], prev)
             total = np.where(alive, total + c, total)
             d = alive & term_cost.done(next_states[h])
             total = np.where(d, total + dc, total)

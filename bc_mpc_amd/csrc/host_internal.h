@@ -190,6 +190,18 @@ struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, 
     double done_cost = 0.0;
     int32_t* d_tc_steps = nullptr;
     bool steps_on_fb = false;
+    // reference tracking (term_cost_x.hip; bcmpc_set_cost_terms_x / bcmpc_set_cost_inputs).  tc_x: the list names
+    // a channel or has a RATE term (RATE sits in tc_terms as kind 4); tc_refs: every term's channel or -1, empty
+    // for a plain list; tcx: what digest_terms adds to tc for those instances.  The inputs: device buffers that
+    // bcmpc_set_cost_inputs allocates (they only grow) and fills, with host copies for the fallback engine
+    bool tc_x = false;
+    std::vector<int32_t> tc_refs;
+    TermCostXArgs tcx{};
+    bool has_inputs = false;
+    double *d_tc_ref = nullptr, *d_tc_prev = nullptr;
+    size_t tc_ref_cap = 0, tc_prev_cap = 0;             // in doubles
+    int32_t in_ref_envs = 0, in_ref_steps = 0, in_prev_envs = 0;    // in_prev_envs == 0: no previous action
+    std::vector<double> h_in_ref, h_in_prev;
     // terminal value (terminal_value.hip): the launch template bcmpc_set_terminal_value builds.  The packed
     // kernels and the parameter block are allocated once at their largest size (a captured graph keeps the
     // addresses over a change of net); d_tc_traj, above, is allocated on first use for engines without terms
@@ -259,6 +271,7 @@ struct RolloutLaunch {
     hipStream_t stream = nullptr;
     const CemLaunch* cem = nullptr;
     bool record_events = true;              // (and bcmpc_engine_set_timing is on)
+    int32_t n_envs = 1;                     // environments the candidates belong to (the cost inputs of each)
     double* act_out_all = nullptr;          // policy engines: every step's actions [H][K][A]
 };
 int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r);

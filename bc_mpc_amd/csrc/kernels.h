@@ -262,6 +262,25 @@ struct TermCostArgs {
 };
 hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);
 
+// ---- reference tracking (term_cost_x.hip): lists with reference channels or RATE terms ----
+// An argument struct of its own, so that TermCostArgs and the instances of term_cost.hip stay as they are.  b is
+// read as there, with three differences.  The slots are the state dims, then the reference channels
+// (slot_action == 2, slot_index the channel), then the actions: slots [b.n_state_slots, b.n_state_slots +
+// n_ref_slots) are the channels.  A TermDev's meta has bit 6 set where its param is the channel slot in `pad`,
+// and bit 7 set for a RATE term (kind bits QUADRATIC).  Candidate k reads environment k / env_paths.
+struct TermCostXArgs {
+    TermCostArgs b;
+    const double* ref;                       // [ref_envs][ref_steps][n_ref] or nullptr (n_ref_slots == 0)
+    const double* prev;                      // [prev_envs][A] or nullptr: a_{-1} := a_0
+    int64_t env_paths;                       // K is a multiple of it
+    int64_t ref_env_stride;                  // ref_steps * n_ref, 0: one reference for all environments
+    int64_t ref_row_stride;                  // n_ref, 0: constant over the horizon
+    int64_t prev_env_stride;                 // A, 0: one previous action for all environments
+    int32_t n_ref_slots, n_ref;
+    int32_t has_rate;                        // the list has a RATE term: row -1 of the action slots is filled
+};
+hipError_t launch_term_cost_x(const TermCostXArgs& a, hipStream_t st);
+
 // ---- model ensembles (ensemble.hip): out[k] = rule over member_costs[0..E-1][k] ----
 struct EnsembleReduceArgs {
     const double* member_costs;              // [E][ld], row e = member e's costs

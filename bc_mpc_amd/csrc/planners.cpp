@@ -459,6 +459,7 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
         RolloutLaunch r;
         r.state = e->d_tiled; r.state_stride = c.state_dim; r.actions = e->d_actions; r.seed = seed;
         r.cand_offset = cand_offset; r.costs = e->d_costs; r.stream = st; r.record_events = false;
+        r.n_envs = n_envs;
         if (const int rc = rollout_impl(e, r)) return rc;
         if (costs_out)
             HIP_TRY(hipMemcpyAsync(costs_out + (size_t)it * c.num_paths, e->d_costs, sizeof(double) * c.num_paths,
@@ -751,7 +752,7 @@ int bcmpc_ensemble_get_actions_batch(bcmpc_ensemble* s, const double* states, in
     HIP_TRY(launch_tile_states(t, st));
     RolloutLaunch r;
     r.state = e0->d_tiled; r.state_stride = c.state_dim; r.actions = d_act; r.seed = seed; r.cand_offset = cand_offset;
-    r.stream = st; r.record_events = false;
+    r.stream = st; r.record_events = false; r.n_envs = n_envs;
     for (int32_t i = 0; i < E; ++i) {
         r.costs = s->d_member + (size_t)i * Ktot;
         if (const int rc = rollout_impl(s->m[i], r)) return rc;

@@ -208,6 +208,7 @@ class _EngineCalls:
         self._mt_fast = None        # get_action_numpy_stream's prepared ctypes arguments
         self._ga_fast = None        # get_action's (device actions, no cost vector) prepared ctypes arguments
         self.cost_terms = None      # the TermCost of a cost="terms" engine (set_cost_terms)
+        self._cost_inputs = None    # the arrays of the last set_cost_inputs
         self._value = None          # the terminal value the library holds (set_terminal_value)
 
     def _state(self, state) -> np.ndarray:
@@ -444,12 +445,17 @@ class RolloutEngine(_EngineCalls):
         """The objective of a ``cost="terms"`` engine (bcmpc_set_cost_terms): a ``cost_functions.TermCost``
         (or an iterable of its terms).  Every rollout entry raises until this has been called; calling it
         again replaces the list for the next launch.  A ``TermCost`` with ``done`` conditions also sets the
-        engine's termination (bcmpc_set_termination), one without removes it; idempotent on ``key()``."""
+        engine's termination (bcmpc_set_termination), one without removes it; idempotent on ``key()``.  A cost
+        with ``ref(c)`` values or ``rate`` terms goes through bcmpc_set_cost_terms_x, and the calls that follow
+        read what ``set_cost_inputs`` left; any other cost is sent exactly as before there were such terms."""
         from .cost_functions import TermCost
         tc = term_cost if isinstance(term_cost, TermCost) else TermCost(term_cost)
         if self.cost_terms is not None and tc.key() == self.cost_terms.key():
             return
         tc.validate(self.state_dim, self.action_dim)
+        if tc.extended:
+            self._set_cost_terms_x(tc)
+            return
 
         def pack(terms):
             arr = (_lib.CostTerm * max(1, len(terms)))()
@@ -470,6 +476,96 @@ class RolloutEngine(_EngineCalls):
             _lib.check(self._lib.bcmpc_set_termination(self._h, *pack(tc.done_conditions),
                                                        ctypes.c_double(tc.done_cost)))
         self.cost_terms = tc
+
+    def _set_cost_terms_x(self, tc) -> None:
+        """set_cost_terms for a cost with reference channels or rate terms: the termination first where the new
+        terms would not fit beside the conditions still held, as there."""
+        def pack(terms):
+            arr = (_lib.CostTerm * max(1, len(terms)))()
+            for dst, t in zip(arr, terms):
+                dst.kind, dst.source, dst.index, dst.cmp = t.kind, t.source, t.index, t.cmp
+                dst.weight, dst.param = t.weight, t.param
+            return arr, ctypes.c_int32(len(terms))
+
+        arr = (_lib.CostTermX * max(1, len(tc.terms)))()
+        for dst, t in zip(arr, tc.terms):
+            dst.kind, dst.source, dst.index, dst.cmp = t.kind, t.source, t.index, t.cmp
+            dst.weight, dst.param, dst.ref = t.weight, t.param, t.ref
+        held = self.cost_terms.done_conditions if self.cost_terms is not None else ()
+        if held:        # (the slot budget counts the held conditions' dims: clear them, the new ones follow)
+            _lib.check(self._lib.bcmpc_set_termination(self._h, None, ctypes.c_int32(0), ctypes.c_double(0.0)))
+        self.cost_terms = None
+        self._cost_inputs = None
+        _lib.check(self._lib.bcmpc_set_cost_terms_x(self._h, arr, ctypes.c_int32(len(tc.terms)),
+                                                    ctypes.c_int32(tc.n_ref)))
+        if tc.done_conditions:
+            _lib.check(self._lib.bcmpc_set_termination(self._h, *pack(tc.done_conditions),
+                                                       ctypes.c_double(tc.done_cost)))
+        self.cost_terms = tc
+
+    def set_cost_inputs(self, reference=None, previous_action=None) -> None:
+        """The inputs of the calls that follow on an engine whose cost has ``ref(c)`` values or ``rate`` terms
+        (bcmpc_set_cost_inputs): ``reference`` ``[R]``, ``[H, R]``, ``[B, 1, R]`` or ``[B, H, R]`` f64 with
+        ``R >= cost.n_ref`` (one environment, or ``B`` environments for the batched calls),
+        ``previous_action`` ``[A]`` or ``[B, A]`` or None (``a_{-1} := a_0``).  One small stream-ordered upload
+        each into buffers the engine owns; they stay valid until replaced."""
+        tc = self.cost_terms
+        if tc is None or not tc.extended:
+            raise ValueError("set_cost_inputs needs a cost with reference channels or rate terms (set_cost_terms)")
+        ref = None
+        ref_envs = ref_steps = 0
+        if tc.n_ref:
+            if reference is None:
+                raise ValueError(f"the cost names reference channels (n_ref = {tc.n_ref}): a reference is needed")
+            ref = np.asarray(reference, dtype=np.float64)
+            if ref.ndim < 1 or ref.ndim > 3:
+                raise ValueError(f"reference must be [R], [H, R] or [B, H, R], not {ref.shape}")
+            ref = ref.reshape((1,) * (3 - ref.ndim) + ref.shape)
+            if ref.shape[2] < tc.n_ref:
+                raise ValueError(f"the reference has {ref.shape[2]} channels, the cost names {tc.n_ref}")
+            if ref.shape[1] not in (1, self.horizon):
+                raise ValueError(f"the reference has {ref.shape[1]} steps: 1 or the horizon ({self.horizon})")
+            ref = np.ascontiguousarray(ref[:, :, :tc.n_ref])
+            ref_envs, ref_steps = ref.shape[0], ref.shape[1]
+        elif reference is not None:
+            raise ValueError("the cost names no reference channel: reference must be None")
+        prev, prev_envs = None, 0
+        if previous_action is not None:
+            if not tc.uses_rate:
+                raise ValueError("the cost has no rate term: previous_action must be None")
+            prev = np.asarray(previous_action, dtype=np.float64)
+            if prev.ndim not in (1, 2) or prev.shape[-1] != self.action_dim:
+                raise ValueError(f"previous_action must be [A] or [B, A] with A = {self.action_dim}, not {prev.shape}")
+            prev = np.ascontiguousarray(prev.reshape(-1, self.action_dim))
+            prev_envs = prev.shape[0]
+        _lib.check(self._lib.bcmpc_set_cost_inputs(
+            self._h, _dp(ref) if ref is not None else None, ctypes.c_int32(ref_envs), ctypes.c_int32(ref_steps),
+            _dp(prev) if prev is not None else None, ctypes.c_int32(prev_envs)))
+        self._cost_inputs = (ref, prev)
+
+    def cost_input_buffers(self):
+        """(device address of the reference buffer, of the previous-action buffer), 0 before they exist."""
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(self._lib.bcmpc_cost_input_buffers(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value or 0), int(b.value or 0)
+
+    def trajectory_cost_inputs_async(self, d_traj: int, K: int, d_costs: int, env_paths: int,
+                                     d_ref: Optional[int] = None, ref_envs: int = 1, ref_steps: int = 1,
+                                     d_prev: Optional[int] = None, prev_envs: int = 1,
+                                     d_actions: Optional[int] = None, seed: int = 0, cand_offset: int = 0,
+                                     d_mu: Optional[int] = None, d_sigma: Optional[int] = None, cem_iter: int = 0,
+                                     stream: Optional[int] = None, d_term_step: Optional[int] = None) -> None:
+        """``trajectory_cost_async`` for a cost with reference channels or rate terms, on device inputs
+        (bcmpc_trajectory_cost_inputs_async): candidate k reads environment ``k // env_paths`` of ``d_ref``
+        ``[ref_envs, ref_steps, n_ref]`` and ``d_prev`` ``[prev_envs, A]`` (None: no previous action);
+        ``ref_envs`` / ``prev_envs`` are 1 or ``K // env_paths``, ``ref_steps`` 1 or the horizon."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_trajectory_cost_inputs_async(
+            self._h, vp(d_traj), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset),
+            vp(d_mu), vp(d_sigma), ctypes.c_int32(cem_iter), ctypes.c_int64(K), vp(d_costs), vp(d_term_step),
+            ctypes.c_int64(env_paths), vp(d_ref), ctypes.c_int32(ref_envs), ctypes.c_int32(ref_steps), vp(d_prev),
+            ctypes.c_int32(prev_envs), ctypes.c_void_p(stream)))
 
     def trajectory_cost_async(self, d_traj: int, K: int, d_costs: int, d_actions: Optional[int] = None,
                               seed: int = 0, cand_offset: int = 0, d_mu: Optional[int] = None,

@@ -29,7 +29,8 @@ import numpy as np
 from . import _lib
 from . import distributed as _dist
 from . import weights as _weights
-from .controllers import _batch_rng_check, _batch_states, _cached_engine, _device, _device_terms, _shape
+from .controllers import (_batch_inputs_check, _batch_rng_check, _batch_states, _cached_engine, _device, _device_terms,
+                          _send_cost_inputs, _shape)
 from .cost_functions import is_cheetah_cost
 from .engine import BatchResult, MLPSpec, RolloutEngine, StepResult, _dp, _engine_config, _EngineCalls, _f64
 
@@ -143,6 +144,11 @@ class EnsembleEngine(_EngineCalls):
     def set_cost_terms(self, term_cost) -> None:
         for m in self.members:
             m.set_cost_terms(term_cost)
+
+    def set_cost_inputs(self, reference=None, previous_action=None) -> None:
+        """Every member gets the same inputs (RolloutEngine.set_cost_inputs)."""
+        for m in self.members:
+            m.set_cost_inputs(reference, previous_action)
 
     def set_action_bounds(self, low, high) -> None:
         for m in self.members:
@@ -385,6 +391,7 @@ def _ctrl_engine(ctrl, S: int, A: int, k_total: int, slot: str) -> EnsembleEngin
                          cost="cheetah" if terms is None else "terms")
     if terms is not None:
         eng.set_cost_terms(terms)
+        _send_cost_inputs(ctrl, eng, terms)
     for i, (s, norm, version) in enumerate(specs):
         eng.set_weights(i, s, norm, version)
     eng.set_rule(model.rule, model.kappa)
@@ -445,6 +452,7 @@ def mpc_get_actions(ctrl, states):
     if K == 0:
         raise ValueError("attempt to get argmin of an empty sequence")
     B = states.shape[0]
+    _batch_inputs_check(ctrl, getattr(ctrl, "_inputs", (None, None)), B)
     eng = _ctrl_engine(ctrl, S, A, B * K, "batch")
     diag = bool(ctrl.dyn_model.diagnostics)
     res = eng.get_actions(states, None, seed=seed, return_costs=ctrl.keep_costs, return_member_costs=diag)

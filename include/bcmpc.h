@@ -374,6 +374,65 @@ int bcmpc_terminal_value_masked_async(bcmpc_engine* eng, const double* d_states,
  * termination set. */
 int bcmpc_last_termination_steps(bcmpc_engine* eng, const int64_t* idx, int32_t n, int32_t* out);
 
+/* ---- Reference tracking: per-call targets and action-rate terms (definition: cost_functions.py episode_cost
+ * with reference / previous_action) ---------------------------------------------------------------------------
+ * A call carries a reference r[env][h][c] of n_ref channels and, optionally, a previous action per environment.
+ * A THRESHOLD or QUADRATIC term whose `ref` is a channel c reads p = r[env][h][c] at step h in place of `param`,
+ * whatever its source; the arithmetic is the term's otherwise, and a non-finite reference value propagates as
+ * IEEE says.  A RATE term is  d = a_h[index] - a_{h-1}[index]; acc = acc + weight * (d * d)  with a_{-1} the
+ * call's previous action, or a_0 itself when the call has none.  Candidate k of a launch over n_envs
+ * environments belongs to environment k / (num_paths / n_envs).  What a list reads per row -- its state dims,
+ * actions and channels, each counted once, the done conditions' dims included -- is at most
+ * BCMPC_MAX_COST_TERMS slots.  Additive to ABI 5: callers detect the feature by the symbol
+ * bcmpc_set_cost_terms_x. */
+#define BCMPC_TERM_RATE 4            /* a bcmpc_term_kind of bcmpc_cost_term_x alone: source ACTION, ref -1 */
+#define BCMPC_MAX_REF_CHANNELS 16
+typedef struct bcmpc_cost_term_x {   /* 48 bytes: bcmpc_cost_term's fields, then ref */
+    int32_t kind, source, index, cmp;
+    double weight, param;
+    int32_t ref;                     /* -1: param is the constant; else the channel, < n_ref */
+    int32_t reserved[3];             /* must be zero */
+} bcmpc_cost_term_x;
+
+/* bcmpc_set_cost_terms with the extended record: every check of bcmpc_set_cost_terms, plus BCMPC_ERR_ARG for
+ * n_ref outside [0, 16], a ref outside [-1, n_ref), a ref on a kind other than THRESHOLD / QUADRATIC, a RATE
+ * whose source is not ACTION, reserved != 0, more than 32 slots, more than 32 entries together with the done
+ * conditions the engine holds.  A list that names no channel and has no RATE term is bcmpc_set_cost_terms'.
+ * bcmpc_set_cost_terms replaces an extended list with a plain one (and still refuses kind 4).  All argument
+ * checks come before any HIP call. */
+int bcmpc_set_cost_terms_x(bcmpc_engine* eng, const bcmpc_cost_term_x* terms, int32_t n, int32_t n_ref);
+
+/* The inputs of the calls that follow, copied from HOST memory into the engine's buffers on the engine's stream
+ * (behind what that stream was given before); the call returns when the copies have landed, so an entry on any
+ * stream, or a graph replay, that is issued afterwards reads the new data.  The caller must not replace the inputs
+ * while a launch it issued on ANOTHER stream may still read them.  Valid until replaced:
+ *   ref         : [ref_envs][ref_steps][n_ref] doubles, ref_steps 1 (constant over the horizon) or H; NULL with
+ *                 an engine whose list names no channel
+ *   prev_action : [prev_envs][A] doubles, or NULL: no previous action (a_{-1} := a_0)
+ * ref_envs / prev_envs are 1 (shared by every environment of a call) or the n_envs of the calls that follow; a
+ * call over another n_envs returns BCMPC_ERR_ARG.  The buffers are allocated here, never inside a stream-ordered
+ * entry, and only grow: calls with the same (or smaller) sizes keep their addresses, so a captured graph replays
+ * on the new data.  BCMPC_ERR_ARG (before any HIP call): a null engine, not an
+ * extended list, ref NULL where the list names a channel, ref_steps outside {1, H}, ref_envs / prev_envs outside
+ * [1, num_paths].  A rollout entry on an engine whose list names a channel returns BCMPC_ERR_STATE before this
+ * call, with nothing launched. */
+int bcmpc_set_cost_inputs(bcmpc_engine* eng, const double* ref, int32_t ref_envs, int32_t ref_steps,
+                          const double* prev_action, int32_t prev_envs);
+
+/* bcmpc_trajectory_cost_steps_async for an extended list, on DEVICE inputs: candidate k reads environment
+ * k / env_paths (K a multiple of env_paths); d_ref [ref_envs][ref_steps][n_ref] (NULL only where no channel is
+ * named), d_prev [prev_envs][A] or NULL; ref_envs / prev_envs 1 or K / env_paths, ref_steps 1 or H.  Allocates
+ * nothing.  BCMPC_ERR_ARG on any of that violated; BCMPC_ERR_STATE: no extended list set. */
+int bcmpc_trajectory_cost_inputs_async(bcmpc_engine* eng, const double* d_traj, const double* d_actions,
+                                       uint64_t seed, int64_t cand_offset, const double* d_mu,
+                                       const double* d_sigma, int32_t cem_iter, int64_t K, double* d_costs,
+                                       int32_t* d_term_step, int64_t env_paths, const double* d_ref,
+                                       int32_t ref_envs, int32_t ref_steps, const double* d_prev,
+                                       int32_t prev_envs, void* stream);
+
+/* Diagnostics: the device addresses of the engine's input buffers (NULL before they exist). */
+int bcmpc_cost_input_buffers(bcmpc_engine* eng, void** d_ref, void** d_prev);
+
 /* env.action_space.low / .high (controllers.py:53). Defaults: [-1, 1]^A. */
 int bcmpc_set_action_bounds(bcmpc_engine* eng, const double* low, const double* high);
 
