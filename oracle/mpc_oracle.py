@@ -204,9 +204,17 @@ class NumpyDynamicsChunked(NumpyDynamics):
 
     def _mm(self, a, W):
         if self.chunks <= 0:                       # one product at a time in k order (a sequential f32 chain)
+            a, W = np.asarray(a, np.float32), np.asarray(W, np.float32)
             acc = np.zeros((a.shape[0], W.shape[1]), np.float32)
-            for k in range(a.shape[1]):
-                acc = (acc + (a[:, k:k + 1] * W[k]).astype(np.float32)).astype(np.float32)
+            # (every output element is its own chain: in place and 128 columns at a time, which stay in cache --
+            #  the same f32 products and f32 adds in the same order)
+            for c0 in range(0, W.shape[1], 128):
+                blk = np.zeros((a.shape[0], min(128, W.shape[1] - c0)), np.float32)
+                prod = np.empty_like(blk)
+                for k in range(a.shape[1]):
+                    np.multiply(a[:, k:k + 1], W[k, c0:c0 + 128], out=prod)
+                    blk += prod
+                acc[:, c0:c0 + 128] = blk
             return acc
         q = np.linspace(0, a.shape[1], self.chunks + 1).astype(int)
         acc = np.zeros((a.shape[0], W.shape[1]), np.float32)
