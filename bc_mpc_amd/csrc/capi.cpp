@@ -1,6 +1,6 @@
 // capi.cpp -- C ABI of libbcmpc (include/bcmpc.h): engine lifetime, the setters' uploads, the rollout launch, team
 // ordering and fallback, the plain control steps, introspection (engine_plan.cpp: the checks and the kernel choice;
-// pack.cpp: weight packing; mt_draw.cpp, planners.cpp: the rest)
+// pack.cpp: weight packing; cost_terms.cpp: the cost-term lists; mt_draw.cpp, planners.cpp: the rest)
 #include "host_internal.h"
 
 using namespace bcmpc::host;
@@ -296,175 +296,31 @@ int bcmpc_first_actions(bcmpc_engine* e, double* out) {
     return BCMPC_OK;
 }
 
-// one cost term's checks (bcmpc_set_cost_terms; a done condition passes them too, then its own)
-static int check_cost_term(const bcmpc_config& c, const bcmpc_cost_term& T, const std::string& at) {
-    if (T.kind < BCMPC_TERM_THRESHOLD || T.kind > BCMPC_TERM_QUADRATIC) return fail(BCMPC_ERR_ARG, at + "unknown kind");
-    if (T.source < BCMPC_SRC_STATE || T.source > BCMPC_SRC_ACTION) return fail(BCMPC_ERR_ARG, at + "unknown source");
-    if (T.kind == BCMPC_TERM_THRESHOLD && (T.cmp < BCMPC_CMP_GE || T.cmp > BCMPC_CMP_LT))
-        return fail(BCMPC_ERR_ARG, at + "unknown cmp");
-    if (T.kind == BCMPC_TERM_DIFF && T.source != BCMPC_SRC_STATE)
-        return fail(BCMPC_ERR_ARG, at + "a DIFF term's source must be STATE");
-    const int lim = T.source == BCMPC_SRC_ACTION ? c.action_dim : c.state_dim;
-    if (T.index < 0 || T.index >= lim)
-        return fail(BCMPC_ERR_ARG, at + "index " + std::to_string(T.index) + " outside [0, " + std::to_string(lim) + ")");
-    if (!std::isfinite(T.weight) || !std::isfinite(T.param))
-        return fail(BCMPC_ERR_ARG, at + "weight and param must be finite");
-    if (T.kind == BCMPC_TERM_DIFF && T.param == 0.0) return fail(BCMPC_ERR_ARG, at + "a DIFF term's param must not be 0");
-    return BCMPC_OK;
-}
-
-// the slots a list reads per row: its state dims (the conditions' included), its channels and its actions, each
-// counted once (refs: every term's channel or -1; empty for a plain list)
-static int count_slots(const std::vector<bcmpc_cost_term>& terms, const std::vector<bcmpc_cost_term>& conds,
-                       const std::vector<int32_t>& refs) {
-    uint32_t seen[3] = {0, 0, 0};                        // state dims, actions, channels
-    for (const auto* v : {&terms, &conds})
-        for (const bcmpc_cost_term& T : *v) seen[T.source == BCMPC_SRC_ACTION ? 1 : 0] |= 1u << T.index;
-    for (const int32_t r : refs)
-        if (r >= 0) seen[2] |= 1u << r;
-    return __builtin_popcount(seen[0]) + __builtin_popcount(seen[1]) + __builtin_popcount(seen[2]);
-}
-
-// the launch template of checked cost terms and done conditions (the conditions follow the terms in
-// TermCostArgs::terms).  The slots: every (state dim) the terms and the conditions read, then every (action) --
-// term_cost.hip wants the actions last.  An extended list (refs not empty or a RATE term; x receives what
-// term_cost_x.hip reads beside the template) has its channels between the two
-static TermCostArgs digest_terms(const bcmpc_config& c, const std::vector<bcmpc_cost_term>& terms,
-                                 const std::vector<bcmpc_cost_term>& conds, double done_cost,
-                                 const std::vector<int32_t>& refs = {}, TermCostXArgs* x = nullptr) {
-    TermCostArgs a{};
-    const int n = (int)terms.size(), nall = n + (int)conds.size();
-    int slot_of[2][BCMPC_MAX_STATE], chan_slot[BCMPC_MAX_REF_CHANNELS];
-    for (auto& row : slot_of)
-        for (int& v : row) v = -1;
-    for (int& v : chan_slot) v = -1;
-    int n_ref_slots = 0, n_ref = 0;
-    bool has_rate = false;
-    for (int pass = 0; pass < 3; ++pass)
-        for (int t = 0; t < nall; ++t) {
-            const bcmpc_cost_term& T = t < n ? terms[t] : conds[t - n];
-            if (pass == 1) {                             // the channels: slots between the state dims and the actions
-                const int r = t < (int)refs.size() ? refs[t] : -1;
-                if (r < 0) continue;
-                if (chan_slot[r] < 0) {
-                    chan_slot[r] = a.n_slots++;
-                    a.slot_index[chan_slot[r]] = (uint8_t)r;
-                    a.slot_action[chan_slot[r]] = 2;
-                    ++n_ref_slots;
-                }
-                n_ref = std::max(n_ref, r + 1);
-                continue;
-            }
-            const int is_act = T.source == BCMPC_SRC_ACTION ? 1 : 0;
-            if (is_act != pass / 2) continue;
-            int& sl = slot_of[is_act][T.index];
-            if (sl < 0) {
-                sl = a.n_slots++;
-                a.slot_index[sl] = (uint8_t)T.index;
-                a.slot_action[sl] = (uint8_t)is_act;
-                if (!is_act) a.n_state_slots = a.n_slots;
-            }
-            TermDev& d = a.terms[t];
-            d.weight = T.weight; d.param = T.param;
-            const bool rate = T.kind == BCMPC_TERM_RATE;
-            has_rate = has_rate || rate;
-            d.meta = (rate ? (uint32_t)BCMPC_TERM_QUADRATIC | 1u << 7 : (uint32_t)T.kind) |
-                     (T.kind == BCMPC_TERM_THRESHOLD ? (uint32_t)T.cmp << 2 : 0u) |
-                     (T.source == BCMPC_SRC_NEXT_STATE ? 1u << 4 : 0u) | (uint32_t)sl << 8;
-            if (T.kind == BCMPC_TERM_DIFF) {
-                // div_rn's precondition (device_common.h): r = RN(1 / b), and neither near the subnormals
-                const double r = 1.0 / T.param, mb = std::fabs(T.param), mr = std::fabs(r);
-                d.rparam = r;
-                if (mb > 0x1p-500 && mb < 0x1p500 && mr > 0x1p-500 && mr < 0x1p500) d.meta |= 1u << 5;
-            }
-        }
-    for (int t = 0; t < n && t < (int)refs.size(); ++t)          // p of a term with a channel: that channel's slot
-        if (refs[t] >= 0) {
-            a.terms[t].meta |= 1u << 6;
-            a.terms[t].pad = (uint32_t)chan_slot[refs[t]];
-        }
-    a.n_terms = n;
-    a.n_done = (int32_t)conds.size();
-    a.done_cost = done_cost;
-    a.H = c.horizon; a.S = c.state_dim; a.A = c.action_dim;
-    if (x) {
-        *x = TermCostXArgs{};
-        x->n_ref_slots = n_ref_slots; x->n_ref = n_ref; x->has_rate = has_rate ? 1 : 0;
-    }
-    return a;
-}
-
+// (the three list setters: every check, the stored lists and the launch template are cost_terms.cpp's)
 int bcmpc_set_cost_terms(bcmpc_engine* e, const bcmpc_cost_term* terms, int32_t n) {
     if (!e) return fail(BCMPC_ERR_ARG, "null argument");
-    const bcmpc_config& c = e->cfg;
-    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "cost terms need an engine created with BCMPC_COST_TERMS");
-    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of cost terms must be in [0, 32]");
-    if (n > 0 && !terms) return fail(BCMPC_ERR_ARG, "null argument");
-    for (int t = 0; t < n; ++t)
-        if (const int rc = check_cost_term(c, terms[t], "cost term " + std::to_string(t) + ": ")) return rc;
-    // (every entry adds at most one slot, so the slots fit whenever the entries do)
-    if (n + (int)e->tc_conds.size() > BCMPC_MAX_COST_TERMS)
-        return fail(BCMPC_ERR_ARG, "cost terms plus done conditions must be at most 32 (" + std::to_string(n) + " + " +
-                                       std::to_string(e->tc_conds.size()) + ")");
-    e->tc_terms.assign(terms, terms + n);
-    e->tc_refs.clear();                                  // (an extended list is replaced by a plain one)
-    e->tc_x = false;
-    e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost);
-    e->has_terms = true;
+    if (const int rc = set_terms(e->cfg, &e->cost, terms, n)) return rc;
     if (e->fb) return bcmpc_set_cost_terms(e->fb, terms, n);
     return BCMPC_OK;
 }
 
 int bcmpc_set_cost_terms_x(bcmpc_engine* e, const bcmpc_cost_term_x* terms, int32_t n, int32_t n_ref) {
     if (!e) return fail(BCMPC_ERR_ARG, "null argument");
-    const bcmpc_config& c = e->cfg;
-    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "cost terms need an engine created with BCMPC_COST_TERMS");
-    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of cost terms must be in [0, 32]");
-    if (n > 0 && !terms) return fail(BCMPC_ERR_ARG, "null argument");
-    if (n_ref < 0 || n_ref > BCMPC_MAX_REF_CHANNELS) return fail(BCMPC_ERR_ARG, "n_ref must be in [0, 16]");
-    std::vector<bcmpc_cost_term> plain((size_t)n);
-    std::vector<int32_t> refs((size_t)n);
-    bool ext = false;
-    for (int t = 0; t < n; ++t) {
-        const bcmpc_cost_term_x& X = terms[t];
-        const std::string at = "cost term " + std::to_string(t) + ": ";
-        bcmpc_cost_term T{X.kind, X.source, X.index, X.cmp, X.weight, X.param};
-        if (X.reserved[0] != 0 || X.reserved[1] != 0 || X.reserved[2] != 0) return fail(BCMPC_ERR_ARG, at + "reserved must be 0");
-        if (X.kind == BCMPC_TERM_RATE) {
-            if (X.source != BCMPC_SRC_ACTION) return fail(BCMPC_ERR_ARG, at + "a RATE term's source must be ACTION");
-            T.kind = BCMPC_TERM_QUADRATIC;               // (the remaining checks are a QUADRATIC's on the action)
-            T.param = 0.0;
-        }
-        if (const int rc = check_cost_term(c, T, at)) return rc;
-        if (X.ref < -1 || X.ref >= n_ref)
-            return fail(BCMPC_ERR_ARG, at + "ref " + std::to_string(X.ref) + " outside [-1, n_ref = " + std::to_string(n_ref) + ")");
-        if (X.ref >= 0 && X.kind != BCMPC_TERM_THRESHOLD && X.kind != BCMPC_TERM_QUADRATIC)
-            return fail(BCMPC_ERR_ARG, at + "a reference channel stands only for a THRESHOLD's or a QUADRATIC's param");
-        T.kind = X.kind;
-        plain[(size_t)t] = T;
-        refs[(size_t)t] = X.ref;
-        ext = ext || X.ref >= 0 || X.kind == BCMPC_TERM_RATE;
-    }
-    if (n + (int)e->tc_conds.size() > BCMPC_MAX_COST_TERMS)
-        return fail(BCMPC_ERR_ARG, "cost terms plus done conditions must be at most 32 (" + std::to_string(n) + " + " +
-                                       std::to_string(e->tc_conds.size()) + ")");
-    const int slots = count_slots(plain, e->tc_conds, refs);
-    if (slots > BCMPC_MAX_COST_TERMS)
-        return fail(BCMPC_ERR_ARG, "the list reads " + std::to_string(slots) + " slots per row (state dims, actions "
-                                   "and reference channels, the done conditions' included): at most 32 fit");
-    if (!ext) {                                          // nothing extended in it: the plain setter's list
-        std::vector<bcmpc_cost_term> p2 = plain;
-        return bcmpc_set_cost_terms(e, p2.data(), n);
-    }
-    int old_n_ref = e->tc_x ? e->tcx.n_ref : 0;
-    e->tc_terms = plain;
-    e->tc_refs = refs;
-    e->tc_x = true;
-    e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost, e->tc_refs, &e->tcx);
-    e->tcx.n_ref = n_ref;                                // (the rows of the call's reference have n_ref channels)
-    if (old_n_ref != n_ref) e->has_inputs = false;       // inputs of another channel count do not carry over
-    e->has_terms = true;
+    if (const int rc = set_terms_x(e->cfg, &e->cost, terms, n, n_ref)) return rc;
     if (e->fb) return bcmpc_set_cost_terms_x(e->fb, terms, n, n_ref);
+    return BCMPC_OK;
+}
+
+int bcmpc_set_termination(bcmpc_engine* e, const bcmpc_cost_term* conds, int32_t n, double done_cost) {
+    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
+    const bcmpc_config& c = e->cfg;
+    if (const int rc = check_termination(c, e->cost, conds, n, done_cost)) return rc;
+    if (n > 0 && !e->d_tc_steps) {
+        HIP_TRY(hipSetDevice(c.device));
+        HIP_TRY(hipMalloc(&e->d_tc_steps, (size_t)std::max<int64_t>(1, c.num_paths) * sizeof(int32_t)));
+    }
+    store_termination(c, &e->cost, conds, n, done_cost);
+    if (e->fb) return bcmpc_set_termination(e->fb, conds, n, done_cost);
     return BCMPC_OK;
 }
 
@@ -472,10 +328,10 @@ int bcmpc_set_cost_inputs(bcmpc_engine* e, const double* ref, int32_t ref_envs, 
                           const double* prev_action, int32_t prev_envs) {
     if (!e) return fail(BCMPC_ERR_ARG, "null argument");
     const bcmpc_config& c = e->cfg;
-    if (c.cost != BCMPC_COST_TERMS || !e->has_terms || !e->tc_x)
+    if (c.cost != BCMPC_COST_TERMS || !e->cost.has_terms || !e->cost.ext)
         return fail(BCMPC_ERR_ARG, "cost inputs need a list set with bcmpc_set_cost_terms_x that names a reference "
                                    "channel or has a RATE term");
-    const int n_ref = e->tcx.n_ref;
+    const int n_ref = e->cost.n_ref;
     const int64_t env_cap = std::max<int64_t>(1, c.num_paths);
     if (n_ref > 0) {
         if (!ref) return fail(BCMPC_ERR_ARG, "the list names reference channels: ref must not be null");
@@ -486,7 +342,7 @@ int bcmpc_set_cost_inputs(bcmpc_engine* e, const double* ref, int32_t ref_envs, 
     } else if (ref) {
         return fail(BCMPC_ERR_ARG, "the list names no reference channel: ref must be null");
     }
-    if (prev_action && !e->tcx.has_rate) return fail(BCMPC_ERR_ARG, "the list has no RATE term: prev_action must be null");
+    if (prev_action && !e->cost.tpl.has_rate) return fail(BCMPC_ERR_ARG, "the list has no RATE term: prev_action must be null");
     if (prev_action && (prev_envs < 1 || prev_envs > env_cap))
         return fail(BCMPC_ERR_ARG, "prev_envs must be in [1, num_paths]");
     const size_t nr = n_ref > 0 ? (size_t)ref_envs * (size_t)ref_steps * (size_t)n_ref : 0;
@@ -506,7 +362,7 @@ int bcmpc_set_cost_inputs(bcmpc_engine* e, const double* ref, int32_t ref_envs, 
         HIP_TRY(hipMalloc(&e->d_tc_prev, np * sizeof(double)));
         e->tc_prev_cap = np;
     }
-    e->has_inputs = false;
+    e->cost.has_inputs = false;
     if (nr) {
         e->h_in_ref.assign(ref, ref + nr);
         HIP_TRY(hipMemcpyAsync(e->d_tc_ref, e->h_in_ref.data(), nr * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -522,10 +378,10 @@ int bcmpc_set_cost_inputs(bcmpc_engine* e, const double* ref, int32_t ref_envs, 
     // the uploads have landed when the call returns: an entry on any other stream (bcmpc_rollout_async on the
     // caller's, a graph replay) needs no ordering of its own against them
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->in_ref_envs = nr ? ref_envs : 0;
-    e->in_ref_steps = nr ? ref_steps : 0;
-    e->in_prev_envs = np ? prev_envs : 0;
-    e->has_inputs = true;
+    e->cost.in_ref_envs = nr ? ref_envs : 0;
+    e->cost.in_ref_steps = nr ? ref_steps : 0;
+    e->cost.in_prev_envs = np ? prev_envs : 0;
+    e->cost.has_inputs = true;
     if (e->fb) return bcmpc_set_cost_inputs(e->fb, ref, ref_envs, ref_steps, prev_action, prev_envs);
     return BCMPC_OK;
 }
@@ -537,50 +393,9 @@ int bcmpc_cost_input_buffers(bcmpc_engine* e, void** d_ref, void** d_prev) {
     return BCMPC_OK;
 }
 
-int bcmpc_set_termination(bcmpc_engine* e, const bcmpc_cost_term* conds, int32_t n, double done_cost) {
-    if (!e) return fail(BCMPC_ERR_ARG, "null argument");
-    const bcmpc_config& c = e->cfg;
-    if (c.cost != BCMPC_COST_TERMS) return fail(BCMPC_ERR_ARG, "termination needs an engine created with BCMPC_COST_TERMS");
-    if (n < 0 || n > BCMPC_MAX_COST_TERMS) return fail(BCMPC_ERR_ARG, "the number of done conditions must be in [0, 32]");
-    if (n > 0 && !conds) return fail(BCMPC_ERR_ARG, "null argument");
-    if (!std::isfinite(done_cost)) return fail(BCMPC_ERR_ARG, "done_cost must be finite");
-    for (int t = 0; t < n; ++t) {
-        const bcmpc_cost_term& T = conds[t];
-        const std::string at = "done condition " + std::to_string(t) + ": ";
-        if (T.kind != BCMPC_TERM_THRESHOLD) return fail(BCMPC_ERR_ARG, at + "the kind must be THRESHOLD");
-        if (T.source != BCMPC_SRC_NEXT_STATE) return fail(BCMPC_ERR_ARG, at + "the source must be NEXT_STATE");
-        if (const int rc = check_cost_term(c, T, at)) return rc;
-        if (T.weight != 0.0) return fail(BCMPC_ERR_ARG, at + "the weight must be 0");
-    }
-    if (n + (int)e->tc_terms.size() > BCMPC_MAX_COST_TERMS)
-        return fail(BCMPC_ERR_ARG, "cost terms plus done conditions must be at most 32 (" +
-                                       std::to_string(e->tc_terms.size()) + " + " + std::to_string(n) + ")");
-    if (e->tc_x) {                                       // (a plain list's slots fit whenever its entries do)
-        const int slots = count_slots(e->tc_terms, std::vector<bcmpc_cost_term>(conds, conds + n), e->tc_refs);
-        if (slots > BCMPC_MAX_COST_TERMS)
-            return fail(BCMPC_ERR_ARG, "the cost terms and these done conditions read " + std::to_string(slots) +
-                                           " slots per row: at most 32 fit");
-    }
-    if (n > 0 && !e->d_tc_steps) {
-        HIP_TRY(hipSetDevice(c.device));
-        HIP_TRY(hipMalloc(&e->d_tc_steps, (size_t)std::max<int64_t>(1, c.num_paths) * sizeof(int32_t)));
-    }
-    e->tc_conds.assign(conds, conds + n);
-    e->done_cost = n > 0 ? done_cost : 0.0;
-    if (e->tc_x) {
-        const int n_ref = e->tcx.n_ref;
-        e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost, e->tc_refs, &e->tcx);
-        e->tcx.n_ref = n_ref;
-    } else {
-        e->tc = digest_terms(c, e->tc_terms, e->tc_conds, e->done_cost);
-    }
-    if (e->fb) return bcmpc_set_termination(e->fb, conds, n, done_cost);
-    return BCMPC_OK;
-}
-
 int bcmpc_last_termination_steps(bcmpc_engine* e, const int64_t* idx, int32_t n, int32_t* out) {
     if (!e || !idx || !out || n < 1) return fail(BCMPC_ERR_ARG, "null argument");
-    if (e->tc_conds.empty() || !e->d_tc_steps) return fail(BCMPC_ERR_STATE, "bcmpc_set_termination has not been called");
+    if (e->cost.conds.empty() || !e->d_tc_steps) return fail(BCMPC_ERR_STATE, "bcmpc_set_termination has not been called");
     for (int i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= e->cfg.num_paths) return fail(BCMPC_ERR_ARG, "candidate index outside [0, num_paths)");
     const bcmpc_engine* src = e->steps_on_fb && e->fb && e->fb->d_tc_steps ? e->fb : e;
@@ -591,20 +406,14 @@ int bcmpc_last_termination_steps(bcmpc_engine* e, const int64_t* idx, int32_t n,
     return BCMPC_OK;
 }
 
-// the inputs of one launch of an extended list (device pointers)
-struct CostInputs {
-    int64_t env_paths;
-    const double* ref;  int32_t ref_envs, ref_steps;
-    const double* prev; int32_t prev_envs;               // prev == nullptr: no previous action
-};
-
 // one term-cost launch on st: the engine's template plus this launch's trajectory, action source and K; in: the
 // inputs of an extended list (else nullptr)
 static int term_cost_launch(bcmpc_engine* e, const double* d_traj, const double* d_actions, uint64_t seed,
                             int64_t cand_offset, const double* d_mu, const double* d_sigma, int32_t cem_iter,
                             int64_t K, double* d_costs, int32_t* d_term_step, hipStream_t st,
                             const CostInputs* in = nullptr) {
-    TermCostArgs a = e->tc;
+    TermCostXArgs x = e->cost.tpl;
+    TermCostArgs& a = x.b;
     a.traj = d_traj; a.actions = d_actions; a.costs = d_costs;
     a.term_step = d_term_step;                           // (read by the DONE instances only)
     a.cem_mu = d_mu; a.cem_sigma = d_sigma; a.cem_iter = cem_iter;
@@ -613,42 +422,18 @@ static int term_cost_launch(bcmpc_engine* e, const double* d_traj, const double*
         a.low[j] = e->h_consts[6 * kConstCols + j];
         a.high[j] = e->h_consts[7 * kConstCols + j];
     }
-    if (!e->tc_x) {
+    if (!e->cost.ext) {
         HIP_TRY(launch_term_cost(a, st));
         return BCMPC_OK;
     }
-    TermCostXArgs x = e->tcx;
-    x.b = a;
-    x.env_paths = in->env_paths;
-    x.ref = x.n_ref_slots > 0 ? in->ref : nullptr;
-    x.ref_row_stride = in->ref_steps > 1 ? x.n_ref : 0;
-    x.ref_env_stride = in->ref_envs > 1 ? (int64_t)in->ref_steps * x.n_ref : 0;
-    x.prev = x.has_rate ? in->prev : nullptr;
-    x.prev_env_stride = in->prev_envs > 1 ? e->cfg.action_dim : 0;
+    bind_inputs(*in, e->cfg.action_dim, &x);
     HIP_TRY(launch_term_cost_x(x, st));
     return BCMPC_OK;
 }
 
 // the inputs of an extended list for a launch over n_envs environments, from what bcmpc_set_cost_inputs left
-// (checked before anything is launched)
-static int engine_cost_inputs(const bcmpc_engine* e, int32_t n_envs, CostInputs* in) {
-    if (e->tcx.n_ref_slots > 0 && !e->has_inputs)
-        return fail(BCMPC_ERR_STATE, "the cost terms name reference channels: bcmpc_set_cost_inputs has not been called");
-    if (n_envs < 1 || e->cfg.num_paths % n_envs != 0) return fail(BCMPC_ERR_ARG, "num_paths is not a multiple of n_envs");
-    *in = CostInputs{};
-    in->env_paths = std::max<int64_t>(1, e->cfg.num_paths / n_envs);
-    if (!e->has_inputs) return BCMPC_OK;
-    if (e->in_ref_envs > 1 && e->in_ref_envs != n_envs)
-        return fail(BCMPC_ERR_ARG, "the reference was set for " + std::to_string(e->in_ref_envs) +
-                                       " environments, this call has " + std::to_string(n_envs));
-    if (e->in_prev_envs > 1 && e->in_prev_envs != n_envs)
-        return fail(BCMPC_ERR_ARG, "the previous actions were set for " + std::to_string(e->in_prev_envs) +
-                                       " environments, this call has " + std::to_string(n_envs));
-    in->ref = e->in_ref_envs ? e->d_tc_ref : nullptr;
-    in->ref_envs = e->in_ref_envs; in->ref_steps = e->in_ref_steps;
-    in->prev = e->in_prev_envs ? e->d_tc_prev : nullptr;
-    in->prev_envs = e->in_prev_envs;
-    return BCMPC_OK;
+static int engine_cost_inputs(const bcmpc_engine* e, int64_t K, int32_t n_envs, CostInputs* in) {
+    return stored_inputs(e->cost, K, n_envs, e->d_tc_ref, e->d_tc_prev, in);
 }
 
 static int trajectory_cost_check(bcmpc_engine* e, const double* d_traj, const double* d_mu, const double* d_sigma,
@@ -658,7 +443,7 @@ static int trajectory_cost_check(bcmpc_engine* e, const double* d_traj, const do
     if (K < 1) return fail(BCMPC_ERR_ARG, "K must be >= 1");
     if (d_mu && !d_sigma) return fail(BCMPC_ERR_ARG, "d_mu without d_sigma");
     if (cem_iter < 0 || cem_iter >= (1 << 22)) return fail(BCMPC_ERR_ARG, "cem_iter must be in [0, 2^22)");
-    if (!e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
+    if (!e->cost.has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
     return BCMPC_OK;
 }
 
@@ -668,15 +453,8 @@ int bcmpc_trajectory_cost_steps_async(bcmpc_engine* e, const double* d_traj, con
                                       void* stream) {
     if (const int rc = trajectory_cost_check(e, d_traj, d_mu, d_sigma, cem_iter, K, d_costs)) return rc;
     CostInputs in{};
-    if (e->tc_x) {                                       // an extended list: one environment, the engine's inputs
-        if (e->tcx.n_ref_slots > 0 && !e->has_inputs)
-            return fail(BCMPC_ERR_STATE, "the cost terms name reference channels: bcmpc_set_cost_inputs has not been called");
-        if (e->in_ref_envs > 1 || e->in_prev_envs > 1)
-            return fail(BCMPC_ERR_ARG, "the inputs were set for several environments: bcmpc_trajectory_cost_inputs_async "
-                                       "takes the environment layout");
-        in.env_paths = K;
-        in.ref = e->in_ref_envs ? e->d_tc_ref : nullptr; in.ref_envs = e->in_ref_envs; in.ref_steps = e->in_ref_steps;
-        in.prev = e->in_prev_envs ? e->d_tc_prev : nullptr; in.prev_envs = e->in_prev_envs;
+    if (e->cost.ext) {                                   // an extended list: one environment, the engine's inputs
+        if (const int rc = stored_inputs_one_env(e->cost, K, e->d_tc_ref, e->d_tc_prev, &in)) return rc;
     }
     HIP_TRY(hipSetDevice(e->cfg.device));
     return term_cost_launch(e, d_traj, d_actions, seed, cand_offset, d_mu, d_sigma, cem_iter, K, d_costs, d_term_step,
@@ -689,15 +467,15 @@ int bcmpc_trajectory_cost_inputs_async(bcmpc_engine* e, const double* d_traj, co
                                        int64_t env_paths, const double* d_ref, int32_t ref_envs, int32_t ref_steps,
                                        const double* d_prev, int32_t prev_envs, void* stream) {
     if (const int rc = trajectory_cost_check(e, d_traj, d_mu, d_sigma, cem_iter, K, d_costs)) return rc;
-    if (!e->tc_x) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms_x has not set a list with reference channels or RATE terms");
+    if (!e->cost.ext) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms_x has not set a list with reference channels or RATE terms");
     if (env_paths < 1 || K % env_paths != 0) return fail(BCMPC_ERR_ARG, "K must be a multiple of env_paths >= 1");
     const int64_t n_envs = K / env_paths;
-    if (e->tcx.n_ref_slots > 0) {
+    if (e->cost.tpl.n_ref_slots > 0) {
         if (!d_ref) return fail(BCMPC_ERR_ARG, "the list names reference channels: d_ref must not be null");
         if (ref_envs != 1 && ref_envs != n_envs) return fail(BCMPC_ERR_ARG, "ref_envs must be 1 or K / env_paths");
         if (ref_steps != 1 && ref_steps != e->cfg.horizon) return fail(BCMPC_ERR_ARG, "ref_steps must be 1 or the horizon");
     }
-    if (d_prev && e->tcx.has_rate && prev_envs != 1 && prev_envs != n_envs)
+    if (d_prev && e->cost.tpl.has_rate && prev_envs != 1 && prev_envs != n_envs)
         return fail(BCMPC_ERR_ARG, "prev_envs must be 1 or K / env_paths");
     CostInputs in{};
     in.env_paths = env_paths;
@@ -951,24 +729,25 @@ int team_fallback(bcmpc_engine* e, bool collective) {
     }
     if (e->reward)
         if (const int rc = bcmpc_set_discount(f, e->gamma)) return rc;
-    if (e->has_terms) {                              // (the same shape: the launch template carries over)
-        f->tc = e->tc;
-        f->tc_terms = e->tc_terms;
-        f->has_terms = true;
-        const bool n_ref_moved = f->tc_x != e->tc_x || f->tcx.n_ref != e->tcx.n_ref;
-        f->tc_x = e->tc_x;
-        f->tc_refs = e->tc_refs;
-        f->tcx = e->tcx;
-        if (n_ref_moved) f->has_inputs = false;
-        if (e->tc_x && e->has_inputs && !f->has_inputs)      // (set before the fallback existed)
-            if (const int rc = bcmpc_set_cost_inputs(f, e->h_in_ref.empty() ? nullptr : e->h_in_ref.data(), e->in_ref_envs,
-                                                     e->in_ref_steps, e->h_in_prev.empty() ? nullptr : e->h_in_prev.data(),
-                                                     e->in_prev_envs))
+    CostState& fc = f->cost;
+    const CostState& ec = e->cost;
+    if (ec.has_terms) {                              // (the same shape: the launch template carries over)
+        if (fc.ext != ec.ext || fc.n_ref != ec.n_ref) fc.has_inputs = false;
+        fc.terms = ec.terms;
+        fc.refs = ec.refs;
+        fc.n_ref = ec.n_ref;
+        fc.ext = ec.ext;
+        fc.tpl = ec.tpl;
+        fc.has_terms = true;
+        if (ec.ext && ec.has_inputs && !fc.has_inputs)       // (set before the fallback existed)
+            if (const int rc = bcmpc_set_cost_inputs(f, e->h_in_ref.empty() ? nullptr : e->h_in_ref.data(), ec.in_ref_envs,
+                                                     ec.in_ref_steps, e->h_in_prev.empty() ? nullptr : e->h_in_prev.data(),
+                                                     ec.in_prev_envs))
                 return rc;
     }
-    f->tc_conds = e->tc_conds;                       // (a synchronous call: the fallback's step buffer may be made here)
-    f->done_cost = e->done_cost;
-    if (!f->tc_conds.empty() && !f->d_tc_steps)
+    fc.conds = ec.conds;                             // (a synchronous call: the fallback's step buffer may be made here)
+    fc.done_cost = ec.done_cost;
+    if (!fc.conds.empty() && !f->d_tc_steps)
         HIP_TRY(hipMalloc(&f->d_tc_steps, (size_t)std::max<int64_t>(1, f->cfg.num_paths) * sizeof(int32_t)));
     if (e->has_value && (!f->has_value || f->value_version != e->value_version || f->tv.weight != e->tv.weight)) {
         const bcmpc_value_net vn = e->hv_copy.view();
@@ -1178,10 +957,10 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     // cost terms: the rollout kernel runs as a BCMPC_COST_NONE launch that writes the trajectory (the caller's
     // or the scratch), term_cost_kernel turns it into d_costs, and the ordinary argmin launch follows
     const bool terms = c.cost == BCMPC_COST_TERMS;
-    if (terms && !e->has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
+    if (terms && !e->cost.has_terms) return fail(BCMPC_ERR_STATE, "bcmpc_set_cost_terms has not been called");
     CostInputs cost_in{};                                // an extended list: this call's reference / previous actions
-    if (terms && e->tc_x)
-        if (const int rc = engine_cost_inputs(e, r.n_envs, &cost_in)) return rc;
+    if (terms && e->cost.ext)
+        if (const int rc = engine_cost_inputs(e, e->cfg.num_paths, r.n_envs, &cost_in)) return rc;
     // terminal value: the rollout also writes the trajectory (beside its fused cost), terminal_value_kernel adds
     // weight * V(traj[H][k]) to d_costs[k], and the ordinary argmin launch follows -- no fused argmin tail
     const bool value = e->has_value;
@@ -1194,7 +973,7 @@ int rollout_impl(bcmpc_engine* e, const RolloutLaunch& r) {
     if (terms || value) d_traj = d_traj ? d_traj : e->d_tc_traj;
     // termination: term_cost_kernel leaves every candidate's terminating step in the engine's buffer and
     // terminal_value_kernel adds the value only where that step is the horizon (the candidate is alive)
-    int32_t* const d_steps = terms && e->tc.n_done > 0 ? e->d_tc_steps : nullptr;
+    int32_t* const d_steps = terms && e->cost.tpl.b.n_done > 0 ? e->d_tc_steps : nullptr;
     e->steps_on_fb = false;
     RolloutArgs a{};
     for (int l = 0; l < e->nwl; ++l) {
@@ -1612,7 +1391,7 @@ int bcmpc_engine_layout(const bcmpc_engine* e, char* buf, int32_t cap) {
                 std::snprintf(s, sizeof(s), "rollout_x3<%d,NC=%d,NW=%d> %s", e->HP, e->nc, e->nw, prec);
     }
     std::snprintf(buf, (size_t)cap, "%s%s%s%s", s, e->cfg.cost == BCMPC_COST_TERMS ? "+terms" : "",
-                  e->has_value ? "+value" : "", e->tc_conds.empty() ? "" : "+done");
+                  e->has_value ? "+value" : "", e->cost.conds.empty() ? "" : "+done");
     return BCMPC_OK;
 }
 

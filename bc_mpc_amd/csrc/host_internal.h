@@ -177,30 +177,19 @@ struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, 
     uint32_t* d_spec_xs = nullptr;
     uint32_t* d_spec_part = nullptr;
     bcmpc_comm* comm = nullptr;         // attached communicator: results exchanged after every argmin
-    // BCMPC_COST_TERMS (term_cost.hip): the launch template bcmpc_set_cost_terms builds (digested terms, slots)
-    // and the trajectory scratch [H+1][num_paths][S] the rollout writes when the caller passes no d_traj --
-    // allocated at create, never inside a stream-ordered entry (a captured graph keeps the address)
-    TermCostArgs tc{};
-    bool has_terms = false;
+    // BCMPC_COST_TERMS (term_cost.hip): the lists the setters stored and the launch template digested from them
+    // (cost_terms.h), and the trajectory scratch [H+1][num_paths][S] the rollout writes when the caller passes no
+    // d_traj -- allocated at create, never inside a stream-ordered entry (a captured graph keeps the address)
+    bcmpc::host::CostState cost;
     double* d_tc_traj = nullptr;
-    // termination (bcmpc_set_termination): the cost terms and done conditions as given -- tc is digested from both,
-    // by whichever setter was called last -- and the launch chains' termination steps [num_paths], allocated by
-    // the setter (a captured graph keeps the address).  steps_on_fb: the last synchronous call reran on fb
-    std::vector<bcmpc_cost_term> tc_terms, tc_conds;
-    double done_cost = 0.0;
+    // termination (bcmpc_set_termination): the launch chains' termination steps [num_paths], allocated by the
+    // setter (a captured graph keeps the address).  steps_on_fb: the last synchronous call reran on fb
     int32_t* d_tc_steps = nullptr;
     bool steps_on_fb = false;
-    // reference tracking (term_cost_x.hip; bcmpc_set_cost_terms_x / bcmpc_set_cost_inputs).  tc_x: the list names
-    // a channel or has a RATE term (RATE sits in tc_terms as kind 4); tc_refs: every term's channel or -1, empty
-    // for a plain list; tcx: what digest_terms adds to tc for those instances.  The inputs: device buffers that
-    // bcmpc_set_cost_inputs allocates (they only grow) and fills, with host copies for the fallback engine
-    bool tc_x = false;
-    std::vector<int32_t> tc_refs;
-    TermCostXArgs tcx{};
-    bool has_inputs = false;
+    // reference tracking (bcmpc_set_cost_inputs): device buffers that the setter allocates (they only grow) and
+    // fills, with host copies for the fallback engine
     double *d_tc_ref = nullptr, *d_tc_prev = nullptr;
     size_t tc_ref_cap = 0, tc_prev_cap = 0;             // in doubles
-    int32_t in_ref_envs = 0, in_ref_steps = 0, in_prev_envs = 0;    // in_prev_envs == 0: no previous action
     std::vector<double> h_in_ref, h_in_prev;
     // terminal value (terminal_value.hip): the launch template bcmpc_set_terminal_value builds.  The packed
     // kernels and the parameter block are allocated once at their largest size (a captured graph keeps the

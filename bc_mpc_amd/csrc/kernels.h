@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/bcmpc.h"
+#include "cost_terms.h"
 #include "shapes.h"
 
 namespace bcmpc {
@@ -229,57 +230,9 @@ struct SegmentArgminArgs {                   // one np.argmin record per environ
     int32_t n_envs, A;
     int32_t maximize;                        // np.argmax (learned reward)
 };
-// ---- declarative cost terms (term_cost.hip): costs[K] from a stored trajectory ----
-// The host compacts what the terms read into at most BCMPC_MAX_COST_TERMS slots: slot i of row r is the
-// state dim slot_index[i] of traj[r][k] (slot_action[i] == 0) or action slot_index[i] of step r (== 1, last).  A term
-// reads its slot of row h (STATE, ACTION, DIFF's s) or of row h + 1 (NEXT_STATE, DIFF's s').
-struct TermDev {                             // one bcmpc_cost_term as the kernel reads it: one 32-byte scalar load
-    double weight, param;
-    double rparam;                           // DIFF: RN(1 / param), div_rn's r
-    uint32_t meta;                           // kind | cmp << 2 | (NEXT_STATE) << 4 | (div_rn applies) << 5 | slot << 8
-    uint32_t pad;
-};
-struct TermCostArgs {
-    const double* traj;                      // [H+1][K][S]
-    const double* actions;                   // [H][K][A] or nullptr => regenerated (action slots only)
-    const double* cem_mu;                    // [H][A] or nullptr: cem_action instead of rng_action
-    const double* cem_sigma;
-    double* costs;                           // [K]
-    uint64_t seed;
-    int64_t cand_offset, K;
-    int32_t H, S, A, cem_iter;
-    int32_t n_terms, n_slots, n_state_slots;  // slots [n_state_slots, n_slots) are the action slots
-    uint8_t slot_index[BCMPC_MAX_COST_TERMS];
-    uint8_t slot_action[BCMPC_MAX_COST_TERMS];
-    uint32_t slot_word[BCMPC_MAX_COST_TERMS / 4];   // (filled by launch_term_cost) the two arrays, a byte per slot
-    double low[BCMPC_MAX_ACTION], high[BCMPC_MAX_ACTION];   // action bounds (regenerated actions)
-    TermDev terms[BCMPC_MAX_COST_TERMS];     // by value: 32 x 32 bytes, no per-launch upload
-    // termination (cost_functions.episode_cost): terms[n_terms .. n_terms + n_done) are the done conditions
-    // (THRESHOLD on NEXT_STATE, a state slot each, ORed); n_terms + n_done <= BCMPC_MAX_COST_TERMS
-    int32_t n_done;
-    double done_cost;                        // added once, at the terminating step
-    int32_t* term_step;                      // [K] the terminating step, H: never; or nullptr (n_done > 0 only)
-};
-hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);
-
-// ---- reference tracking (term_cost_x.hip): lists with reference channels or RATE terms ----
-// An argument struct of its own, so that TermCostArgs and the instances of term_cost.hip stay as they are.  b is
-// read as there, with three differences.  The slots are the state dims, then the reference channels
-// (slot_action == 2, slot_index the channel), then the actions: slots [b.n_state_slots, b.n_state_slots +
-// n_ref_slots) are the channels.  A TermDev's meta has bit 6 set where its param is the channel slot in `pad`,
-// and bit 7 set for a RATE term (kind bits QUADRATIC).  Candidate k reads environment k / env_paths.
-struct TermCostXArgs {
-    TermCostArgs b;
-    const double* ref;                       // [ref_envs][ref_steps][n_ref] or nullptr (n_ref_slots == 0)
-    const double* prev;                      // [prev_envs][A] or nullptr: a_{-1} := a_0
-    int64_t env_paths;                       // K is a multiple of it
-    int64_t ref_env_stride;                  // ref_steps * n_ref, 0: one reference for all environments
-    int64_t ref_row_stride;                  // n_ref, 0: constant over the horizon
-    int64_t prev_env_stride;                 // A, 0: one previous action for all environments
-    int32_t n_ref_slots, n_ref;
-    int32_t has_rate;                        // the list has a RATE term: row -1 of the action slots is filled
-};
-hipError_t launch_term_cost_x(const TermCostXArgs& a, hipStream_t st);
+// ---- declarative cost terms (term_cost.hip; TermCostArgs / TermCostXArgs and the host logic: cost_terms.h) ----
+hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st);      // the plain variant
+hipError_t launch_term_cost_x(const TermCostXArgs& a, hipStream_t st);   // lists with reference channels or RATE terms
 
 // ---- model ensembles (ensemble.hip): out[k] = rule over member_costs[0..E-1][k] ----
 struct EnsembleReduceArgs {

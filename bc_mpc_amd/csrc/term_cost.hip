@@ -3,6 +3,8 @@
 // costs[k] = sum_h c_h(traj[h][k], a[h][k], traj[h+1][k]) for a list of at most 32 terms (include/bcmpc.h,
 // bcmpc_cost_term): the objective of a BCMPC_COST_TERMS engine, launched between the rollout kernel (which
 // writes the trajectory and no cost) and the ordinary argmin / select / MPPI kernels (which read costs[K]).
+// One kernel template in two variants: the plain one (X = false, TermCostArgs) and the extended one (X = true,
+// TermCostXArgs) for lists with reference channels or RATE terms; a list without either never runs the latter.
 //
 // One lane owns one candidate.  The terms of a step are added in list order and the steps in step order,
 // each with one explicit round-to-nearest f64 intrinsic (the file is built with -ffp-contract=off), so a
@@ -33,11 +35,32 @@
 // the candidate is alive and, on a flagged step, adds done_cost once, notes the step and pays nothing after it.
 // The padded steps of the last trip (scored on the repeated row) neither pay nor terminate.  Dead lanes ride
 // along to the end of the walk: a wave that leaves once all of its lanes are dead measured no faster.
+//
+// What the extended variant adds (the NumPy definition is episode_cost with reference / previous_action); every
+// difference is an `if constexpr (X)` or the compile-time row offset P (the chain over a term's kind is written once
+// per variant), so the plain instances keep their kernel-argument block and all forty instances the machine code they
+// had as two units (profiles/term_cost_merge_digest.txt):
+//
+// * The environment.  A launch covers K = n_envs * env_paths candidates; lane k reads the reference and the
+//   previous action of environment k / env_paths (local k).  env_paths need not be a multiple of 64, so the
+//   lanes of a wave may belong to two or more environments: the index is per lane, computed once.
+//
+// * A reference channel is one more slot.  Its per-lane base is ref + env * ref_env_stride + c and its row
+//   stride is n_ref (a reference per step) or 0 (constant over the horizon); row h is step h's, clamped to
+//   H - 1 like an action's.  It rides the prefetch-ahead ring with the state dims, and a term's p becomes a
+//   ring read like its x: no load inside the term loop, every load unconditional and in bounds.  The slots are
+//   ordered state dims, channels, actions (the regenerated actions stay last).
+//
+// * RATE needs a_{h-1}.  The ring is one row deeper (P = 1, PF + 2 rows): in the trip of steps
+//   h0 .. h0 + PF - 1 it holds rows h0 - 1 .. h0 + PF, so step h0 finds the action of step h0 - 1 where the
+//   previous trip left it -- loaded from the explicit array, or regenerated there with the functions the
+//   rollout kernels call.  Row -1 is written before the first trip: the previous action of the lane's
+//   environment, or, without one, a_0 itself (d is then a_0 - a_0, as the definition has it).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cmath>
+#include <type_traits>
 
 #include "../../include/bcmpc.h"
 #include "kernels.h"
@@ -65,52 +88,108 @@ __device__ __forceinline__ double term_div(double a, double b, double r, bool fa
     return __ddiv_rn(a, b);
 }
 
-template <int ND, int PF, bool REGEN, bool DONE>
-__global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArgs a) {
-    constexpr int R = PF + 1;                            // LDS ring: row r lives in rows[r % R]
+// (extended) row r of a slot: a channel's and an explicit action's rows end at H - 1, a state dim's at H (by
+// value: the strides are uniform and stay in scalar registers)
+__device__ __forceinline__ double load_slot(const double* p, uint32_t chan, uint32_t act, int r, int H, int64_t RS,
+                                            int64_t KA, int64_t KS) {
+    const int rs = r < H ? r : H, ra = r < H ? r : H - 1;
+    const int64_t row = chan | act ? ra : rs;
+    const int64_t stride = chan ? RS : act ? KA : KS;
+    return p[row * stride];
+}
+
+// what a variant's argument block holds: the block both share, and the extended fields read outside `if constexpr`
+__host__ __device__ __forceinline__ const TermCostArgs& term_base(const TermCostArgs& a) { return a; }
+__host__ __device__ __forceinline__ const TermCostArgs& term_base(const TermCostXArgs& ax) { return ax.b; }
+__host__ __device__ __forceinline__ TermCostArgs& term_base(TermCostArgs& a) { return a; }
+__host__ __device__ __forceinline__ TermCostArgs& term_base(TermCostXArgs& ax) { return ax.b; }
+__device__ __forceinline__ int64_t term_env(const TermCostArgs&, int64_t) { return 0; }
+__device__ __forceinline__ int64_t term_env(const TermCostXArgs& ax, int64_t k) { return k / ax.env_paths; }
+__device__ __forceinline__ int64_t term_ref_stride(const TermCostArgs&) { return 0; }
+__device__ __forceinline__ int64_t term_ref_stride(const TermCostXArgs& ax) { return ax.ref_row_stride; }
+
+template <bool X, int ND, int PF, bool REGEN, bool DONE>
+__global__ __launch_bounds__(kTermLanes) void term_cost_kernel(
+    const std::conditional_t<X, TermCostXArgs, TermCostArgs> ax) {
+    constexpr int P = X ? 1 : 0;                         // rows the ring keeps behind row h0 (extended: row h0 - 1)
+    constexpr int R = PF + 1 + P;                        // LDS ring: row r lives in rows[(r + P) % R], r >= -P
     __shared__ double rows[R][ND][kTermLanes];
+    const TermCostArgs& a = term_base(ax);
     const int lane = threadIdx.x;
     const int64_t k = (int64_t)blockIdx.x * kTermLanes + lane;
     if (k >= a.K) return;                                // tail lanes (no barrier follows)
     const uint64_t g = (uint64_t)(a.cand_offset + k);
+    const int64_t env = term_env(ax, k);                 // (extended) this lane's environment
     const int nd = a.n_slots, H = a.H;
 
-    // Every slot is a load with a per-lane base and a uniform row stride, set up once: a state dim walks the
-    // trajectory's rows 0 .. H; an action of the explicit array walks that array's rows 0 .. H - 1.  A
-    // regenerated action's slot is filled when its trip is scored; its load reads state dim 0 instead, a
-    // value that is then overwritten.  amask: the explicit-action slots.
+    // Every slot is a load with a per-lane base and a uniform row stride, set up once.  The slots, a byte each:
+    // index | channel << 6 | action << 7.  A state dim walks the trajectory's rows 0 .. H; an action of the
+    // explicit array walks that array's rows 0 .. H - 1, and so does a channel its environment's reference
+    // rows.  A regenerated action's slot is filled when its trip is scored; its load reads state dim 0 instead,
+    // a value that is then overwritten.  amask: the explicit-action slots; rmask: the channel slots.
     uint32_t sw[ND / 4];
 #pragma unroll
     for (int j = 0; j < ND / 4; ++j) sw[j] = a.slot_word[j];
     const bool have_actions = a.actions != nullptr;
-    const int64_t KS = a.K * a.S, KA = a.K * a.A;
+    const int64_t KS = a.K * a.S, KA = a.K * a.A, RS = term_ref_stride(ax);
     const double* sp[ND];
-    uint32_t amask = 0;
+    uint32_t amask = 0, rmask = 0;
 #pragma unroll
     for (int i = 0; i < ND; ++i) {
         const uint32_t b = (sw[i >> 2] >> (8 * (i & 3))) & 0xffu;
         const bool act = (b >> 7) != 0;
         if (act && have_actions) amask |= 1u << i;
-        sp[i] = act ? (have_actions ? a.actions + k * a.A + (b & 31u) : a.traj + k * a.S)
-                    : a.traj + k * a.S + (b & 31u);
+        if constexpr (X) {
+            const bool chan = ((b >> 6) & 1u) != 0;
+            if (chan) rmask |= 1u << i;
+            sp[i] = chan ? ax.ref + env * ax.ref_env_stride + (b & 31u)
+                  : act  ? (have_actions ? a.actions + k * a.A + (b & 31u) : a.traj + k * a.S)
+                         : a.traj + k * a.S + (b & 31u);
+        } else {
+            sp[i] = act ? (have_actions ? a.actions + k * a.A + (b & 31u) : a.traj + k * a.S)
+                        : a.traj + k * a.S + (b & 31u);
+        }
     }
     // (one load instruction per slot and row, no branch around it: a load whose value passes through a select
     //  or a guarded block is waited for at once, and nothing would stay in flight.  Rows past the last -- H,
-    //  or H - 1 of the action array -- repeat it, slots past n_slots read state dim 0: in bounds, never used)
+    //  or H - 1 of the action array or a reference -- repeat it, slots past n_slots read state dim 0: in
+    //  bounds, never used)
     auto load = [&](int i, int r) -> double {
-        r = r < H ? r : H;
-        const int64_t off = (amask >> i) & 1u ? (int64_t)(r < H ? r : H - 1) * KA : (int64_t)r * KS;
-        return sp[i][off];
+        if constexpr (X) {
+            return load_slot(sp[i], (rmask >> i) & 1u, (amask >> i) & 1u, r, H, RS, KA, KS);
+        } else {
+            r = r < H ? r : H;
+            const int64_t off = (amask >> i) & 1u ? (int64_t)(r < H ? r : H - 1) * KA : (int64_t)r * KS;
+            return sp[i][off];
+        }
     };
 
     // row 0 into LDS; rows 1 .. PF into the registers
 #pragma unroll
-    for (int i = 0; i < ND; ++i) rows[0][i][lane] = load(i, 0);
+    for (int i = 0; i < ND; ++i) rows[P][i][lane] = load(i, 0);
     double pf[PF][ND];
 #pragma unroll
     for (int u = 0; u < PF; ++u)
 #pragma unroll
         for (int i = 0; i < ND; ++i) pf[u][i] = load(i, u + 1);
+
+    auto act0 = [&]() -> int {                           // the first action slot (the channels sit before it)
+        if constexpr (X) return a.n_state_slots + ax.n_ref_slots;
+        else return a.n_state_slots;
+    };
+
+    // (extended) row -1, the action slots of a list with RATE terms: the environment's previous action, else a_0
+    if constexpr (X) {
+        if (ax.has_rate) {
+#pragma unroll 1
+            for (int i = act0(); i < nd; ++i) {
+                const int j = (a.slot_word[i >> 2] >> (8 * (i & 3))) & 31u;
+                rows[0][i][lane] = ax.prev      ? ax.prev[env * ax.prev_env_stride + j]
+                                   : have_actions ? rows[1][i][lane]
+                                                  : term_regen(a, 0, j, g);
+            }
+        }
+    }
 
     // The terms are uniform, one 32-byte scalar load each: term t + 1 (term 0 of the next trip after the
     // last) is requested before term t is evaluated.
@@ -125,12 +204,12 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
 #pragma unroll 1
     for (int h0 = 0; h0 < H; h0 += PF) {
         // rows h0 + 1 .. h0 + PF arrive and go to the ring; their registers take the next trip's rows
-        const int b0 = h0 % R;                           // ring position of row h0
-        auto pos = [&](int u) { return b0 + u < R ? b0 + u : b0 + u - R; };   // ... of row h0 + u
+        const int b0 = h0 % R;                           // ring position of row h0 - P
+        auto pos = [&](int v) { return b0 + v < R ? b0 + v : b0 + v - R; };   // ... of row h0 - P + v
 #pragma unroll
         for (int u = 0; u < PF; ++u)
 #pragma unroll
-            for (int i = 0; i < ND; ++i) rows[pos(u + 1)][i][lane] = pf[u][i];
+            for (int i = 0; i < ND; ++i) rows[pos(u + 1 + P)][i][lane] = pf[u][i];
 #pragma unroll
         for (int u = 0; u < PF; ++u)
 #pragma unroll
@@ -141,8 +220,8 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
             for (int u = 0; u < PF; ++u) {
                 if (h0 + u >= H) break;
 #pragma unroll 1
-                for (int i = a.n_state_slots; i < nd; ++i)
-                    rows[pos(u)][i][lane] =
+                for (int i = act0(); i < nd; ++i)
+                    rows[pos(u + P)][i][lane] =
                         term_regen(a, h0 + u, (a.slot_word[i >> 2] >> (8 * (i & 3))) & 31u, g);
             }
         }
@@ -157,42 +236,97 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
             tn = tn + 1 < nt ? tn + 1 : 0;
             const TermDev T = cur;
             cur = a.terms[tn];
-            const uint32_t kind = T.meta & 3u, cmp = (T.meta >> 2) & 3u;
-            const int sl = (int)(T.meta >> 8);
-            const int nx = (T.meta >> 4) & 1u;           // NEXT_STATE: the value of row h + 1
-            const double w = T.weight, p = T.param;
-            if (DONE && t >= nc) {
+            // The chain over a term's kind is written once per variant.  Shared, with the channel read of p and the
+            // RATE branch guarded, it compiled to the two-unit build's code in 30 of the 40 instances only: a local
+            // that reads T.pad must not exist in a plain instance and must sit here, ahead of the chain, in an
+            // extended one (profiles/term_cost_merge_digest.txt).  A new kind or comparison goes into both.
+            if constexpr (X) {
+                const uint32_t kind = T.meta & 3u, cmp = (T.meta >> 2) & 3u;
+                const int sl = (int)(T.meta >> 8);
+                const int nx = (T.meta >> 4) & 1u;           // NEXT_STATE: the value of row h + 1
+                const bool chan = (T.meta >> 6) & 1u;        // p is the channel slot T.pad of row h
+                const int psl = (int)T.pad;
+                const double w = T.weight, p = T.param;
+                if (DONE && t >= nc) {
 #pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    const double x = rows[pos(u + 1)][sl][lane];
-                    const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
-                                   : cmp == BCMPC_CMP_LE ? x <= p : x < p;
-                    flags |= (hit ? 1u : 0u) << u;
+                    for (int u = 0; u < PF; ++u) {
+                        const double x = rows[pos(u + 1 + P)][sl][lane];
+                        const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
+                                       : cmp == BCMPC_CMP_LE ? x <= p : x < p;
+                        flags |= (hit ? 1u : 0u) << u;
+                    }
+                } else if ((T.meta >> 7) & 1u) {             // RATE
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double d = __dsub_rn(rows[pos(u + P)][sl][lane], rows[pos(u)][sl][lane]);
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, __dmul_rn(d, d)));
+                    }
+                } else if (kind == BCMPC_TERM_DIFF) {
+                    const bool fast = (T.meta >> 5) & 1u;
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double d = __dsub_rn(rows[pos(u + 1 + P)][sl][lane], rows[pos(u + P)][sl][lane]);
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, term_div(d, p, T.rparam, fast)));
+                    }
+                } else if (kind == BCMPC_TERM_THRESHOLD) {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double x = rows[nx ? pos(u + 1 + P) : pos(u + P)][sl][lane];
+                        const double q = chan ? rows[pos(u + P)][psl][lane] : p;
+                        const bool hit = cmp == BCMPC_CMP_GE ? x >= q : cmp == BCMPC_CMP_GT ? x > q
+                                       : cmp == BCMPC_CMP_LE ? x <= q : x < q;
+                        acc[u] = hit ? __dadd_rn(acc[u], w) : acc[u];
+                    }
+                } else if (kind == BCMPC_TERM_LINEAR) {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u)
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, rows[nx ? pos(u + 1 + P) : pos(u + P)][sl][lane]));
+                } else {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double q = chan ? rows[pos(u + P)][psl][lane] : p;
+                        const double d = __dsub_rn(rows[nx ? pos(u + 1 + P) : pos(u + P)][sl][lane], q);
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, __dmul_rn(d, d)));
+                    }
                 }
-            } else if (kind == BCMPC_TERM_DIFF) {
-                const bool fast = (T.meta >> 5) & 1u;
-#pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    const double d = __dsub_rn(rows[pos(u + 1)][sl][lane], rows[pos(u)][sl][lane]);
-                    acc[u] = __dadd_rn(acc[u], __dmul_rn(w, term_div(d, p, T.rparam, fast)));
-                }
-            } else if (kind == BCMPC_TERM_THRESHOLD) {
-#pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    const double x = rows[nx ? pos(u + 1) : pos(u)][sl][lane];
-                    const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
-                                   : cmp == BCMPC_CMP_LE ? x <= p : x < p;
-                    acc[u] = hit ? __dadd_rn(acc[u], w) : acc[u];
-                }
-            } else if (kind == BCMPC_TERM_LINEAR) {
-#pragma unroll
-                for (int u = 0; u < PF; ++u)
-                    acc[u] = __dadd_rn(acc[u], __dmul_rn(w, rows[nx ? pos(u + 1) : pos(u)][sl][lane]));
             } else {
+                const uint32_t kind = T.meta & 3u, cmp = (T.meta >> 2) & 3u;
+                const int sl = (int)(T.meta >> 8);
+                const int nx = (T.meta >> 4) & 1u;           // NEXT_STATE: the value of row h + 1
+                const double w = T.weight, p = T.param;
+                if (DONE && t >= nc) {
 #pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    const double d = __dsub_rn(rows[nx ? pos(u + 1) : pos(u)][sl][lane], p);
-                    acc[u] = __dadd_rn(acc[u], __dmul_rn(w, __dmul_rn(d, d)));
+                    for (int u = 0; u < PF; ++u) {
+                        const double x = rows[pos(u + 1)][sl][lane];
+                        const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
+                                       : cmp == BCMPC_CMP_LE ? x <= p : x < p;
+                        flags |= (hit ? 1u : 0u) << u;
+                    }
+                } else if (kind == BCMPC_TERM_DIFF) {
+                    const bool fast = (T.meta >> 5) & 1u;
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double d = __dsub_rn(rows[pos(u + 1)][sl][lane], rows[pos(u)][sl][lane]);
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, term_div(d, p, T.rparam, fast)));
+                    }
+                } else if (kind == BCMPC_TERM_THRESHOLD) {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double x = rows[nx ? pos(u + 1) : pos(u)][sl][lane];
+                        const bool hit = cmp == BCMPC_CMP_GE ? x >= p : cmp == BCMPC_CMP_GT ? x > p
+                                       : cmp == BCMPC_CMP_LE ? x <= p : x < p;
+                        acc[u] = hit ? __dadd_rn(acc[u], w) : acc[u];
+                    }
+                } else if (kind == BCMPC_TERM_LINEAR) {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u)
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, rows[nx ? pos(u + 1) : pos(u)][sl][lane]));
+                } else {
+#pragma unroll
+                    for (int u = 0; u < PF; ++u) {
+                        const double d = __dsub_rn(rows[nx ? pos(u + 1) : pos(u)][sl][lane], p);
+                        acc[u] = __dadd_rn(acc[u], __dmul_rn(w, __dmul_rn(d, d)));
+                    }
                 }
             }
         }
@@ -216,47 +350,45 @@ __global__ __launch_bounds__(kTermLanes) void term_cost_kernel(const TermCostArg
     if (DONE && a.term_step) a.term_step[k] = tstep;
 }
 
-template <int ND, int PF>
-hipError_t launch_t(TermCostArgs a, hipStream_t st) {
-    for (int i = 0; i < a.n_slots; ++i)          // the slots as the kernel reads them: index | action << 7, a byte each
-        a.slot_word[i >> 2] |= (uint32_t)(a.slot_index[i] | (a.slot_action[i] ? 0x80 : 0)) << (8 * (i & 3));
-    const bool regen = !a.actions && a.n_state_slots < a.n_slots;     // Philox only where an ACTION term needs it
-    const int64_t blocks = (a.K + kTermLanes - 1) / kTermLanes;
+template <bool X, int ND, int PF>
+hipError_t launch_t(std::conditional_t<X, TermCostXArgs, TermCostArgs> ax, hipStream_t st) {
+    TermCostArgs& a = term_base(ax);
+    host::pack_slots(&a);                                // the slots as the kernel reads them, a byte each
+    int n_ref_slots = 0;
+    if constexpr (X) n_ref_slots = ax.n_ref_slots;
+    const bool regen = !a.actions && a.n_state_slots + n_ref_slots < a.n_slots;   // Philox only where an ACTION
+    const int64_t blocks = (a.K + kTermLanes - 1) / kTermLanes;                   // term needs it
     if (blocks > INT32_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(kTermLanes);
     if (a.n_done > 0) {                                  // termination: the DONE instances, a family of their own
-        if (regen) hipLaunchKernelGGL((term_cost_kernel<ND, PF, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((term_cost_kernel<ND, PF, false, true>), grid, block, 0, st, a);
+        if (regen) hipLaunchKernelGGL((term_cost_kernel<X, ND, PF, true, true>), grid, block, 0, st, ax);
+        else hipLaunchKernelGGL((term_cost_kernel<X, ND, PF, false, true>), grid, block, 0, st, ax);
     } else if (regen) {
-        hipLaunchKernelGGL((term_cost_kernel<ND, PF, true, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((term_cost_kernel<X, ND, PF, true, false>), grid, block, 0, st, ax);
     } else {
-        hipLaunchKernelGGL((term_cost_kernel<ND, PF, false, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((term_cost_kernel<X, ND, PF, false, false>), grid, block, 0, st, ax);
     }
     return hipGetLastError();
 }
 
+// ND slots (every one is loaded: the smallest instance that holds n_slots, the channels counted in) x PF rows in
+// flight: at most 32 doubles (64 VGPRs) of prefetch registers in every instance
+template <bool X>
+hipError_t launch_any(const std::conditional_t<X, TermCostXArgs, TermCostArgs>& ax, hipStream_t st) {
+    const TermCostArgs& a = term_base(ax);
+    const TermCostXArgs* x = nullptr;
+    if constexpr (X) x = &ax;
+    if (!host::term_launch_ok(a, x)) return hipErrorInvalidValue;
+    if (a.n_slots <= 4) return launch_t<X, 4, 8>(ax, st);
+    if (a.n_slots <= 8) return launch_t<X, 8, 4>(ax, st);
+    if (a.n_slots <= 16) return launch_t<X, 16, 2>(ax, st);
+    if (a.n_slots <= 24) return launch_t<X, 24, 1>(ax, st);
+    return launch_t<X, 32, 1>(ax, st);
+}
+
 }  // namespace
 
-// ND slots (every one is loaded: the smallest instance that holds n_slots) x PF rows in flight: at most 32
-// doubles (64 VGPRs) of prefetch registers in every instance
-hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st) {
-    if (!a.traj || !a.costs || a.K < 1 || a.H < 1 || a.S < 1 || a.S > BCMPC_MAX_STATE || a.A < 1 ||
-        a.A > BCMPC_MAX_ACTION || a.n_terms < 0 || a.n_done < 0 || a.n_terms + a.n_done > BCMPC_MAX_COST_TERMS ||
-        a.n_slots < 0 || a.n_slots > a.n_terms + a.n_done || a.n_state_slots < 0 || a.n_state_slots > a.n_slots ||
-        !std::isfinite(a.done_cost))
-        return hipErrorInvalidValue;
-    for (int i = 0; i < a.n_slots; ++i)
-        if ((a.slot_action[i] != 0) != (i >= a.n_state_slots) || a.slot_index[i] >= (a.slot_action[i] ? a.A : a.S))
-            return hipErrorInvalidValue;
-    for (int t = 0; t < a.n_terms + a.n_done; ++t)
-        if ((int)(a.terms[t].meta >> 8) >= a.n_slots) return hipErrorInvalidValue;
-    for (int t = a.n_terms; t < a.n_terms + a.n_done; ++t)      // a done condition reads a state slot
-        if ((int)(a.terms[t].meta >> 8) >= a.n_state_slots) return hipErrorInvalidValue;
-    if (a.n_slots <= 4) return launch_t<4, 8>(a, st);
-    if (a.n_slots <= 8) return launch_t<8, 4>(a, st);
-    if (a.n_slots <= 16) return launch_t<16, 2>(a, st);
-    if (a.n_slots <= 24) return launch_t<24, 1>(a, st);
-    return launch_t<32, 1>(a, st);
-}
+hipError_t launch_term_cost(const TermCostArgs& a, hipStream_t st) { return launch_any<false>(a, st); }
+hipError_t launch_term_cost_x(const TermCostXArgs& ax, hipStream_t st) { return launch_any<true>(ax, st); }
 
 }  // namespace bcmpc

@@ -1,4 +1,4 @@
-"""Reference tracking on the GPU (csrc/term_cost_x.hip): per-call reference channels and action-rate terms.
+"""Reference tracking on the GPU (the extended variant of csrc/term_cost.hip): per-call reference channels and action-rate terms.
 
 The definition is cost_functions.episode_cost with ``reference`` / ``previous_action``; every comparison below is
 bit for bit (np.array_equal with equal NaN positions) on the trajectory and the actions the kernel was given.
@@ -293,6 +293,82 @@ def test_action_sources_for_the_rate_term(S, A, H):
                 same(got, want, f"S={S} H={H} {label} prev={p is not None}")
     finally:
         eng.set_action_bounds(nt.low, nt.high)
+
+
+# ------------------------------------------------------------------ 3b. the two variants of the one kernel template
+def _instance(n_slots):
+    """<ND, PF> of launch_term_cost / launch_term_cost_x for a list of n_slots slots."""
+    return (4, 8) if n_slots <= 4 else (8, 4) if n_slots <= 8 else (16, 2) if n_slots <= 16 else \
+        (24, 1) if n_slots <= 24 else (32, 1)
+
+
+def variant_pair(n_state, n_act, n_chan, done):
+    """The same list twice: with constant thresholds / targets (the plain variant scores it) and with the first
+    ``n_chan`` of those constants delivered through reference channels (the extended variant); the constants."""
+    from bc_mpc_amd import cost_functions as cf
+    consts, lists = [], ([], [])
+    slots = [(i, "next_state" if i % 3 == 1 else "state") for i in range(n_state)] + [(j, "action") for j in range(n_act)]
+    for n, (i, on) in enumerate(slots):
+        v, w = VALS[n % 4], 0.5 + 0.25 * n
+        for ext, terms in enumerate(lists):
+            p = v
+            if ext and n < n_chan:
+                p = cf.ref(n)
+            if n % 2:
+                terms.append(cf.quadratic(i, w, target=p, on=on))
+            else:
+                terms.append(cf.threshold(i, (">=", ">", "<=", "<")[(n // 2) % 4], p, w, on=on))
+        if n < n_chan:
+            consts.append(v)
+    kw = dict(done=[cf.done_when(0, ">", 1.6)], done_cost=3.5) if done else {}
+    return cf.TermCost(lists[0], **kw), cf.TermCost(lists[1], **kw), np.array(consts)
+
+
+@pytest.mark.parametrize("slots,n_state,n_act,n_chan", [
+    (4, 1, 1, 2),        # plain  2 slots, extended  4: both <4, 8>
+    (8, 3, 2, 3),        # plain  5 slots, extended  8: both <8, 4>
+    (16, 7, 3, 6),       # plain 10 slots, extended 16: both <16, 2>
+    (24, 13, 5, 6),      # plain 18 slots, extended 24: both <24, 1>
+    (32, 20, 6, 6),      # plain 26 slots, extended 32: both <32, 1> (all of S = 20, A = 6: the channels make up 32)
+])
+def test_plain_and_extended_variants_agree(slots, n_state, n_act, n_chan):
+    """term_cost.hip's two variants are one template: a plain list with constant thresholds and targets, and the
+    same list with those constants in reference channels, give the same bits -- and the definition's.  K = 130 (two
+    full waves, a two-lane tail), env_paths = 65 (a wave's lanes span two environments), H = 9 (every PF has a padded
+    last trip and at least two trips); explicit and regenerated actions, with and without a done condition."""
+    from oracle import mpc_oracle as orc
+    S, A, K, H, seed, off = 20, 6, 130, 9, 0x5EED5, 4000
+    nt = net(S, A)
+    eng = nt.engine("auto", 64, H, weights=False)
+    traj, acts, _, _ = hand_data(S, A, K, H, 1, seed=slots)
+    d_traj, d_acts = _dev(traj), _dev(acts)
+    sources = [("explicit", acts, dict(d_actions=d_acts.data_ptr()), {}),
+               ("philox", orc.device_rng_actions(seed, off, K, H, nt.low, nt.high), {}, dict(seed=seed, cand_offset=off))]
+    for done in (False, True):
+        plain, ext, consts = variant_pair(n_state, n_act, n_chan, done)
+        assert not plain.extended and ext.extended and ext.n_ref == n_chan
+        assert plain.n_slots == n_state + n_act and ext.n_slots == slots
+        assert _instance(plain.n_slots) == _instance(ext.n_slots)          # the same <ND, PF> on both sides
+        for label, want_acts, plain_kw, kw in sources:
+            want, wsteps = definition(plain, traj, want_acts)
+            eng.set_cost_terms(plain)
+            d_costs, d_steps = _empty(K + 8), _steps(K)
+            eng.trajectory_cost_async(d_traj.data_ptr(), K, d_costs.data_ptr(), stream=_stream(),
+                                      d_term_step=d_steps.data_ptr() if done else None, **plain_kw, **kw)
+            got = d_costs.cpu().numpy()
+            assert np.isnan(got[K:]).all(), "wrote past K"
+            where = f"slots={slots} done={done} {label}"
+            same(got[:K], want, where + " plain")
+            if done:
+                same(d_steps.cpu().numpy(), wsteps, where + " plain steps")
+                assert (wsteps < H).any() and (wsteps == H).any(), where
+            eng.set_cost_terms(ext)
+            for ref_steps in (1, H):
+                ref = np.broadcast_to(consts, (2, ref_steps, n_chan))      # every row of both environments equal
+                gx, sx = run_kernel(eng, traj, acts if label == "explicit" else None, ref, None, 65, steps=done, **kw)
+                same(gx, got[:K], f"{where} ref_steps={ref_steps} extended against plain")
+                if done:
+                    same(sx, wsteps, f"{where} ref_steps={ref_steps} extended steps")
 
 
 # ------------------------------------------------------------------ 4. end to end, S = 11, A = 3

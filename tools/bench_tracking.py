@@ -2,10 +2,11 @@
 """What reference channels and a rate term cost beside the same cost with constant targets.
 
 Side (a), "const": two constant-target quadratics on the next state and an action quadratic -- a plain list, scored
-by the instances of csrc/term_cost.hip.  Side (b): the same cost with both targets as reference channels plus a rate
-term on the action it already reads -- an extended list, csrc/term_cost_x.hip, 5 slots against 3 -- with a reference constant over the horizon
-("chan_R", [R]) and one per step ("chan_HR", [H, R]); a call of side (b) is set_cost_inputs (one small upload) plus
-get_action, as a tracking controller makes it every control step.  Three points, each in one process:
+by the plain instances of csrc/term_cost.hip.  Side (b): the same cost with both targets as reference channels plus
+a rate term on the action it already reads -- an extended list, the kernel's extended variant, 5 slots against 3 --
+with a reference constant over the horizon ("chan_R", [R]) and one per step ("chan_HR", [H, R]); a call of side (b)
+is set_cost_inputs (one small upload) plus get_action, as a tracking controller makes it every control step.  Three
+points, each in one process:
 
   cfg3          K = 65,536, H = 20, 2 x 500 tanh
   cfg2          K = 4,096,  H = 20, 2 x 500 tanh

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of every gfx950 kernel in host objects: does a source change move any machine code?
 
-usage: tools/kernel_digest.py OBJ... [--against OBJ...]
+usage: tools/kernel_digest.py [--by-content] OBJ... [--against OBJ...]
 
 Each OBJ is a host object built by hipcc (build/*.o).  Its device code object is extracted with
 `llvm-objcopy --dump-section .hip_fatbin` and `clang-offload-bundler --unbundle`; every kernel (a FUNC
@@ -12,6 +12,7 @@ symbol NAME with a kernel descriptor NAME.kd) prints as
 (the entry offset is the distance from the descriptor to the code, which moves with everything else in the
 unit).  With --against, the kernels of the first list are compared with those of the second as sets of
 (symbol, size, digest, descriptor), whatever object each sits in; exit status 1 if they differ in any way.
+--by-content pairs them by (size, digest, descriptor) alone, for a change that renames the symbols.
 Bytes only: no instruction is inspected.
 """
 import hashlib
@@ -98,6 +99,8 @@ def main(argv):
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0 if argv else 2
+    by_content = "--by-content" in argv
+    argv = [o for o in argv if o != "--by-content"]
     mine, theirs = (argv[:argv.index("--against")], argv[argv.index("--against") + 1:]) if "--against" in argv \
         else (argv, None)
     rows = digest(mine)
@@ -111,6 +114,25 @@ def main(argv):
     for obj in theirs:
         print(f"# against {obj}: {sum(r[0] == obj for r in ref)} kernels")
     a, b = sorted(r[1:] for r in rows), sorted(r[1:] for r in ref)
+    if by_content:                                      # the symbols were renamed: pair the kernels by what they hold
+        ca, cb = sorted(r[1:] for r in a), sorted(r[1:] for r in b)
+        left = list(cb)
+        for r in ca:
+            if r in left:
+                left.remove(r)
+        same = len(cb) - len(left)
+        print(f"# by content: {same} of {len(ca)} kernels have a kernel of the same size, code digest and descriptor "
+              f"among the {len(cb)} of the second list")
+        if same == len(ca) == len(cb):
+            return 0
+        for name, *r in a:
+            if tuple(r) not in cb:
+                print(f"# no match in the second list: {name}")
+        for name, *r in b:
+            if tuple(r) not in ca:
+                print(f"# no match in the first list: {name}")
+        print("# DIFFERENT")
+        return 1
     if a == b:
         print(f"# identical: {len(a)} kernels, every symbol, size, code digest and descriptor")
         return 0
