@@ -170,6 +170,18 @@ class Sampling(ctypes.Structure):
     ]
 
 
+class MppiExt(ctypes.Structure):
+    """bcmpc_mppi_ext (40 bytes): MPPI's control-cost weight and sigma update (bc_mpc_amd/mppi_update.py)."""
+    _fields_ = [
+        ("control_weight", ctypes.c_double),
+        ("adapt_sigma", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("sigma_alpha", ctypes.c_double),
+        ("min_std", ctypes.c_double),
+        ("max_std", ctypes.c_double),
+    ]
+
+
 class MppiStats(ctypes.Structure):
     """One MPPI update's statistics (bcmpc_mppi_stats); no valid candidate: 0, 0, NaN, 0."""
     _fields_ = [
@@ -332,6 +344,18 @@ SIGNATURES = [
     ("bcmpc_plan_keep_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
       ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_mppi_get_action_x", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt), ctypes.c_uint64,
+      _DP, _DP, ctypes.POINTER(Result), ctypes.POINTER(MppiStats)]),
+    ("bcmpc_mppi_get_actions_batch_x", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt),
+      ctypes.c_uint64, ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result), ctypes.POINTER(MppiStats), _DP]),
+    ("bcmpc_mppi_control_cost_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_mppi_sigma_update_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     ("bcmpc_ensemble_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_ensemble_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_ensemble_size", ctypes.c_int, [ctypes.c_void_p]),

@@ -170,7 +170,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
     for (void* p : {(void*)e->d_w, (void*)e->d_b, (void*)e->d_ln, (void*)e->d_consts, (void*)e->d_state,
                     (void*)e->d_actions, (void*)e->d_costs, (void*)e->d_result, (void*)e->d_pw, (void*)e->d_pb,
                     (void*)e->d_first, (void*)e->d_gpow, (void*)e->d_mu, (void*)e->d_sigma, (void*)e->d_elite,
-                    (void*)e->d_count, (void*)e->d_mppi, (void*)e->d_mppi_stats, (void*)e->d_amin_c, (void*)e->d_amin_i,
+                    (void*)e->d_count, (void*)e->d_mppi, (void*)e->d_mppi_stats, (void*)e->d_mppi_scores, (void*)e->d_amin_c, (void*)e->d_amin_i,
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,

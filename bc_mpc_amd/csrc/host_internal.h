@@ -136,6 +136,8 @@ struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, 
     // [256] counts, [H * A + 2][partials] -- grown on demand, and the synchronous call's statistics
     double* d_mppi = nullptr; size_t mppi_cap = 0;
     bcmpc_mppi_stats* d_mppi_stats = nullptr;
+    // ... and the control-cost term's augmented scores [num_paths] (bcmpc_mppi_get_action_x, mppi_ext.hip)
+    double* d_mppi_scores = nullptr; size_t mppi_scores_cap = 0;
     double explore = 0.0;
     uint64_t pol_version = 0;
     bool has_policy = false;

@@ -331,4 +331,37 @@ struct PlanKeepArgs {                        // keep[b][e] = the stored sequence
 hipError_t launch_plan_sample_corr(const PlanSampleCorrArgs& a, hipStream_t st);
 hipError_t launch_plan_keep(const PlanKeepArgs& a, hipStream_t st);
 
+// ---- MPPI's control-cost term and weighted sigma update (mppi_ext.hip; bc_mpc_amd/mppi_update.py) ----
+// Both read the iteration's stored actions [H][n_envs * K][A]; environment b: costs / scores / out + b K,
+// mu / sigma / mu_new + b H A.
+constexpr size_t kMppiControlMaxLds = 65536;     // the gain table and mu in LDS: H * A <= 4096
+struct MppiControlArgs {                         // out[c] = costs[c] +- weight * sum_h sum_j g[h][j] (a[h][c][j] - mu[h][j])
+    const double* costs;                         // [n_envs * K] raw costs
+    const double* actions;                       // [H][Ktot][A]
+    const double* mu;                            // [n_envs][H][A] the plan the iteration sampled from
+    const double* sigma;
+    double* out;                                 // [n_envs * K] the augmented scores
+    int64_t K, Ktot, bpe;                        // bpe: workgroups per environment, ceil(K / 256)
+    int32_t n_envs, H, A;
+    int32_t maximize;                            // learned reward: costs - weight * q
+    double weight;
+};
+struct MppiSigmaArgs {                           // sigma' = clamp(alpha sigma + (1 - alpha) sqrt(sum w (a - mu')^2 / sum w))
+    const double* scores;                        // [n_envs * K] the vector the update ran on
+    const double* actions;                       // [H][Ktot][A]
+    const double* mu_new;                        // [n_envs][H][A] the updated plan
+    double* sigma;                               // [n_envs][H][A], in / out
+    double* pmin;                                // [n_envs][kMppiMinParts], as MppiArgs
+    int64_t* pcnt;
+    double* part;                                // [n_envs][H * A + 1][nparts]: V[h][j], then W
+    int64_t K, Ktot, nparts;                     // nparts = mppi_parts(K)
+    int32_t n_envs, H, A, cpl, nmin;             // cpl = mppi_cpl(K), nmin = mppi_min_blocks(K)
+    int32_t maximize;
+    double lambda, alpha, min_std, max_std;
+};
+size_t mppi_control_lds(int32_t HA);             // bytes of dynamic LDS the control-cost kernel takes
+size_t mppi_sigma_scratch(int64_t K, int32_t n_envs, int32_t HA);   // doubles: [B][256] [B][256] [B][HA + 1][parts]
+hipError_t launch_mppi_control_cost(const MppiControlArgs& a, hipStream_t st);
+hipError_t launch_mppi_sigma_update(const MppiSigmaArgs& a, hipStream_t st);   // min, partial, final
+
 }  // namespace bcmpc

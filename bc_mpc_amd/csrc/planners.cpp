@@ -112,6 +112,26 @@ static int sampling_check(const bcmpc_sampling* s, bool mppi) {
     return BCMPC_OK;
 }
 
+// MPPI's control-cost term and sigma update (bcmpc_mppi_ext; nullptr or both switched off: the plain update)
+static bool mppi_ext_default(const bcmpc_mppi_ext* x) { return !x || (x->control_weight == 0.0 && x->adapt_sigma == 0); }
+static int control_weight_check(double w) {
+    if (!(std::isfinite(w) && w >= 0.0)) return fail(BCMPC_ERR_ARG, "control_weight must be finite and >= 0");
+    return BCMPC_OK;
+}
+static int sigma_step_check(double alpha, double min_std, double max_std) {
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(BCMPC_ERR_ARG, "sigma_alpha must be in [0, 1]");
+    if (!(std::isfinite(min_std) && min_std >= 0.0)) return fail(BCMPC_ERR_ARG, "min_std must be finite and >= 0");
+    if (!(max_std >= min_std)) return fail(BCMPC_ERR_ARG, "max_std must be >= min_std");
+    return BCMPC_OK;
+}
+static int mppi_ext_check(const bcmpc_mppi_ext* x) {
+    if (!x) return BCMPC_OK;
+    if (const int rc = control_weight_check(x->control_weight)) return rc;
+    if (x->adapt_sigma != 0 && x->adapt_sigma != 1) return fail(BCMPC_ERR_ARG, "adapt_sigma must be 0 or 1");
+    if (x->reserved != 0) return fail(BCMPC_ERR_ARG, "bcmpc_mppi_ext.reserved must be zero");
+    return sigma_step_check(x->sigma_alpha, x->min_std, x->max_std);
+}
+
 // a synchronous planner call's input plans, kept on a team engine for the rerun after a give-up: n doubles of
 // mu, and of sigma where the call writes it back (CEM)
 struct PlanInputs {
@@ -282,6 +302,79 @@ static int mppi_update_batch_impl(bcmpc_engine* e, const double* d_costs, int32_
     return BCMPC_OK;
 }
 
+// c~ = costs +- weight q into d_scores (mppi_ext.hip): the plans are the ones the actions were sampled from
+static int control_cost_impl(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs, int64_t K,
+                             const double* d_mu, const double* d_sigma, double weight, double* d_scores,
+                             hipStream_t st) {
+    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+    if (mppi_control_lds(ha) > kMppiControlMaxLds)
+        return fail(BCMPC_ERR_UNSUPPORTED, "horizon * action_dim is too large for the control-cost kernel's table");
+    if ((K + 255) / 256 * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one launch");
+    MppiControlArgs a{};
+    a.costs = d_costs; a.actions = d_actions; a.mu = d_mu; a.sigma = d_sigma; a.out = d_scores;
+    a.K = K; a.Ktot = K * n_envs; a.bpe = (K + 255) / 256;
+    a.n_envs = n_envs; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    a.weight = weight;
+    HIP_TRY(launch_mppi_control_cost(a, st));
+    return BCMPC_OK;
+}
+
+// sigma' from the weights of d_scores about d_mu_new (mppi_ext.hip); the scratch is the update's, grown like it
+static int sigma_update_impl(bcmpc_engine* e, const double* d_scores, const double* d_actions, int32_t n_envs, int64_t K,
+                             double lambda, const double* d_mu_new, double* d_sigma, double alpha, double min_std,
+                             double max_std, hipStream_t st) {
+    const int64_t parts = mppi_parts(K);
+    if (parts * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one update");
+    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+    const size_t need = mppi_sigma_scratch(K, n_envs, ha);
+    if (need > e->mppi_cap) {
+        if (e->d_mppi) (void)hipFree(e->d_mppi);
+        e->d_mppi = nullptr;
+        e->mppi_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_mppi, need * sizeof(double)));
+        e->mppi_cap = need;
+    }
+    MppiSigmaArgs a{};
+    a.scores = d_scores; a.actions = d_actions; a.mu_new = d_mu_new; a.sigma = d_sigma;
+    a.pmin = e->d_mppi;
+    a.pcnt = reinterpret_cast<int64_t*>(e->d_mppi + (size_t)n_envs * kMppiMinParts);
+    a.part = e->d_mppi + 2 * (size_t)n_envs * kMppiMinParts;
+    a.K = K; a.Ktot = K * n_envs; a.nparts = parts;
+    a.n_envs = n_envs; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.cpl = mppi_cpl(K); a.nmin = mppi_min_blocks(K);
+    a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
+    a.lambda = lambda; a.alpha = alpha; a.min_std = min_std; a.max_std = max_std;
+    HIP_TRY(launch_mppi_sigma_update(a, st));
+    return BCMPC_OK;
+}
+
+int bcmpc_mppi_control_cost_async(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs,
+                                  int64_t K, const double* d_mu, const double* d_sigma, double weight,
+                                  double* d_scores, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_actions || !d_mu || !d_sigma || !d_scores) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = control_weight_check(weight)) return rc;
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return control_cost_impl(e, d_costs, d_actions, n_envs, K, d_mu, d_sigma, weight, d_scores, (hipStream_t)stream);
+}
+
+int bcmpc_mppi_sigma_update_async(bcmpc_engine* e, const double* d_scores, const double* d_actions, int32_t n_envs,
+                                  int64_t K, double lambda, const double* d_mu_new, double* d_sigma, double alpha,
+                                  double min_std, double max_std, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_scores || !d_actions || !d_mu_new || !d_sigma) return fail(BCMPC_ERR_ARG, "null argument");
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (const int rc = sigma_step_check(alpha, min_std, max_std)) return rc;
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return sigma_update_impl(e, d_scores, d_actions, n_envs, K, lambda, d_mu_new, d_sigma, alpha, min_std, max_std,
+                             (hipStream_t)stream);
+}
+
 int bcmpc_plan_sample_async(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
                             uint64_t seed, int32_t iteration, int64_t cand_offset, double* d_actions, void* stream) {
     // (arguments first: a bad call is answered before any HIP call)
@@ -420,10 +513,13 @@ static int keep_buffers(bcmpc_engine* e, int32_t n_envs, int32_t n_elite) {
 // plans down, one stream synchronisation.  cem != nullptr: CEM, else MPPI (mp).  A non-default smp (checked by
 // the caller): plan_sample_corr instead of plan_sample, and with keep_elites plan_keep behind every refit that
 // another iteration follows -- iteration it >= 1 then starts with iteration it - 1's elites.
+// A non-default ext (MPPI; checked by the caller): the control-cost launch in front of the update, whose augmented
+// scores replace the costs in it (the record stays on the raw costs), and with adapt_sigma the sigma launches
+// behind it; sigma_io is then written back like CEM's.
 static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* cem,
                             const bcmpc_mppi* mp, const bcmpc_sampling* smp, uint64_t seed, int64_t cand_offset,
                             double* mu, double* sigma_io, const double* sigma_in, bcmpc_result* out,
-                            bcmpc_mppi_stats* stats, double* costs_out) {
+                            bcmpc_mppi_stats* stats, double* costs_out, const bcmpc_mppi_ext* ext = nullptr) {
     const bcmpc_config& c = e->cfg;
     const int32_t iterations = cem ? cem->iterations : mp->iterations;
     const int64_t K = c.num_paths / n_envs;
@@ -437,8 +533,17 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     if (carry)
         if (const int rc = keep_buffers(e, n_envs, cem->n_elite)) return rc;
     if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
-    const double* sigma = cem ? sigma_io : sigma_in;
-    const PlanInputs inputs(e->kernel == BCMPC_KERNEL_TEAM, mu, cem ? sigma_io : nullptr, nplan);
+    const bool control = ext && !cem && ext->control_weight != 0.0, adapt = ext && !cem && ext->adapt_sigma != 0;
+    if (control && (size_t)c.num_paths > e->mppi_scores_cap) {
+        if (e->d_mppi_scores) (void)hipFree(e->d_mppi_scores);
+        e->d_mppi_scores = nullptr;
+        e->mppi_scores_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_mppi_scores, (size_t)c.num_paths * sizeof(double)));
+        e->mppi_scores_cap = (size_t)c.num_paths;
+    }
+    const bool sigma_out = cem || adapt;               // the call writes sigma back
+    const double* sigma = sigma_out ? sigma_io : sigma_in;
+    const PlanInputs inputs(e->kernel == BCMPC_KERNEL_TEAM, mu, sigma_out ? sigma_io : nullptr, nplan);
     hipStream_t st = e->stream;
     HIP_TRY(hipMemcpyAsync(e->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->d_bmu, mu, nplan * sizeof(double), hipMemcpyHostToDevice, st));
@@ -468,11 +573,19 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
         int rc = plan_argmin_impl(e, e->d_costs, e->d_actions, n_envs, K, it, it > 0, e->d_bresults, st);
         if (rc == BCMPC_OK && cem)
             rc = select_batch_impl(e, e->d_costs, n_envs, K, cand_offset, cem->n_elite, e->d_belite, e->d_bcount, st);
+        // (MPPI with the control-cost term: the update and the sigma launches read the augmented scores)
+        const double* scores = control ? e->d_mppi_scores : e->d_costs;
+        if (rc == BCMPC_OK && control)
+            rc = control_cost_impl(e, e->d_costs, e->d_actions, n_envs, K, e->d_bmu, e->d_bsigma, ext->control_weight,
+                                   e->d_mppi_scores, st);
         if (rc == BCMPC_OK)
             rc = cem ? refit_batch_impl(e, e->d_belite, e->d_bcount, n_envs, cem->n_elite, seed, it, cem->alpha, e->d_bmu,
                                         e->d_bsigma, e->d_actions, K, cand_offset, st)
-                     : mppi_update_batch_impl(e, e->d_costs, n_envs, K, cand_offset, seed, it, mp->lambda, e->d_bmu,
+                     : mppi_update_batch_impl(e, scores, n_envs, K, cand_offset, seed, it, mp->lambda, e->d_bmu,
                                               e->d_bsigma, e->d_bstats, e->d_actions, st);
+        if (rc == BCMPC_OK && adapt)
+            rc = sigma_update_impl(e, scores, e->d_actions, n_envs, K, mp->lambda, e->d_bmu, e->d_bsigma,
+                                   ext->sigma_alpha, ext->min_std, ext->max_std, st);
         // the elites' sequences out of the array, before the next iteration's sampling overwrites it
         if (rc == BCMPC_OK && carry && it + 1 < iterations)
             rc = plan_keep_impl(e, e->d_belite, e->d_bcount, e->d_actions, n_envs, K, cand_offset, cem->n_elite,
@@ -486,14 +599,14 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     e->timed = e->timing;
     HIP_TRY(hipMemcpyAsync(e->h_bresults, e->d_bresults, (size_t)n_envs * sizeof(bcmpc_result), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(mu, e->d_bmu, nplan * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (cem) HIP_TRY(hipMemcpyAsync(sigma_io, e->d_bsigma, nplan * sizeof(double), hipMemcpyDeviceToHost, st));
-    else HIP_TRY(hipMemcpyAsync(stats, e->d_bstats, (size_t)n_envs * sizeof(bcmpc_mppi_stats), hipMemcpyDeviceToHost, st));
+    if (sigma_out) HIP_TRY(hipMemcpyAsync(sigma_io, e->d_bsigma, nplan * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!cem) HIP_TRY(hipMemcpyAsync(stats, e->d_bstats, (size_t)n_envs * sizeof(bcmpc_mppi_stats), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (team_failed(e)) {                              // the whole call again, from the original plans
         if (const int fr = team_fallback(e)) return fr;
         inputs.restore(mu, sigma_io);
         return plan_get_actions(e->fb, states, n_envs, cem, mp, smp, seed, cand_offset, mu, sigma_io, sigma_in, out,
-                                stats, costs_out);
+                                stats, costs_out, ext);
     }
     std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
     return BCMPC_OK;
@@ -538,6 +651,25 @@ int bcmpc_mppi_get_actions_batch(bcmpc_engine* e, const double* states, int32_t 
                                  bcmpc_mppi_stats* stats, double* costs_out) {
     return bcmpc_mppi_get_actions_batch_s(e, states, n_envs, p, nullptr, seed, cand_offset, mu, sigma, out, stats,
                                           costs_out);
+}
+
+int bcmpc_mppi_get_actions_batch_x(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext, uint64_t seed,
+                                   int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                   bcmpc_mppi_stats* stats, double* costs_out) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (const int rc = mppi_ext_check(ext)) return rc;
+    if (mppi_ext_default(ext))
+        return bcmpc_mppi_get_actions_batch_s(e, states, n_envs, p, sampling, seed, cand_offset, mu, sigma, out, stats,
+                                              costs_out);
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    if (const int rc = k_global_check(p->k_global, "batched MPPI", e->cfg.num_paths / n_envs, "num_paths / n_envs")) return rc;
+    return plan_get_actions(e, states, n_envs, nullptr, p, sampling, seed, cand_offset, mu, sigma, sigma, out, stats,
+                            costs_out, ext);
 }
 
 // ---- model ensembles: E member engines, one launch chain on member 0's stream -----------
@@ -904,6 +1036,21 @@ int bcmpc_mppi_get_action_s(bcmpc_engine* e, const double* state, const bcmpc_mp
     if (const int rc = k_global_check(p->k_global, "single-device MPPI", e->cfg.num_paths)) return rc;
     if (const int rc = batch_check(e, 1)) return rc;
     return plan_get_actions(e, state, 1, nullptr, p, sampling, seed, 0, mu, nullptr, sigma, out, stats, nullptr);
+}
+
+// ... and with the control-cost term / the sigma update: off, the call above; on, the batched chain as for rho
+int bcmpc_mppi_get_action_x(bcmpc_engine* e, const double* state, const bcmpc_mppi* p, const bcmpc_sampling* sampling,
+                            const bcmpc_mppi_ext* ext, uint64_t seed, double* mu, double* sigma, bcmpc_result* out,
+                            bcmpc_mppi_stats* stats) {
+    if (const int rc = mppi_ext_check(ext)) return rc;
+    if (mppi_ext_default(ext)) return bcmpc_mppi_get_action_s(e, state, p, sampling, seed, mu, sigma, out, stats);
+    if (!e || !state || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "MPPI needs a fused objective");
+    if (const int rc = k_global_check(p->k_global, "single-device MPPI", e->cfg.num_paths)) return rc;
+    if (const int rc = batch_check(e, 1)) return rc;
+    return plan_get_actions(e, state, 1, nullptr, p, sampling, seed, 0, mu, sigma, sigma, out, stats, nullptr, ext);
 }
 
 int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, uint64_t seed,

@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from . import mppi_update as _mppi_update
 from . import sampling as _sampling
 
 _ACT = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
@@ -197,6 +198,7 @@ class _EngineCalls:
     ``_MPPI``).  The class provides ``_lib``, ``_h``, ``state_dim``, ``action_dim``, ``horizon``, ``num_paths``."""
     _CEM, _MPPI = "bcmpc_cem_get_action", "bcmpc_mppi_get_action"
     _CEM_S, _MPPI_S = "bcmpc_cem_get_action_s", "bcmpc_mppi_get_action_s"     # (None: no such entry)
+    _MPPI_X = "bcmpc_mppi_get_action_x"
 
     def _fresh(self) -> None:
         """The wrapper's host state for a handle nothing has been set on yet."""
@@ -233,15 +235,21 @@ class _EngineCalls:
         rho, keep = _sampling.check_rho(rho), _sampling.check_keep_elites(keep_elites)
         return _lib.Sampling(rho, int(keep), 0) if rho != 0.0 or keep else None
 
+    def _mppi_ext(self, control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature):
+        """The ``_lib.MppiExt`` of an MPPI call's control-cost weight and sigma update (mppi_update.py), or None
+        with both switched off: the call then goes to the entry point it has always gone to."""
+        weight, adapt, alpha, lo, hi = _mppi_update.check_options(control_cost, adapt_sigma, sigma_alpha, min_std,
+                                                                  max_std, temperature)
+        return _lib.MppiExt(weight, int(adapt), 0, alpha, lo, hi) if weight != 0.0 or adapt else None
+
     def _step_result(self, res, costs=None) -> StepResult:
         return StepResult(int(res.best_index), float(res.best_cost),
                           np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
 
     # ------------------------------------------------------------------ CEM / MPPI, one plan
-    def _s_entry(self, name: Optional[str], what: str):
+    def _s_entry(self, name: Optional[str], what: str, options: str = "correlated noise and elite carry-over"):
         if name is None:
-            raise NotImplementedError(f"{type(self).__name__}.{what}: correlated noise and elite carry-over are "
-                                      "not built for ensembles")
+            raise NotImplementedError(f"{type(self).__name__}.{what}: {options} are not built for ensembles")
         return getattr(self._lib, name)
 
     def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
@@ -269,20 +277,34 @@ class _EngineCalls:
         return self._step_result(res), m, s
 
     def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
-                        seed: int, rho: float = 0.0) -> Tuple[StepResult, np.ndarray, "_lib.MppiStats"]:
+                        seed: int, rho: float = 0.0, control_cost=0.0, adapt_sigma: bool = False,
+                        sigma_alpha: float = 0.0, min_std: float = 0.0, max_std: Optional[float] = None):
         """``iterations`` rounds of CEM-style rollout + MPPI update on this device (bcmpc_mppi_get_action; an
         ensemble: bcmpc_ensemble_mppi_get_action, the softmin weights from the combined value; DESIGN.md "MPPI").
         ``mu``/``sigma`` are ``[H, A]``; returns (the best single candidate over all rounds, best_index =
         iteration*K + candidate; the updated plan mu', whose row 0 is the action to apply; the last round's
         statistics).  sigma is not modified.  ``rho``: temporally correlated noise (sampling.py;
-        bcmpc_mppi_get_action_s)."""
+        bcmpc_mppi_get_action_s).
+
+        ``control_cost`` (a weight >= 0, or True for the temperature) adds MPPI's control-cost term to the score
+        the weights see -- the record stays on the raw costs, ``stats.min_cost`` is the minimum augmented score --
+        and ``adapt_sigma`` refits sigma after every round as ``clamp(sigma_alpha * sigma + (1 - sigma_alpha) *
+        weighted std, min_std, max_std)`` (mppi_update.py; bcmpc_mppi_get_action_x).  With
+        ``adapt_sigma`` a fourth element, sigma' ``[H, A]``, is returned."""
         smp = self._sampling(rho)
+        ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
         st = self._state(state)
         shape = (self.horizon, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res, stats = _lib.Result(), _lib.MppiStats()
+        if ext is not None:
+            s = np.array(s, dtype=np.float64, copy=True)           # (in / out: the caller's array is not written)
+            _lib.check(self._s_entry(self._MPPI_X, "mppi_get_action", "MPPI's control cost and sigma update")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None, ctypes.byref(ext),
+                ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res), ctypes.byref(stats)))
+            return (self._step_result(res), m, stats, s) if ext.adapt_sigma else (self._step_result(res), m, stats)
         if smp is None:
             _lib.check(getattr(self._lib, self._MPPI)(self._h, _dp(st), ctypes.byref(p),
                                                       ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
@@ -985,19 +1007,31 @@ class RolloutEngine(_EngineCalls):
         return self._batch_result(res, B, costs, int(iterations)), m, s
 
     def mppi_get_actions(self, states, mu, sigma, iterations: int, temperature: float, seed: int,
-                         cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0
-                         ) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+                         cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0, control_cost=0.0,
+                         adapt_sigma: bool = False, sigma_alpha: float = 0.0, min_std: float = 0.0,
+                         max_std: Optional[float] = None):
         """Batched MPPI (bcmpc_mppi_get_actions_batch): as cem_get_actions, with the softmin update of
         mppi_get_action per environment.  Returns (records, mu' ``[B, H, A]`` whose rows ``[b, 0]`` are the
         actions to apply, the last round's statistics as a ``[B]`` array of MPPI_STATS).  sigma is not
-        modified.  ``rho``: temporally correlated noise (sampling.py; bcmpc_mppi_get_actions_batch_s)."""
+        modified.  ``rho``: temporally correlated noise (sampling.py; bcmpc_mppi_get_actions_batch_s).
+        ``control_cost`` / ``adapt_sigma`` / ``sigma_alpha`` / ``min_std`` / ``max_std``: as mppi_get_action
+        (bcmpc_mppi_get_actions_batch_x); the returned costs stay the raw ones, and with ``adapt_sigma`` a fourth
+        element, sigma' ``[B, H, A]``, is returned."""
         smp = self._sampling(rho)
-        st, B, m, s = self._plan_batch_args(states, mu, sigma, False)
+        ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, ext is not None)
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res = (_lib.Result * B)()
         stats = np.zeros(B, dtype=MPPI_STATS)
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
         d_stats, d_costs = stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None
+        if ext is not None:
+            _lib.check(self._lib.bcmpc_mppi_get_actions_batch_x(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(ext), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s),
+                res, d_stats, d_costs))
+            out = self._batch_result(res, B, costs, int(iterations))
+            return (out, m, stats, s) if ext.adapt_sigma else (out, m, stats)
         if smp is None:
             _lib.check(self._lib.bcmpc_mppi_get_actions_batch(
                 self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
@@ -1084,6 +1118,31 @@ class RolloutEngine(_EngineCalls):
         _lib.check(self._lib.bcmpc_mppi_update_batch_async(
             self._h, vp(d_costs), int(n_envs), int(K), int(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)),
             int(iteration), float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), vp(d_actions),
+            ctypes.c_void_p(stream)))
+
+    def mppi_control_cost_async(self, d_costs: int, d_actions: int, n_envs: int, K: int, d_mu: int, d_sigma: int,
+                                weight: float, d_scores: int, stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_control_cost_async: ``d_scores`` ``[n_envs*K]`` = the costs ``d_costs`` plus (a reward
+        engine: minus) ``weight`` times the control cost of the stored actions ``d_actions`` ``[H, n_envs*K, A]``
+        under the plans ``d_mu`` / ``d_sigma`` ``[n_envs, H, A]`` they were sampled from
+        (mppi_update.control_cost / augmented)."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_control_cost_async(
+            self._h, vp(d_costs), vp(d_actions), int(n_envs), int(K), vp(d_mu), vp(d_sigma), float(weight),
+            vp(d_scores), ctypes.c_void_p(stream)))
+
+    def mppi_sigma_update_async(self, d_scores: int, d_actions: int, n_envs: int, K: int, temperature: float,
+                                d_mu_new: int, d_sigma: int, alpha: float = 0.0, min_std: float = 0.0,
+                                max_std: Optional[float] = None, stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_sigma_update_async: ``d_sigma`` ``[n_envs, H, A]`` in place from the softmin weights of
+        ``d_scores`` (the vector the update ran on) about the UPDATED plans ``d_mu_new``
+        (mppi_update.weighted_sigma / sigma_step).  It relies on no scratch of an earlier call."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_sigma_update_async(
+            self._h, vp(d_scores), vp(d_actions), int(n_envs), int(K), float(temperature), vp(d_mu_new), vp(d_sigma),
+            float(alpha), float(min_std), float("inf") if max_std is None else float(max_std),
             ctypes.c_void_p(stream)))
 
     def set_comm(self, comm) -> None:

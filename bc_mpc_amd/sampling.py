@@ -14,7 +14,7 @@ nothing itself: the independent normals ``z`` are the planners' Irwin-Hall draws
 * ``refit_from_actions``: the CEM refit's statistics on given elite actions, in the device's summation order.
 
 Not built: power-law (FFT) noise, elites carried (shifted) from one control step to the next, carrying a
-fraction of the elites, ensembles and more than one rank, MPPI's control-cost term.
+fraction of the elites, ensembles and more than one rank.  (MPPI's control-cost term: mppi_update.py.)
 """
 from __future__ import annotations
 

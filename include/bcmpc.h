@@ -745,6 +745,64 @@ int bcmpc_plan_keep_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const i
                           double* d_keep, int32_t* d_keep_count, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MPPI's control-cost term and a weighted sigma update (additive to ABI 5; callers detect them by the symbol
+ * bcmpc_mppi_get_action_x; semantics in DESIGN.md 9l, defined by bc_mpc_amd/mppi_update.py).  One round with the
+ * options on, (mu, sigma) the plan it samples from:
+ *   record   the argmin runs over the RAW costs: best_cost, best_index and costs_out never hold the control cost
+ *   scores   c~[k] = cost[k] + control_weight * q[k] (BCMPC_COST_REWARD: cost[k] - control_weight * q[k]) with
+ *            q[k] = sum_h sum_j g[h][j] * (a[h][k][j] - mu[h][j]), g = mu / (sigma * sigma), 0 where sigma == 0;
+ *            a: the clipped sampled actions.  From 0.0, h ascending and j inside it, every operation an
+ *            individually rounded f64 one.  Under correlated noise this is the diagonal (marginal-variance)
+ *            form of Sigma^-1.  control_weight == 0: no launch, the scores are the costs
+ *   update   mu', stats == bcmpc_mppi_update_batch_async on c~, bit for bit -- stats.min_cost is therefore the
+ *            minimum AUGMENTED score
+ *   sigma    (adapt_sigma) sigma' = min(max(sigma_alpha * sigma + (1 - sigma_alpha) * s, min_std), max_std),
+ *            s[h][j] = sqrt(sum_k w[k] (a[h][k][j] - mu'[h][j])^2 / sum_k w[k]) with the update's weights w; no
+ *            valid candidate: sigma unchanged, as mu.  The next round samples from (mu', sigma').
+ * A NULL ext or one with control_weight == 0 and adapt_sigma == 0 forwards to the _s entry point: today's call,
+ * bit for bit.  Anything else runs the batched chain (n_envs = 1, cand_offset = 0 for the single call) with the
+ * control-cost launch before every update and the sigma launches behind it.
+ *   sigma : host [n_envs][H][A] (single call: [H][A]); read, and written back only when adapt_sigma is set
+ * BCMPC_ERR_ARG (before any HIP call): control_weight negative or not finite, adapt_sigma not 0 / 1, reserved
+ * not zero, sigma_alpha outside [0, 1], min_std negative or not finite, max_std < min_std (or NaN), and what the
+ * _s calls refuse.  BCMPC_ERR_UNSUPPORTED: a communicator attached, a fused policy, horizon * action_dim > 4096
+ * (the control-cost kernel's table).  Ensembles have no _x entry. */
+typedef struct bcmpc_mppi_ext {
+    double  control_weight;  /* >= 0, finite; 0: off */
+    int32_t adapt_sigma;     /* 0 | 1 */
+    int32_t reserved;        /* must be zero */
+    double  sigma_alpha;     /* in [0, 1] */
+    double  min_std;         /* >= 0 */
+    double  max_std;         /* >= min_std, +inf allowed */
+} bcmpc_mppi_ext;
+
+int bcmpc_mppi_get_action_x(bcmpc_engine* eng, const double* state, const bcmpc_mppi* params,
+                            const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext, uint64_t seed, double* mu,
+                            double* sigma /* in/out */, bcmpc_result* out, bcmpc_mppi_stats* stats);
+int bcmpc_mppi_get_actions_batch_x(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_mppi* params,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext, uint64_t seed,
+                                   int64_t cand_offset, double* mu, double* sigma /* in/out */, bcmpc_result* out,
+                                   bcmpc_mppi_stats* stats, double* costs_out);
+
+/* Their building blocks (device pointers, stream-ordered, as bcmpc_plan_sample_async and its siblings; n_envs and K
+ * are explicit, the engine gives H, A and the objective's direction).  d_actions is the iteration's stored array
+ * [H][n_envs * K][A] and is required: there is no Philox form.
+ *   control_cost  d_scores[c] = c~ of column c from d_costs [n_envs * K] and the plans d_mu / d_sigma
+ *                 [n_envs][H][A] the actions were sampled from; d_scores may be d_costs itself (every thread
+ *                 reads and writes its own entry) and may overlap it in no other way
+ *   sigma_update  d_sigma [n_envs][H][A] in place from the weights of d_scores (the vector the update ran on)
+ *                 about d_mu_new, the UPDATED plans.  Self-contained: it recomputes v_min, the count and W as the
+ *                 update does and relies on no scratch of an earlier call; the engine's scratch serves one update
+ *                 or sigma update at a time.
+ * BCMPC_ERR_ARG: null pointers, n_envs < 1, K < 1, weight, lambda, sigma_alpha / min_std / max_std as above. */
+int bcmpc_mppi_control_cost_async(bcmpc_engine* eng, const double* d_costs, const double* d_actions, int32_t n_envs,
+                                  int64_t K, const double* d_mu, const double* d_sigma, double weight,
+                                  double* d_scores, void* stream);
+int bcmpc_mppi_sigma_update_async(bcmpc_engine* eng, const double* d_scores, const double* d_actions, int32_t n_envs,
+                                  int64_t K, double lambda, const double* d_mu_new, double* d_sigma, double alpha,
+                                  double min_std, double max_std, void* stream);
+
+/* ------------------------------------------------------------------------
  * Model ensembles (additive to ABI 5; callers detect them by the symbol bcmpc_ensemble_create; not in
  * the reference, semantics in DESIGN.md 9g).  An ensemble holds E dynamics nets of one architecture and
  * one configuration -- E member engines of the same config, hence the same kernel layout.  Candidate k
