@@ -182,6 +182,20 @@ class MppiExt(ctypes.Structure):
     ]
 
 
+class Proposals(ctypes.Structure):
+    """bcmpc_proposals (40 bytes): given action sequences in every iteration's population (bc_mpc_amd/proposals.py);
+    ``sequences`` is a host pointer (``device`` 0, canonical ``[n_envs][P][H][A]``) or a device pointer (``device``
+    1, read through the three element strides)."""
+    _fields_ = [
+        ("sequences", ctypes.c_void_p),
+        ("count", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("env_stride", ctypes.c_int64),
+        ("seq_stride", ctypes.c_int64),
+        ("step_stride", ctypes.c_int64),
+    ]
+
+
 class MppiStats(ctypes.Structure):
     """One MPPI update's statistics (bcmpc_mppi_stats); no valid candidate: 0, 0, NaN, 0."""
     _fields_ = [
@@ -356,6 +370,27 @@ SIGNATURES = [
     ("bcmpc_mppi_sigma_update_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    ("bcmpc_cem_get_action_p", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.POINTER(Proposals), ctypes.c_uint64,
+      _DP, _DP, ctypes.POINTER(Result)]),
+    ("bcmpc_mppi_get_action_p", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt),
+      ctypes.POINTER(Proposals), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result), ctypes.POINTER(MppiStats)]),
+    ("bcmpc_cem_get_actions_batch_p", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.POINTER(Proposals),
+      ctypes.c_uint64, ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result), _DP]),
+    ("bcmpc_mppi_get_actions_batch_p", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt),
+      ctypes.POINTER(Proposals), ctypes.c_uint64, ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result),
+      ctypes.POINTER(MppiStats), _DP]),
+    ("bcmpc_plan_sample_prop_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+      ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("bcmpc_rollout_policy_batch_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("bcmpc_ensemble_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_ensemble_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_ensemble_size", ctypes.c_int, [ctypes.c_void_p]),

@@ -46,7 +46,10 @@ class CEMcontroller(Planner):
     hold the refitted distribution, ``last_cost`` / ``last_position`` the best sample (batched: ``[B, H, A]``
     and ``[B]``).  ``noise_rho`` in ``[0, 1)``: AR(1) noise over the horizon instead of independent draws;
     ``keep_elites``: every iteration after the first starts with all elites of the one before (sampling.py,
-    DESIGN.md 9j; both are read on every call, one rank and one dynamics model only)."""
+    DESIGN.md 9j; both are read on every call, one rank and one dynamics model only).  ``proposals=`` on a call
+    and ``policy_prior`` / ``policy_paths`` / ``policy_stochastic`` / ``policy_explore``: given action sequences, and
+    a policy net's closed-loop rollouts, in the last candidates of every iteration (proposals.py; one
+    rank and one dynamics model only); ``last_proposal_costs`` / ``last_best_from_proposal`` report on them."""
     _KIND = "CEM"
 
     def __init__(self,
@@ -69,11 +72,16 @@ class CEMcontroller(Planner):
                  terminal_value=None,
                  terminal_weight: float = -1.0,
                  noise_rho: float = 0.0,
-                 keep_elites: bool = False):
+                 keep_elites: bool = False,
+                 policy_prior=None,
+                 policy_paths: int = 0,
+                 policy_stochastic: bool = True,
+                 policy_explore: float = 0.0):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0xCE5EED if seed is None else seed, device, process_group,
                          terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho,
-                         keep_elites=keep_elites)
+                         keep_elites=keep_elites, policy_prior=policy_prior, policy_paths=policy_paths,
+                         policy_stochastic=policy_stochastic, policy_explore=policy_explore)
         self.elite_frac = float(elite_frac)
         self._n_elite = n_elite
         self.alpha = float(alpha)
@@ -107,6 +115,21 @@ class CEMcontroller(Planner):
         self.last_mu, self.last_sigma = mu, sd
         self.last_cost, self.last_position = cost, pos
         return first
+
+    def _call_proposals(self, eng, states, mu0, sd0, seed, src):
+        return eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, eng.num_paths // states.shape[0]),
+                                   self.alpha, seed, return_costs=True, proposals=src, **self._sampling_args())
+
+    def _publish_proposals(self, eng, out, K, single: bool):
+        res, mu, sd = out
+        if single:
+            self._note_planner_value(eng, int(res.best_index[0]), K)
+            return self._publish(float(res.best_cost[0]), int(res.best_index[0]), res.first_action[0].copy(), mu[0], sd[0])
+        self._note_planner_value(eng, res.best_index, K)
+        self._store_plans(mu)
+        self.last_mu, self.last_sigma = mu, sd
+        self.last_cost, self.last_position = res.best_cost, res.best_index
+        return res.first_action
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed,

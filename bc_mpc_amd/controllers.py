@@ -42,8 +42,10 @@ from typing import Optional
 
 import numpy as np
 
+from . import _lib
 from . import distributed as _dist
 from . import policy as _policy
+from . import proposals as _proposals
 from . import sampling as _sampling
 from . import value as _value
 from . import weights as _weights
@@ -328,10 +330,19 @@ class Planner(_TerminalValue, Controller):
     noise_rho = 0.0
     keep_elites = False
 
+    # proposals (proposals.py): a policy net rolled through the model gives every call's last candidates
+    policy_prior = None
+    policy_paths = 0
+    policy_stochastic = True
+    policy_explore = 0.0
+    last_proposal_costs = None      # [P] / [B, P]: the final iteration's costs of the proposal columns
+    last_best_from_proposal = None  # bool / [B] bool: the best sample's column is a proposal column
+
     def __init__(self, env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                  warm_start, seed, device, process_group, terminal_value=None, terminal_weight=-1.0, noise_rho=0.0,
-                 keep_elites=False):
+                 keep_elites=False, policy_prior=None, policy_paths=0, policy_stochastic=True, policy_explore=0.0):
         self._init_terminal_value(terminal_value, terminal_weight)
+        self._init_policy_prior(policy_prior, policy_paths, policy_stochastic, policy_explore)
         self.noise_rho = _sampling.check_rho(noise_rho)
         self.keep_elites = _sampling.check_keep_elites(keep_elites)
         self.env = env
@@ -451,6 +462,121 @@ class Planner(_TerminalValue, Controller):
         if self._sampling_args():
             raise NotImplementedError(f"{self._KIND}controller: noise_rho / keep_elites are not built {where}")
 
+    # ------------------------------------------------------------------ proposals (proposals.py)
+    def _init_policy_prior(self, policy_prior, policy_paths, policy_stochastic, policy_explore) -> None:
+        paths, explore = int(policy_paths), float(policy_explore)
+        if policy_prior is None and paths != 0:
+            raise ValueError(f"policy_paths = {policy_paths!r} needs a policy_prior")
+        if policy_prior is not None and paths < 1:
+            raise ValueError(f"policy_prior needs policy_paths >= 1, got {policy_paths!r}")
+        if not (math.isfinite(explore) and 0.0 <= explore <= 1.0):
+            raise ValueError(f"policy_explore must be in [0, 1], got {policy_explore!r}")
+        if policy_prior is not None:
+            _policy.extract(policy_prior)               # a container that cannot be read fails here, not mid-episode
+        self.policy_prior, self.policy_paths = policy_prior, paths
+        self.policy_stochastic, self.policy_explore = bool(policy_stochastic), explore
+
+    def _user_proposals(self, proposals, A: int, n_envs):
+        """A call's ``proposals=`` as ``[P, H, A]`` / ``[B, P, H, A]`` f64 or None; ValueError before anything is drawn."""
+        if proposals is None:
+            return None
+        return _proposals.as_sequences(proposals, int(self.horizon), A, n_envs)
+
+    def _forget_proposal_report(self) -> None:
+        """``last_proposal_costs`` / ``last_best_from_proposal`` of an earlier call (a controller that never carried
+        proposals keeps the class's None and gains no attribute)."""
+        if "last_proposal_costs" in self.__dict__:
+            self.last_proposal_costs = self.last_best_from_proposal = None
+
+    def _refuse_proposals(self, user, where: str) -> None:
+        """Proposals run on one engine of one rank; raised before a seed is drawn."""
+        if user is not None or self.policy_prior is not None:
+            raise NotImplementedError(f"{self._KIND}controller: proposals= / policy_prior are not built {where}")
+
+    def _prior_engine(self, slot: str, spec, norm, version, S: int, A: int, n_envs: int, user, K: int, kernel=None):
+        """The checks of a call's proposals against its K candidates and, with a ``policy_prior``, the engine that
+        rolls the policy through the model: a second engine in a slot of its own with ``n_envs * policy_paths``
+        candidates, under the policy engines' limits (a prior outside them is refused here with the engine's
+        message).  Everything here happens before a seed is drawn.  Returns the engine or None."""
+        n_user = 0 if user is None else user.shape[-3]
+        prior = self.policy_prior is not None
+        if not n_user and not prior:
+            return None
+        carried = min(int(self.n_elite), K) if _sampling.check_keep_elites(self.keep_elites) else 0
+        _proposals.check_count(n_user + (int(self.policy_paths) if prior else 0), K, carried)
+        if not prior:
+            return None
+        if spec.model == "reward":
+            raise ValueError(f"{self._KIND}controller: policy_prior over a learned-reward dyn_model is not covered "
+                             "(proposals= is)")
+        pspec, pversion = _policy.extract(self.policy_prior)
+        extra = {} if kernel is None else dict(kernel=kernel[0], precision=kernel[1])
+        # (cost="cheetah": policy engines need a fused cost; its values are ignored)
+        eng = _cached_engine(self, "_engines", slot, S, A, spec.hidden, spec.n_layers, spec.activation,
+                             spec.layer_norm, int(self.horizon), n_envs * int(self.policy_paths), device=_device(self),
+                             cost="cheetah", model=spec.model, policy_hidden=pspec.hidden,
+                             policy_layers=pspec.n_layers,
+                             policy_mode="stochastic" if self.policy_stochastic else "explore", **extra)
+        eng.set_weights(spec, norm, version)
+        eng.set_policy(pspec, float(self.policy_explore), pversion)
+        return eng
+
+    def _prior_fallback(self, slot: str, spec, norm, version, S: int, A: int, n_envs: int, user, K: int):
+        """The prior on a kernel that needs no resident team (what a synchronous call's rerun runs on): the split slab
+        kernel, or the fp32 group kernel where the net is in split precision on the team kernel only."""
+        try:
+            return self._prior_engine(slot + "_fb", spec, norm, version, S, A, n_envs, user, K, ("split2", "split"))
+        except ValueError:
+            return self._prior_engine(slot + "_fb", spec, norm, version, S, A, n_envs, user, K, ("group4", "fp32"))
+
+    def _prior_rollout(self, peng, eng, states, user, pseed: int):
+        """The prior block: ``policy_paths`` closed-loop policy rollouts per state on ``peng``, on the planning
+        engine's stream, into a torch device buffer -- handed on as device proposals in the policy engines' output
+        layout.  A user's proposals come first, the policy's follow."""
+        import torch
+        from .engine import DeviceProposals
+        dev = torch.device("cuda", eng.device)
+        B, Pp, H, A = states.shape[0], int(self.policy_paths), int(self.horizon), peng.action_dim
+        f64 = dict(dtype=torch.float64, device=dev)
+        with torch.cuda.stream(torch.cuda.ExternalStream(eng.stream, device=dev)):
+            d_states = torch.from_numpy(np.array(states, copy=True)).to(dev)      # (a copy: states may be read-only)
+            d_out = torch.empty((H, B * Pp, A), **f64)
+            d_costs = torch.empty(B * Pp, **f64)
+            peng.rollout_policy_batch_async(d_states.data_ptr(), B, None, pseed, 0, d_costs.data_ptr(), None,
+                                            d_out.data_ptr(), eng.stream)
+            if user is None:
+                return DeviceProposals(d_out.data_ptr(), Pp, *_proposals.policy_strides(B, Pp, A),
+                                       keep=(d_states, d_out, d_costs))
+            Pu = user.shape[1]
+            d_all = torch.empty((H, B, Pu + Pp, A), **f64)
+            d_all[:, :, :Pu] = torch.from_numpy(np.array(user, copy=True)).to(dev).permute(2, 0, 1, 3)
+            d_all[:, :, Pu:] = d_out.view(H, B, Pp, A)
+        return DeviceProposals(d_all.data_ptr(), Pu + Pp, *_proposals.policy_strides(B, Pu + Pp, A),
+                               keep=(d_states, d_out, d_costs, d_all))
+
+    def _with_proposals(self, eng, states, mu0, sd0, seed, K, user, peng, prior_args):
+        """A call with proposals: the prior block (a second draw from the seed stream, made only with a prior), then
+        the batched engine call -- ``get_action`` is its ``B = 1`` form, which equals the single call bit for bit and
+        also returns the costs.  A team-kernel prior that gave up is never used: the call is answered again with
+        the prior on its fallback kernel.  Returns ``_call_proposals``' tuple."""
+        src = user
+        if peng is not None:
+            pseed = self._next_seed()
+            src = self._prior_rollout(peng, eng, states, user, pseed)
+        out = self._call_proposals(eng, states, mu0, sd0, seed, src)
+        if peng is not None:
+            try:
+                peng.check_status()
+            except _lib.BcmpcError:
+                fb = self._prior_fallback(*prior_args)
+                out = self._call_proposals(eng, states, mu0, sd0, seed, self._prior_rollout(fb, eng, states, user, pseed))
+                fb.check_status()
+        P = (0 if user is None else user.shape[1]) + (int(self.policy_paths) if peng is not None else 0)
+        res = out[0]
+        self.last_proposal_costs = res.costs[-1][:, K - P:].copy()
+        self.last_best_from_proposal = (np.asarray(res.best_index) % K) >= K - P
+        return out
+
     def _model(self, S: int, A: int):
         """(spec, normalisation, version, the TermCost scored on the device or None) of a supported pair of
         model and cost: the learned reward of a reward model, else the fused cheetah cost or a TermCost."""
@@ -488,18 +614,23 @@ class Planner(_TerminalValue, Controller):
         self._batch_engine = self._cached("batch", spec, S, A, k_total, terms)
         return self._batch_engine
 
-    def get_action(self, state, reference=None, previous_action=None):
+    def get_action(self, state, reference=None, previous_action=None, proposals=None):
         """``reference`` (``[R]`` or ``[H, R]``) and ``previous_action`` (``[A]``): the inputs of a ``TermCost``
-        with ``ref(c)`` values / ``rate`` terms (cost_functions.py), explicit on every call."""
+        with ``ref(c)`` values / ``rate`` terms (cost_functions.py), explicit on every call.  ``proposals``
+        (``[P, H, A]``): action sequences that sit, clipped to the box, in the last P candidates of every
+        iteration (proposals.py); with a ``policy_prior`` the policy's ``policy_paths`` rollouts follow them."""
         self._inputs = _cost_inputs(self, reference, previous_action, False)
         S, A, K = _shape(self)
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
+        user = self._user_proposals(proposals, A, None)
+        self._forget_proposal_report()
         if getattr(self.dyn_model, "is_ensemble", False):
             # an EnsembleDynamicsModel (ensemble.py): its engine has RolloutEngine's planner calls, scored on the
             # members' combined value; it refuses ranks, costs and members itself, before anything is drawn
             from . import ensemble as _ensemble
             self._refuse_sampling("over an EnsembleDynamicsModel")
+            self._refuse_proposals(user, "over an EnsembleDynamicsModel")
             state = np.asarray(state, dtype=np.float64).reshape(-1)
             eng = _ensemble._ctrl_engine(self, S, A, K, "single")
             mu0, sd0 = self.initial_distribution()
@@ -508,23 +639,34 @@ class Planner(_TerminalValue, Controller):
         if ws > 1:
             self._refuse_ranks(ws)
             self._refuse_sampling(f"for more than one rank (world size {ws})")
+            self._refuse_proposals(user, f"for more than one rank (world size {ws})")
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         spec, norm, version, terms = self._model(S, A)
+        prior_args = ("prior", spec, norm, version, S, A, 1, user, K)
+        peng = self._prior_engine(*prior_args)
         mu0, sd0 = self.initial_distribution()
         seed = self._next_seed()
         if ws > 1:
             return self._sharded(rank, ws, state, spec, norm, version, terms, mu0, sd0, seed, S, A, K)
         eng = self._engine_for(spec, S, A, K, *_opt(terms))
         eng.set_weights(spec, norm, version)
-        return self._solve(eng, state, mu0, sd0, seed, K)
+        if user is None and peng is None:
+            return self._solve(eng, state, mu0, sd0, seed, K)
+        out = self._with_proposals(eng, state[None], mu0[None], sd0[None], seed, K,
+                                   None if user is None else user[None], peng, prior_args)
+        self.last_proposal_costs = self.last_proposal_costs[0]
+        self.last_best_from_proposal = bool(self.last_best_from_proposal[0])
+        return self._publish_proposals(eng, out, K, True)
 
-    def get_actions(self, states, reference=None, previous_action=None):
+    def get_actions(self, states, reference=None, previous_action=None, proposals=None):
         """Batched control step: ``states`` is ``[B, S]``, one independent answer per row with
         ``num_simulated_paths`` candidates each, all environments in one launch chain.  Every environment
         keeps its own warm-start plan (see ``reset``); one seed is drawn per call.  Returns ``[B, A]``
         float64; ``last_mu`` is ``[B, H, A]`` and the other ``last_*`` hold one entry per environment.  One
         rank only.  ``reference`` (``[B, R]`` or ``[B, H, R]``) and ``previous_action`` (``[B, A]``): every
-        environment's inputs of a ``TermCost`` with ``ref(c)`` values / ``rate`` terms."""
+        environment's inputs of a ``TermCost`` with ``ref(c)`` values / ``rate`` terms.  ``proposals``
+        (``[B, P, H, A]``): every environment's own sequences, as in ``get_action``; a ``policy_prior`` is rolled
+        out from every environment's state (``B * policy_paths`` rollouts in one launch)."""
         if getattr(self.dyn_model, "is_ensemble", False):
             raise NotImplementedError(f"batched {self._KIND} over an EnsembleDynamicsModel is not built yet: "
                                       "use get_action")
@@ -534,13 +676,20 @@ class Planner(_TerminalValue, Controller):
         _batch_inputs_check(self, self._inputs, states.shape[0])
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
-        spec, norm, version, terms = self._model(S, A)
         B = states.shape[0]
+        user = self._user_proposals(proposals, A, B)
+        self._forget_proposal_report()
+        spec, norm, version, terms = self._model(S, A)
+        prior_args = ("prior_batch", spec, norm, version, S, A, B, user, K)
+        peng = self._prior_engine(*prior_args)
         mu0, sd0 = self.batch_initial_distribution(B)
         seed = self._next_seed()
         eng = self._batch_engine_for(spec, S, A, B * K, *_opt(terms))
         eng.set_weights(spec, norm, version)
-        return self._solve_batch(eng, states, mu0, sd0, seed, K)
+        if user is None and peng is None:
+            return self._solve_batch(eng, states, mu0, sd0, seed, K)
+        return self._publish_proposals(eng, self._with_proposals(eng, states, mu0, sd0, seed, K, user, peng, prior_args),
+                                       K, False)
 
 
 class MPCcontroller(_TerminalValue, Controller):

@@ -174,7 +174,8 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_amin_ticket, (void*)e->d_team, (void*)e->d_team_ctl, (void*)e->d_mt_io, (void*)e->d_mt_bounds, (void*)e->d_mt_xs,
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
-                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_keep, (void*)e->d_keep_count, (void*)e->d_tc_traj,
+                    (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_keep, (void*)e->d_keep_count, (void*)e->d_prop,
+                    (void*)e->d_tc_traj,
                     (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues, (void*)e->d_tc_steps,
                     (void*)e->d_tc_ref, (void*)e->d_tc_prev})
         if (p) (void)hipFree(p);
@@ -1244,6 +1245,32 @@ int bcmpc_rollout_policy_async(bcmpc_engine* e, const double* d_state, const dou
     RolloutLaunch r;
     r.state = d_state; r.actions = d_actions; r.seed = seed; r.cand_offset = cand_offset;
     r.costs = d_costs; r.traj = d_traj; r.result = d_result; r.stream = (hipStream_t)stream;
+    r.act_out_all = d_actions_out;
+    return rollout_impl(e, r);
+}
+
+// ... with one start state per environment: tile_states, then the same launch with per-candidate states
+int bcmpc_rollout_policy_batch_async(bcmpc_engine* e, const double* d_states, int32_t n_envs, const double* d_actions,
+                                     uint64_t seed, int64_t cand_offset, double* d_costs, double* d_traj,
+                                     double* d_actions_out, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (!e || !d_states || !d_actions_out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (e->PL == 0) return fail(BCMPC_ERR_STATE, "engine was created without a policy (config.policy_hidden == 0)");
+    const bcmpc_config& c = e->cfg;
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (c.num_paths == 0) return fail(BCMPC_ERR_EMPTY, "attempt to get argmin of an empty sequence");
+    if (c.num_paths % n_envs != 0)
+        return fail(BCMPC_ERR_ARG, "num_paths (" + std::to_string(c.num_paths) + ") is not a multiple of n_envs (" +
+                                       std::to_string(n_envs) + ")");
+    HIP_TRY(hipSetDevice(c.device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
+    TileStatesArgs t{};
+    t.states = d_states; t.out = e->d_tiled; t.K = c.num_paths / n_envs; t.Ktot = c.num_paths; t.S = c.state_dim;
+    HIP_TRY(launch_tile_states(t, st));
+    RolloutLaunch r;
+    r.state = e->d_tiled; r.state_stride = c.state_dim; r.actions = d_actions; r.seed = seed; r.cand_offset = cand_offset;
+    r.costs = d_costs; r.traj = d_traj; r.stream = st; r.n_envs = n_envs;
     r.act_out_all = d_actions_out;
     return rollout_impl(e, r);
 }

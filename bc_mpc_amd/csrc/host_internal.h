@@ -98,6 +98,9 @@ struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, 
     // CEM elite carry-over (plan_noise.hip): the elites' sequences [n_envs][n_elite][H][A] and their counts
     double* d_keep = nullptr; size_t keep_cap = 0;
     int32_t* d_keep_count = nullptr; int32_t keep_count_cap = 0;
+    // proposals (plan_prop.hip): a synchronous call's host sequences [n_envs][P][H][A], uploaded with the plans
+    double* d_prop = nullptr; size_t prop_cap = 0;
+    // policy engines' batched rollout (bcmpc_rollout_policy_batch_async) tiles its states into d_tiled, above
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;
     bool team_defer = false;            // the weights are packed for rollout_team's deferred last LayerNorm

@@ -331,6 +331,15 @@ struct PlanKeepArgs {                        // keep[b][e] = the stored sequence
 hipError_t launch_plan_sample_corr(const PlanSampleCorrArgs& a, hipStream_t st);
 hipError_t launch_plan_keep(const PlanKeepArgs& a, hipStream_t st);
 
+// ---- proposals: given action sequences in every environment's last columns (plan_prop.hip; bc_mpc_amd/proposals.py) ----
+struct PlanSamplePropArgs {                  // plan_sample_corr, then column K - n_prop + p of environment b at (h, j) =
+    PlanSampleCorrArgs s;                    //   clip(prop[b * env_stride + p * seq_stride + h * step_stride + j])
+    const double* prop;                      // the source; read only, strides in doubles
+    int64_t env_stride, seq_stride, step_stride;
+    int32_t n_prop;                          // 1 <= n_prop <= K
+};
+hipError_t launch_plan_sample_prop(const PlanSamplePropArgs& a, hipStream_t st);
+
 // ---- MPPI's control-cost term and weighted sigma update (mppi_ext.hip; bc_mpc_amd/mppi_update.py) ----
 // Both read the iteration's stored actions [H][n_envs * K][A]; environment b: costs / scores / out + b K,
 // mu / sigma / mu_new + b H A.

@@ -132,6 +132,50 @@ static int mppi_ext_check(const bcmpc_mppi_ext* x) {
     return sigma_step_check(x->sigma_alpha, x->min_std, x->max_std);
 }
 
+// Proposals (bcmpc_proposals; nullptr or count == 0: none).  The source's three element strides over the extents
+// (n_envs, P, H), j innermost with stride 1 and extent A: refused when two elements could share an address --
+// taken from the smallest stride to the largest over the dimensions of extent > 1, each must cover what lies below it
+static bool proposals_none(const bcmpc_proposals* q) { return !q || q->count == 0; }
+static int prop_strides_check(int32_t n_envs, int32_t P, int32_t H, int32_t A, int64_t env_stride, int64_t seq_stride,
+                              int64_t step_stride) {
+    struct Dim { int64_t stride, extent; } d[3] = {{env_stride, n_envs}, {seq_stride, P}, {step_stride, H}};
+    for (const Dim& x : d)
+        if (x.stride < 0) return fail(BCMPC_ERR_ARG, "proposals: the strides must be >= 0");
+    std::sort(d, d + 3, [](const Dim& x, const Dim& y) { return x.stride < y.stride; });
+    int64_t below = A;                                  // elements the dimensions so far span
+    for (const Dim& x : d) {
+        if (x.extent <= 1) continue;
+        if (x.stride < below) return fail(BCMPC_ERR_ARG, "proposals: the strides alias (two elements share an address)");
+        if (x.stride > INT64_MAX / x.extent) return fail(BCMPC_ERR_ARG, "proposals: a stride is too large");
+        below = x.stride * x.extent;
+    }
+    return BCMPC_OK;
+}
+// what a call's struct shows on its own, asked before the engine is looked at ...
+static int proposals_struct_check(const bcmpc_proposals* q) {
+    if (q->count < 0) return fail(BCMPC_ERR_ARG, "proposals: count must be >= 0");
+    if (!q->sequences) return fail(BCMPC_ERR_ARG, "proposals: sequences is NULL");
+    if (q->device != 0 && q->device != 1) return fail(BCMPC_ERR_ARG, "proposals: device must be 0 (host) or 1 (device)");
+    if (q->env_stride < 0 || q->seq_stride < 0 || q->step_stride < 0)
+        return fail(BCMPC_ERR_ARG, "proposals: the strides must be >= 0");
+    return BCMPC_OK;
+}
+// ... and against the call's K candidates per environment; n_elite: CEM's with keep_elites, else 0
+static int proposals_check(const bcmpc_proposals* q, const bcmpc_engine* e, int32_t n_envs, int64_t K, int32_t n_elite) {
+    if ((int64_t)q->count + n_elite > K)
+        return fail(BCMPC_ERR_ARG, n_elite ? "proposals: count + n_elite must be <= K (the carried elites keep the first columns)"
+                                           : "proposals: count must be <= K (candidates per environment)");
+    const int32_t H = e->cfg.horizon, A = e->cfg.action_dim;
+    if (q->device == 0) {
+        const bool zero = q->env_stride == 0 && q->seq_stride == 0 && q->step_stride == 0;
+        const bool canon = q->env_stride == (int64_t)q->count * H * A && q->seq_stride == (int64_t)H * A && q->step_stride == A;
+        if (!zero && !canon)
+            return fail(BCMPC_ERR_ARG, "proposals: host sequences are [n_envs][P][H][A] (strides 0, or P*H*A, H*A, A)");
+        return BCMPC_OK;
+    }
+    return prop_strides_check(n_envs, q->count, H, A, q->env_stride, q->seq_stride, q->step_stride);
+}
+
 // a synchronous planner call's input plans, kept on a team engine for the rerun after a give-up: n doubles of
 // mu, and of sigma where the call writes it back (CEM)
 struct PlanInputs {
@@ -219,6 +263,25 @@ static int plan_sample_corr_impl(bcmpc_engine* e, const double* d_mu, const doub
     a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim; a.n_elite = n_elite;
     a.rho = rho; a.c = std::sqrt(1.0 - rho * rho);
     HIP_TRY(launch_plan_sample_corr(a, st));
+    return BCMPC_OK;
+}
+
+// ... with environment b's last n_prop columns given: d_prop read through the three strides (plan_prop.hip)
+static int plan_sample_prop_impl(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                 uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                 const int32_t* d_keep_count, int32_t n_elite, const double* d_prop, int32_t n_prop,
+                                 int64_t env_stride, int64_t seq_stride, int64_t step_stride, double* d_actions,
+                                 hipStream_t st) {
+    PlanSamplePropArgs p{};
+    PlanSampleCorrArgs& a = p.s;
+    a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts; a.out = d_actions;
+    a.keep = d_keep; a.keep_count = d_keep_count;
+    a.seed = seed; a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
+    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim; a.n_elite = n_elite;
+    a.rho = rho; a.c = std::sqrt(1.0 - rho * rho);
+    p.prop = d_prop; p.n_prop = n_prop;
+    p.env_stride = env_stride; p.seq_stride = seq_stride; p.step_stride = step_stride;
+    HIP_TRY(launch_plan_sample_prop(p, st));
     return BCMPC_OK;
 }
 
@@ -401,6 +464,32 @@ int bcmpc_plan_sample_corr_async(bcmpc_engine* e, const double* d_mu, const doub
                                  n_elite, d_actions, (hipStream_t)stream);
 }
 
+int bcmpc_plan_sample_prop_async(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                 uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                 const int32_t* d_keep_count, int32_t n_elite, const double* d_proposals, int32_t n_prop,
+                                 int64_t env_stride, int64_t seq_stride, int64_t step_stride, double* d_actions,
+                                 void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_mu || !d_sigma || !d_actions || !d_proposals) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = rho_check(rho)) return rc;
+    if ((d_keep != nullptr) != (d_keep_count != nullptr))
+        return fail(BCMPC_ERR_ARG, "d_keep and d_keep_count go together (both, or both NULL)");
+    if (d_keep && n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    if (n_prop < 1) return fail(BCMPC_ERR_ARG, "n_prop must be >= 1");
+    if ((int64_t)n_prop + (d_keep ? n_elite : 0) > K)
+        return fail(BCMPC_ERR_ARG, d_keep ? "n_prop + n_elite must be <= K (the carried elites keep the first columns)"
+                                          : "n_prop must be <= K");
+    if (const int rc = prop_strides_check(n_envs, n_prop, e->cfg.horizon, e->cfg.action_dim, env_stride, seq_stride,
+                                          step_stride))
+        return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_sample_prop_impl(e, d_mu, d_sigma, n_envs, K, seed, iteration, cand_offset, rho, d_keep, d_keep_count,
+                                 n_elite, d_proposals, n_prop, env_stride, seq_stride, step_stride, d_actions,
+                                 (hipStream_t)stream);
+}
+
 int bcmpc_plan_keep_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, const double* d_actions,
                           int32_t n_envs, int64_t K, int64_t cand_offset, int32_t n_elite, double* d_keep,
                           int32_t* d_keep_count, void* stream) {
@@ -519,7 +608,8 @@ static int keep_buffers(bcmpc_engine* e, int32_t n_envs, int32_t n_elite) {
 static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* cem,
                             const bcmpc_mppi* mp, const bcmpc_sampling* smp, uint64_t seed, int64_t cand_offset,
                             double* mu, double* sigma_io, const double* sigma_in, bcmpc_result* out,
-                            bcmpc_mppi_stats* stats, double* costs_out, const bcmpc_mppi_ext* ext = nullptr) {
+                            bcmpc_mppi_stats* stats, double* costs_out, const bcmpc_mppi_ext* ext = nullptr,
+                            const bcmpc_proposals* prop = nullptr) {
     const bcmpc_config& c = e->cfg;
     const int32_t iterations = cem ? cem->iterations : mp->iterations;
     const int64_t K = c.num_paths / n_envs;
@@ -532,6 +622,20 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     const bool corr = !sampling_default(smp), carry = corr && cem && smp->keep_elites && iterations > 1;
     if (carry)
         if (const int rc = keep_buffers(e, n_envs, cem->n_elite)) return rc;
+    // proposals (checked by the caller): host sequences go up with the plans, device ones are read where they are
+    const int32_t P = proposals_none(prop) ? 0 : prop->count;
+    const size_t nprop = (size_t)n_envs * (size_t)P * ha;
+    if (P && !prop->device && nprop > e->prop_cap) {
+        if (e->d_prop) (void)hipFree(e->d_prop);
+        e->d_prop = nullptr;
+        e->prop_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_prop, nprop * sizeof(double)));
+        e->prop_cap = nprop;
+    }
+    const double* d_prop = !P ? nullptr : prop->device ? prop->sequences : e->d_prop;
+    const int64_t prop_env = !P ? 0 : prop->device ? prop->env_stride : (int64_t)P * (int64_t)ha;
+    const int64_t prop_seq = !P ? 0 : prop->device ? prop->seq_stride : (int64_t)ha;
+    const int64_t prop_step = !P ? 0 : prop->device ? prop->step_stride : (int64_t)c.action_dim;
     if (!e->d_tiled) HIP_TRY(hipMalloc(&e->d_tiled, (size_t)c.num_paths * c.state_dim * sizeof(double)));
     const bool control = ext && !cem && ext->control_weight != 0.0, adapt = ext && !cem && ext->adapt_sigma != 0;
     if (control && (size_t)c.num_paths > e->mppi_scores_cap) {
@@ -548,13 +652,19 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     HIP_TRY(hipMemcpyAsync(e->d_bstates, states, sizeof(double) * (size_t)n_envs * c.state_dim, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->d_bmu, mu, nplan * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->d_bsigma, sigma, nplan * sizeof(double), hipMemcpyHostToDevice, st));
+    if (P && !prop->device)
+        HIP_TRY(hipMemcpyAsync(e->d_prop, prop->sequences, nprop * sizeof(double), hipMemcpyHostToDevice, st));
     if (e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
     TileStatesArgs t{};
     t.states = e->d_bstates; t.out = e->d_tiled; t.K = K; t.Ktot = c.num_paths; t.S = c.state_dim;
     HIP_TRY(launch_tile_states(t, st));
     for (int it = 0; it < iterations; ++it) {
         const bool kept = carry && it > 0;
-        if (const int rc = !corr ? plan_sample_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+        if (const int rc = P ? plan_sample_prop_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+                                                     smp ? smp->rho : 0.0, kept ? e->d_keep : nullptr,
+                                                     kept ? e->d_keep_count : nullptr, cem ? cem->n_elite : 0, d_prop,
+                                                     P, prop_env, prop_seq, prop_step, e->d_actions, st)
+                           : !corr ? plan_sample_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
                                                     e->d_actions, st)
                                  : plan_sample_corr_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
                                                          smp->rho, kept ? e->d_keep : nullptr,
@@ -606,7 +716,7 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
         if (const int fr = team_fallback(e)) return fr;
         inputs.restore(mu, sigma_io);
         return plan_get_actions(e->fb, states, n_envs, cem, mp, smp, seed, cand_offset, mu, sigma_io, sigma_in, out,
-                                stats, costs_out, ext);
+                                stats, costs_out, ext, prop);
     }
     std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
     return BCMPC_OK;
@@ -1051,6 +1161,86 @@ int bcmpc_mppi_get_action_x(bcmpc_engine* e, const double* state, const bcmpc_mp
     if (const int rc = k_global_check(p->k_global, "single-device MPPI", e->cfg.num_paths)) return rc;
     if (const int rc = batch_check(e, 1)) return rc;
     return plan_get_actions(e, state, 1, nullptr, p, sampling, seed, 0, mu, sigma, sigma, out, stats, nullptr, ext);
+}
+
+// ... and with proposals: none, the calls above; else the batched chain with plan_sample_prop as its
+// sampler.  One body per planner: the single calls are its n_envs = 1, cand_offset = 0 form with the single
+// calls' own refusals in front.
+static int cem_proposals_call(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                              const bcmpc_sampling* sampling, const bcmpc_proposals* prop, uint64_t seed,
+                              int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out, double* costs_out,
+                              bool single) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (const int rc = proposals_struct_check(prop)) return rc;
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (single && e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "CEM needs a fused objective");
+    if (const int rc = cem_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, false)) return rc;
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    const int64_t K = e->cfg.num_paths / n_envs;
+    if (const int rc = single ? k_global_check(p->k_global, "single-device CEM", K)
+                              : k_global_check(p->k_global, "batched CEM", K, "num_paths / n_envs"))
+        return rc;
+    const bool keep = sampling && sampling->keep_elites;
+    if (const int rc = proposals_check(prop, e, n_envs, K, keep ? p->n_elite : 0)) return rc;
+    return plan_get_actions(e, states, n_envs, p, nullptr, sampling, seed, cand_offset, mu, sigma, nullptr, out, nullptr,
+                            costs_out, nullptr, prop);
+}
+
+static int mppi_proposals_call(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                               const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext, const bcmpc_proposals* prop,
+                               uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                               bcmpc_mppi_stats* stats, double* costs_out, bool single) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (const int rc = mppi_ext_check(ext)) return rc;
+    if (const int rc = proposals_struct_check(prop)) return rc;
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (single && e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "MPPI needs a fused objective");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    const int64_t K = e->cfg.num_paths / n_envs;
+    if (const int rc = single ? k_global_check(p->k_global, "single-device MPPI", K)
+                              : k_global_check(p->k_global, "batched MPPI", K, "num_paths / n_envs"))
+        return rc;
+    if (const int rc = proposals_check(prop, e, n_envs, K, 0)) return rc;
+    // (sigma is written back only under adapt_sigma, as in the _x calls)
+    return plan_get_actions(e, states, n_envs, nullptr, p, sampling, seed, cand_offset, mu, sigma, sigma, out, stats,
+                            costs_out, mppi_ext_default(ext) ? nullptr : ext, prop);
+}
+
+int bcmpc_cem_get_action_p(bcmpc_engine* e, const double* state, const bcmpc_cem* p, const bcmpc_sampling* sampling,
+                           const bcmpc_proposals* prop, uint64_t seed, double* mu, double* sigma, bcmpc_result* out) {
+    if (proposals_none(prop)) return bcmpc_cem_get_action_s(e, state, p, sampling, seed, mu, sigma, out);
+    return cem_proposals_call(e, state, 1, p, sampling, prop, seed, 0, mu, sigma, out, nullptr, true);
+}
+
+int bcmpc_mppi_get_action_p(bcmpc_engine* e, const double* state, const bcmpc_mppi* p, const bcmpc_sampling* sampling,
+                            const bcmpc_mppi_ext* ext, const bcmpc_proposals* prop, uint64_t seed, double* mu,
+                            double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    if (proposals_none(prop)) return bcmpc_mppi_get_action_x(e, state, p, sampling, ext, seed, mu, sigma, out, stats);
+    return mppi_proposals_call(e, state, 1, p, sampling, ext, prop, seed, 0, mu, sigma, out, stats, nullptr, true);
+}
+
+int bcmpc_cem_get_actions_batch_p(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                                  const bcmpc_sampling* sampling, const bcmpc_proposals* prop, uint64_t seed,
+                                  int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out, double* costs_out) {
+    if (proposals_none(prop))
+        return bcmpc_cem_get_actions_batch_s(e, states, n_envs, p, sampling, seed, cand_offset, mu, sigma, out, costs_out);
+    return cem_proposals_call(e, states, n_envs, p, sampling, prop, seed, cand_offset, mu, sigma, out, costs_out, false);
+}
+
+int bcmpc_mppi_get_actions_batch_p(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                                   const bcmpc_proposals* prop, uint64_t seed, int64_t cand_offset, double* mu,
+                                   double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out) {
+    if (proposals_none(prop))
+        return bcmpc_mppi_get_actions_batch_x(e, states, n_envs, p, sampling, ext, seed, cand_offset, mu, sigma, out,
+                                              stats, costs_out);
+    return mppi_proposals_call(e, states, n_envs, p, sampling, ext, prop, seed, cand_offset, mu, sigma, out, stats,
+                               costs_out, false);
 }
 
 int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, uint64_t seed,

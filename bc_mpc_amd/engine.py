@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from . import mppi_update as _mppi_update
+from . import proposals as _proposals
 from . import sampling as _sampling
 
 _ACT = {"tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU}
@@ -83,6 +84,19 @@ class BatchResult:
     best_cost: np.ndarray      # [B] f64
     first_action: np.ndarray   # [B, A] f64
     costs: Optional[np.ndarray] = None   # [B, K] f64 (cem_get_actions / mppi_get_actions: [iterations, B, K])
+
+
+@dataclass
+class DeviceProposals:
+    """Proposals in device memory for the planners' ``proposals=`` (proposals.py): ``ptr`` a device address of
+    f64, ``count`` sequences per environment, read in the engine's stream order through the element strides (in
+    doubles; the action dimension has stride 1).  ``keep``: whatever owns the memory, held for the call."""
+    ptr: int
+    count: int
+    env_stride: int
+    seq_stride: int
+    step_stride: int
+    keep: object = None
 
 
 # bcmpc_mppi_stats as a NumPy record (mppi_get_actions returns one per environment)
@@ -199,6 +213,7 @@ class _EngineCalls:
     _CEM, _MPPI = "bcmpc_cem_get_action", "bcmpc_mppi_get_action"
     _CEM_S, _MPPI_S = "bcmpc_cem_get_action_s", "bcmpc_mppi_get_action_s"     # (None: no such entry)
     _MPPI_X = "bcmpc_mppi_get_action_x"
+    _CEM_P, _MPPI_P = "bcmpc_cem_get_action_p", "bcmpc_mppi_get_action_p"
 
     def _fresh(self) -> None:
         """The wrapper's host state for a handle nothing has been set on yet."""
@@ -242,6 +257,25 @@ class _EngineCalls:
                                                                   max_std, temperature)
         return _lib.MppiExt(weight, int(adapt), 0, alpha, lo, hi) if weight != 0.0 or adapt else None
 
+    def _proposals(self, proposals, n_envs: Optional[int], n_elite: int = 0):
+        """The ``_lib.Proposals`` of a planner call's ``proposals=`` (proposals.py) and what keeps its memory alive,
+        or ``(None, None)`` without: the call then goes to the entry point it has always gone to.  A host array is
+        ``[P, H, A]`` (``n_envs`` None: the single calls) or ``[n_envs, P, H, A]``; ``DeviceProposals`` names device
+        memory.  ``n_elite``: the carried elites of a CEM call with ``keep_elites`` (they keep the first columns)."""
+        if proposals is None:
+            return None, None
+        B = 1 if n_envs is None else int(n_envs)
+        K = self.num_paths // B
+        if isinstance(proposals, DeviceProposals):
+            d = proposals
+            _proposals.check_count(d.count, K, n_elite)
+            _proposals.check_strides(B, d.count, self.horizon, self.action_dim, d.env_stride, d.seq_stride, d.step_stride)
+            return _lib.Proposals(int(d.ptr), int(d.count), 1, int(d.env_stride), int(d.seq_stride),
+                                  int(d.step_stride)), d
+        arr = _proposals.as_sequences(proposals, self.horizon, self.action_dim, n_envs)
+        P = _proposals.check_count(arr.shape[-3], K, n_elite)
+        return _lib.Proposals(arr.ctypes.data, P, 0, *_proposals.canonical_strides(P, self.horizon, self.action_dim)), arr
+
     def _step_result(self, res, costs=None) -> StepResult:
         return StepResult(int(res.best_index), float(res.best_cost),
                           np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
@@ -253,20 +287,27 @@ class _EngineCalls:
         return getattr(self._lib, name)
 
     def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
-                       seed: int, rho: float = 0.0, keep_elites: bool = False
+                       seed: int, rho: float = 0.0, keep_elites: bool = False, proposals=None
                        ) -> Tuple[StepResult, np.ndarray, np.ndarray]:
         """All CEM iterations on this device (bcmpc_cem_get_action; an ensemble: bcmpc_ensemble_cem_get_action,
         the elites of every iteration chosen by the combined value).  ``mu``/``sigma`` are ``[H, A]``; returns
         (result with best_index = iteration*K + candidate, mu', sigma').  ``rho`` / ``keep_elites``:
-        temporally correlated noise and elite carry-over (sampling.py; bcmpc_cem_get_action_s)."""
+        temporally correlated noise and elite carry-over (sampling.py; bcmpc_cem_get_action_s).  ``proposals``
+        (``[P, H, A]`` or ``DeviceProposals``): given sequences in the last P columns of every iteration's
+        population (proposals.py; bcmpc_cem_get_action_p)."""
         smp = self._sampling(rho, keep_elites)
+        prop, _alive = self._proposals(proposals, None, int(n_elite) if smp is not None and smp.keep_elites else 0)
         st = self._state(state)
         shape = (self.horizon, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = _lib.Result()
-        if smp is None:
+        if prop is not None:
+            _lib.check(self._s_entry(self._CEM_P, "cem_get_action", "proposals")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None, ctypes.byref(prop),
+                ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res)))
+        elif smp is None:
             _lib.check(getattr(self._lib, self._CEM)(self._h, _dp(st), ctypes.byref(p),
                                                      ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s),
                                                      ctypes.byref(res)))
@@ -278,7 +319,8 @@ class _EngineCalls:
 
     def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
                         seed: int, rho: float = 0.0, control_cost=0.0, adapt_sigma: bool = False,
-                        sigma_alpha: float = 0.0, min_std: float = 0.0, max_std: Optional[float] = None):
+                        sigma_alpha: float = 0.0, min_std: float = 0.0, max_std: Optional[float] = None,
+                        proposals=None):
         """``iterations`` rounds of CEM-style rollout + MPPI update on this device (bcmpc_mppi_get_action; an
         ensemble: bcmpc_ensemble_mppi_get_action, the softmin weights from the combined value; DESIGN.md "MPPI").
         ``mu``/``sigma`` are ``[H, A]``; returns (the best single candidate over all rounds, best_index =
@@ -290,15 +332,28 @@ class _EngineCalls:
         the weights see -- the record stays on the raw costs, ``stats.min_cost`` is the minimum augmented score --
         and ``adapt_sigma`` refits sigma after every round as ``clamp(sigma_alpha * sigma + (1 - sigma_alpha) *
         weighted std, min_std, max_std)`` (mppi_update.py; bcmpc_mppi_get_action_x).  With
-        ``adapt_sigma`` a fourth element, sigma' ``[H, A]``, is returned."""
+        ``adapt_sigma`` a fourth element, sigma' ``[H, A]``, is returned.
+
+        ``proposals`` (``[P, H, A]`` or ``DeviceProposals``): given sequences in the last P columns of every round's
+        population (proposals.py; bcmpc_mppi_get_action_p).  A proposal is weighted like a sample although it is
+        not a draw from ``N(mu, sigma)``."""
         smp = self._sampling(rho)
         ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
+        prop, _alive = self._proposals(proposals, None)
         st = self._state(state)
         shape = (self.horizon, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res, stats = _lib.Result(), _lib.MppiStats()
+        if prop is not None:
+            s = np.array(s, dtype=np.float64, copy=True)           # (in / out: the caller's array is not written)
+            _lib.check(self._s_entry(self._MPPI_P, "mppi_get_action", "proposals")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(ext) if ext is not None else None, ctypes.byref(prop),
+                ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res), ctypes.byref(stats)))
+            adapt = ext is not None and ext.adapt_sigma
+            return (self._step_result(res), m, stats, s) if adapt else (self._step_result(res), m, stats)
         if ext is not None:
             s = np.array(s, dtype=np.float64, copy=True)           # (in / out: the caller's array is not written)
             _lib.check(self._s_entry(self._MPPI_X, "mppi_get_action", "MPPI's control cost and sigma update")(
@@ -922,6 +977,20 @@ class RolloutEngine(_EngineCalls):
             ctypes.c_int64(cand_offset), vp(d_costs), vp(d_traj), ctypes.c_void_p(d_actions_out), vp(d_result),
             ctypes.c_void_p(stream)))
 
+    def rollout_policy_batch_async(self, d_states: int, n_envs: int, d_actions: Optional[int], seed: int,
+                                   cand_offset: int, d_costs: Optional[int], d_traj: Optional[int],
+                                   d_actions_out: int, stream: Optional[int] = None) -> None:
+        """Policy engines: rollout_policy_async with one start state per environment (bcmpc_rollout_policy_batch_async).
+        ``d_states`` ``[n_envs, S]``; environment b owns columns ``[b * K, (b + 1) * K)``, ``K = num_paths //
+        n_envs``, all started from ``d_states[b]``.  ``d_actions_out`` ``[H, num_paths, A]`` is then a proposal
+        source with ``proposals.policy_strides(n_envs, K, A)``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_rollout_policy_batch_async(
+            self._h, ctypes.c_void_p(d_states), int(n_envs), vp(d_actions), ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(cand_offset), vp(d_costs), vp(d_traj), ctypes.c_void_p(d_actions_out),
+            ctypes.c_void_p(stream)))
+
     # ------------------------------------------------------------------ CEM
     def cem_rollout_async(self, d_state: int, d_mu: int, d_sigma: int, seed: int, iteration: int,
                           cand_offset: int, k_global: int, d_costs: int, d_result: Optional[int], merge: bool,
@@ -983,19 +1052,26 @@ class RolloutEngine(_EngineCalls):
 
     def cem_get_actions(self, states, mu, sigma, iterations: int, n_elite: int, alpha: float, seed: int,
                         cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0,
-                        keep_elites: bool = False) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+                        keep_elites: bool = False, proposals=None) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
         """Batched CEM (bcmpc_cem_get_actions_batch): ``states`` ``[B, S]``, ``mu`` / ``sigma``
         ``[B, H, A]``, ``K = num_paths // B`` candidates and ``n_elite`` elites per environment, columns
         as for get_actions.  Returns (records with ``best_index = iteration*K + candidate`` per
         environment and ``costs`` ``[iterations, B, K]`` when asked for, mu' ``[B, H, A]``, sigma').
         ``rho`` / ``keep_elites``: temporally correlated noise and elite carry-over (sampling.py;
-        bcmpc_cem_get_actions_batch_s)."""
+        bcmpc_cem_get_actions_batch_s).  ``proposals`` (``[B, P, H, A]`` or ``DeviceProposals``): every
+        environment's given sequences in its last P columns (proposals.py; bcmpc_cem_get_actions_batch_p)."""
         smp = self._sampling(rho, keep_elites)
         st, B, m, s = self._plan_batch_args(states, mu, sigma, True)
+        prop, _alive = self._proposals(proposals, B, int(n_elite) if smp is not None and smp.keep_elites else 0)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = (_lib.Result * B)()
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
-        if smp is None:
+        if prop is not None:
+            _lib.check(self._lib.bcmpc_cem_get_actions_batch_p(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(prop), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s),
+                res, _dp(costs) if costs is not None else None))
+        elif smp is None:
             _lib.check(self._lib.bcmpc_cem_get_actions_batch(
                 self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.c_uint64(seed & (2**64 - 1)),
                 ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, _dp(costs) if costs is not None else None))
@@ -1009,22 +1085,31 @@ class RolloutEngine(_EngineCalls):
     def mppi_get_actions(self, states, mu, sigma, iterations: int, temperature: float, seed: int,
                          cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0, control_cost=0.0,
                          adapt_sigma: bool = False, sigma_alpha: float = 0.0, min_std: float = 0.0,
-                         max_std: Optional[float] = None):
+                         max_std: Optional[float] = None, proposals=None):
         """Batched MPPI (bcmpc_mppi_get_actions_batch): as cem_get_actions, with the softmin update of
         mppi_get_action per environment.  Returns (records, mu' ``[B, H, A]`` whose rows ``[b, 0]`` are the
         actions to apply, the last round's statistics as a ``[B]`` array of MPPI_STATS).  sigma is not
         modified.  ``rho``: temporally correlated noise (sampling.py; bcmpc_mppi_get_actions_batch_s).
         ``control_cost`` / ``adapt_sigma`` / ``sigma_alpha`` / ``min_std`` / ``max_std``: as mppi_get_action
         (bcmpc_mppi_get_actions_batch_x); the returned costs stay the raw ones, and with ``adapt_sigma`` a fourth
-        element, sigma' ``[B, H, A]``, is returned."""
+        element, sigma' ``[B, H, A]``, is returned.  ``proposals`` (``[B, P, H, A]`` or ``DeviceProposals``): every
+        environment's given sequences in its last P columns (proposals.py; bcmpc_mppi_get_actions_batch_p)."""
         smp = self._sampling(rho)
         ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
-        st, B, m, s = self._plan_batch_args(states, mu, sigma, ext is not None)
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, ext is not None or proposals is not None)
+        prop, _alive = self._proposals(proposals, B)
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res = (_lib.Result * B)()
         stats = np.zeros(B, dtype=MPPI_STATS)
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
         d_stats, d_costs = stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None
+        if prop is not None:
+            _lib.check(self._lib.bcmpc_mppi_get_actions_batch_p(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(ext) if ext is not None else None, ctypes.byref(prop), ctypes.c_uint64(seed & (2**64 - 1)),
+                ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, d_stats, d_costs))
+            out = self._batch_result(res, B, costs, int(iterations))
+            return (out, m, stats, s) if ext is not None and ext.adapt_sigma else (out, m, stats)
         if ext is not None:
             _lib.check(self._lib.bcmpc_mppi_get_actions_batch_x(
                 self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
@@ -1066,6 +1151,22 @@ class RolloutEngine(_EngineCalls):
             self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
             int(iteration), int(cand_offset), float(rho), vp(d_keep), vp(d_keep_count), int(n_elite),
             vp(d_actions), ctypes.c_void_p(stream)))
+
+    def plan_sample_prop_async(self, d_mu: int, d_sigma: int, n_envs: int, K: int, seed: int, iteration: int,
+                               cand_offset: int, rho: float, d_actions: int, d_proposals: int, n_prop: int,
+                               env_stride: int, seq_stride: int, step_stride: int, d_keep: Optional[int] = None,
+                               d_keep_count: Optional[int] = None, n_elite: int = 0,
+                               stream: Optional[int] = None) -> None:
+        """bcmpc_plan_sample_prop_async: plan_sample_corr_async with environment b's LAST ``n_prop`` columns given --
+        column ``K - n_prop + p`` at ``(h, j)`` is the clipped ``d_proposals[b * env_stride + p * seq_stride + h *
+        step_stride + j]`` (f64, strides in doubles; proposals.inject).  The source is read only."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_sample_prop_async(
+            self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), int(cand_offset), float(rho), vp(d_keep), vp(d_keep_count), int(n_elite),
+            vp(d_proposals), int(n_prop), int(env_stride), int(seq_stride), int(step_stride), vp(d_actions),
+            ctypes.c_void_p(stream)))
 
     def plan_keep_async(self, d_elite: int, d_count: int, d_actions: int, n_envs: int, K: int, cand_offset: int,
                         n_elite: int, d_keep: int, d_keep_count: int, stream: Optional[int] = None) -> None:

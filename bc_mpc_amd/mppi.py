@@ -48,7 +48,11 @@ class MPPIcontroller(Planner):
     every call, one rank and one dynamics model only).  ``control_cost`` / ``adapt_sigma`` / ``sigma_alpha`` /
     ``min_std`` / ``max_std``: the control-cost term and the sigma update (module docstring; read on every call,
     one rank and one dynamics model only); ``last_sigma`` is the sigma the call ended with (``[H, A]``, batched
-    ``[B, H, A]``) and, with the control cost on, ``last_stats.min_cost`` the minimum augmented score."""
+    ``[B, H, A]``) and, with the control cost on, ``last_stats.min_cost`` the minimum augmented score.
+    ``proposals=`` on a call and ``policy_prior`` / ``policy_paths`` / ``policy_stochastic`` / ``policy_explore``: given
+    action sequences, and a policy net's closed-loop rollouts, in the last candidates of every round (proposals.py,
+    DESIGN.md 9m; one rank and one dynamics model only).  A proposal is no draw from ``N(mu, sigma)``: its softmin
+    weight and its control-cost term (``eps = a - mu``) are the heuristic TD-MPC uses for its policy trajectories."""
     _KIND = "MPPI"
     # what the update adds (mppi_update.py): read on every call, never an engine constructor argument
     control_cost = 0.0
@@ -79,10 +83,16 @@ class MPPIcontroller(Planner):
                  adapt_sigma: bool = False,
                  sigma_alpha: float = 0.0,
                  min_std: float = 0.0,
-                 max_std: Optional[float] = None):
+                 max_std: Optional[float] = None,
+                 policy_prior=None,
+                 policy_paths: int = 0,
+                 policy_stochastic: bool = True,
+                 policy_explore: float = 0.0):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0x3B9AC1 if seed is None else seed, device, process_group,
-                         terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho)
+                         terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho,
+                         policy_prior=policy_prior, policy_paths=policy_paths, policy_stochastic=policy_stochastic,
+                         policy_explore=policy_explore)
         if not (math.isfinite(temperature) and temperature > 0):
             raise ValueError("temperature must be finite and > 0")
         self.temperature = float(temperature)
@@ -124,6 +134,30 @@ class MPPIcontroller(Planner):
         self.last_cost, self.last_position = res.best_cost, res.best_index
         self.last_ess, self.last_stats = float(stats.ess), stats
         return mu[0].copy()
+
+    def _call_proposals(self, eng, states, mu0, sd0, seed, src):
+        res, mu, stats, *sd = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed,
+                                                   return_costs=True, proposals=src, **self._sampling_args(),
+                                                   **self._update_args())
+        return res, mu, stats, sd[0] if sd else sd0
+
+    def _publish_proposals(self, eng, out, K, single: bool):
+        res, mu, stats, sd = out
+        if single:
+            from . import _lib
+            self._note_planner_value(eng, int(res.best_index[0]), K)
+            self._mu = self.last_mu = mu[0]
+            self.last_sigma = sd[0]
+            self.last_cost, self.last_position = float(res.best_cost[0]), int(res.best_index[0])
+            self.last_stats = _lib.MppiStats(*stats[0].tolist())
+            self.last_ess = float(self.last_stats.ess)
+            return mu[0, 0].copy()
+        self._note_planner_value(eng, res.best_index, K)
+        self._store_plans(mu)
+        self.last_mu, self.last_sigma = mu, sd
+        self.last_cost, self.last_position = res.best_cost, res.best_index
+        self.last_ess, self.last_stats = stats["ess"].copy(), stats
+        return mu[:, 0].copy()
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, stats, *sd = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed,

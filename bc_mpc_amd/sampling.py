@@ -13,8 +13,9 @@ nothing itself: the independent normals ``z`` are the planners' Irwin-Hall draws
   the best sequence found so far is never lost and the per-iteration best cost cannot rise.
 * ``refit_from_actions``: the CEM refit's statistics on given elite actions, in the device's summation order.
 
-Not built: power-law (FFT) noise, elites carried (shifted) from one control step to the next, carrying a
-fraction of the elites, ensembles and more than one rank.  (MPPI's control-cost term: mppi_update.py.)
+Not built: power-law (FFT) noise, carrying a fraction of the elites, ensembles and more than one rank.  The
+library itself carries no elites from one control step to the next; a caller who keeps them passes them (shifted)
+as ``proposals=`` of the next call (proposals.py).  (MPPI's control-cost term: mppi_update.py.)
 """
 from __future__ import annotations
 

@@ -803,6 +803,80 @@ int bcmpc_mppi_sigma_update_async(bcmpc_engine* eng, const double* d_scores, con
                                   double min_std, double max_std, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Proposals: given action sequences in every iteration's population (additive to ABI 5; callers detect them by the
+ * symbol bcmpc_cem_get_action_p; semantics in DESIGN.md 9m, defined bit for bit by bc_mpc_amd/proposals.py).
+ * A call carries count = P >= 1 sequences [H][A] per environment.  In EVERY iteration environment b's population is
+ * the one the call would have had, with its LAST P columns replaced: column K - P + p at (h, j) holds
+ *   v = sequences[b * env_stride + p * seq_stride + h * step_stride + j];  v < low[j] ? low[j] : (v > high[j] ? high[j] : v)
+ * -- the samplers' own clip: a NaN stays NaN (last in select, no weight in MPPI), -0.0 against a bound of 0.0 stays
+ * -0.0.  The replaced columns' Philox draws are unused and no index shifts: every other column holds today's bits.
+ * Carried elites keep the FIRST columns: P + n_elite <= K with keep_elites, P <= K otherwise (P == K: nothing is
+ * sampled).  Everything downstream reads the stored array, as under rho: the record (best_index = iteration * K +
+ * column may name a proposal column, first_action is then the stored, clipped one), select, the refit, plan_keep, the
+ * MPPI update, the control cost and the sigma update.  In MPPI a proposal is not a draw from N(mu, sigma): its
+ * softmin weight and its control-cost term (eps = a - mu) are the heuristic TD-MPC uses.  Nothing is carried
+ * between calls.
+ *   device == 0  sequences is host memory in the canonical layout [n_envs][P][H][A], uploaded with the plans; the
+ *                strides are all 0 or the canonical (P * H * A, H * A, A)
+ *   device == 1  sequences is device memory, read in the engine's stream order through the three element strides
+ *                (in doubles; j has stride 1): the canonical layout, or (P * A, A, n_envs * P * A) for the policy
+ *                engines' output [H][n_envs * P][A] (bcmpc_rollout_policy_batch_async).  The strides are >= 0 and,
+ *                taken from the smallest to the largest over the dimensions of extent > 1, each is at least the
+ *                extent it steps over (A, then stride * extent of the one before): no two elements alias.
+ * A NULL pointer or count == 0 forwards to the _s / _x entry: today's call, bit for bit.  Anything else runs the
+ * batched chain (n_envs = 1, cand_offset = 0 for the single calls) with plan_sample_prop as its sampler -- one
+ * sampler launch per iteration, as ever; at rho == 0 the sampled columns hold plan_sample's bits.  A team-kernel
+ * engine whose team gave up reruns the whole call, proposals included, on its fallback engine.
+ * BCMPC_ERR_ARG (before any HIP call): count < 0 or beyond the limits above, NULL sequences, device not 0 / 1,
+ * strides that alias (or, on the host, are not canonical), and what the _s / _x calls refuse.
+ * BCMPC_ERR_UNSUPPORTED: a communicator attached, a fused policy on the planning engine.  Ensembles have no _p
+ * entry. */
+typedef struct bcmpc_proposals {
+    const double* sequences;
+    int32_t count;           /* P: sequences per environment; 0: none */
+    int32_t device;          /* 0: host memory, canonical | 1: device memory */
+    int64_t env_stride;      /* in doubles */
+    int64_t seq_stride;
+    int64_t step_stride;
+} bcmpc_proposals;
+
+int bcmpc_cem_get_action_p(bcmpc_engine* eng, const double* state, const bcmpc_cem* params,
+                           const bcmpc_sampling* sampling, const bcmpc_proposals* proposals, uint64_t seed,
+                           double* mu, double* sigma, bcmpc_result* out);
+int bcmpc_mppi_get_action_p(bcmpc_engine* eng, const double* state, const bcmpc_mppi* params,
+                            const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                            const bcmpc_proposals* proposals, uint64_t seed, double* mu, double* sigma /* in/out */,
+                            bcmpc_result* out, bcmpc_mppi_stats* stats);
+int bcmpc_cem_get_actions_batch_p(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_cem* params,
+                                  const bcmpc_sampling* sampling, const bcmpc_proposals* proposals, uint64_t seed,
+                                  int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                  double* costs_out);
+int bcmpc_mppi_get_actions_batch_p(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_mppi* params,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                                   const bcmpc_proposals* proposals, uint64_t seed, int64_t cand_offset, double* mu,
+                                   double* sigma /* in/out */, bcmpc_result* out, bcmpc_mppi_stats* stats,
+                                   double* costs_out);
+
+/* Their building blocks (device pointers, stream-ordered, no host synchronisation).
+ *   plan_sample_prop      bcmpc_plan_sample_corr_async plus the proposal columns: d_proposals, n_prop (1 <= n_prop <=
+ *                K, n_prop + n_elite <= K with a keep buffer) and the three strides, as device == 1 above.  The
+ *                source is read only.
+ *   rollout_policy_batch  bcmpc_rollout_policy_async with one start state per environment: d_states [n_envs][S],
+ *                num_paths % n_envs == 0, environment b owns columns [b * K, (b + 1) * K), K = num_paths / n_envs,
+ *                and every one of them starts from d_states[b] (the states are tiled, then rolled out with a state
+ *                stride of S -- no kernel differs).  d_actions_out [H][num_paths][A] is then the source layout
+ *                (P * A, A, n_envs * P * A) with P = K.  n_envs == 1 gives bcmpc_rollout_policy_async's bits.
+ *                Team-kernel engines: bcmpc_engine_status once the stream has completed, as always. */
+int bcmpc_plan_sample_prop_async(bcmpc_engine* eng, const double* d_mu, const double* d_sigma, int32_t n_envs,
+                                 int64_t K, uint64_t seed, int32_t iteration, int64_t cand_offset, double rho,
+                                 const double* d_keep, const int32_t* d_keep_count, int32_t n_elite,
+                                 const double* d_proposals, int32_t n_prop, int64_t env_stride, int64_t seq_stride,
+                                 int64_t step_stride, double* d_actions, void* stream);
+int bcmpc_rollout_policy_batch_async(bcmpc_engine* eng, const double* d_states, int32_t n_envs,
+                                     const double* d_actions, uint64_t seed, int64_t cand_offset, double* d_costs,
+                                     double* d_traj, double* d_actions_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Model ensembles (additive to ABI 5; callers detect them by the symbol bcmpc_ensemble_create; not in
  * the reference, semantics in DESIGN.md 9g).  An ensemble holds E dynamics nets of one architecture and
  * one configuration -- E member engines of the same config, hence the same kernel layout.  Candidate k
