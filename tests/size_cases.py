@@ -67,10 +67,24 @@ def normalization(S, A, reward=False):
     return norm
 
 
+def net_spec(net):
+    """(hidden, L, act, ln, seed_base) of a name of NETS, or of a (hidden, L, act, ln[, seed_base]) tuple given
+    in its place (depth_cases.py's nets, which are not entries of NETS)."""
+    t = NETS[net] if isinstance(net, str) else tuple(net)
+    return t if len(t) == 5 else t + (1000,)          # (1000: synthetic_weights' own default)
+
+
+def net_name(net):
+    if isinstance(net, str):
+        return net
+    hidden, L, act, ln = net_spec(net)[:4]
+    return f"{L}x{hidden}{act}{'LN' if ln else ''}"
+
+
 def weights(S, A, net):
     from oracle import mpc_oracle as orc
-    hidden, L, act, ln = NETS[net]
-    return orc.synthetic_weights(S, A, hidden, L, act, ln)
+    hidden, L, act, ln, seed_base = net_spec(net)
+    return orc.synthetic_weights(S, A, hidden, L, act, ln, seed_base=seed_base)
 
 
 def no_cost(state, action, next_state):
@@ -84,15 +98,16 @@ def other_roundings(w, norm):
             orc.NumpyDynamicsChunked(w, norm, 0)]
 
 
-def state_bar(w, norm, state, acts, want, label=""):
+def state_bar(w, norm, state, acts, want, label="", check=True):
     """The per-entry bar for the states ``want`` = rollout(NumpyDynamics(w, norm), state, acts) and the rounding
-    spread in base bars (module docstring).  Fails when the widened bar would pass 1e-5 + 1e-5 |want| anywhere."""
+    spread in base bars (module docstring).  Fails when the widened bar would pass 1e-5 + 1e-5 |want| anywhere
+    (``check=False``: returns it all the same, for measuring a net before it is taken)."""
     from oracle import mpc_oracle as orc
     from test_gpu_parity import COND_K
     spread = np.max([np.abs(orc.rollout(d, state, acts, no_cost)[1] - want) for d in other_roundings(w, norm)], axis=0)
     base = BASE_A + BASE_R * np.abs(want)
     bar = base + COND_K * spread
-    assert (bar <= CAP_A + CAP_R * np.abs(want)).all(), (
+    assert not check or (bar <= CAP_A + CAP_R * np.abs(want)).all(), (
         f"{label}: the rounding spread of these inputs reaches {np.max(spread / base):.2f} base bars; the widened "
         f"bar would pass 1e-5 (1 + |want|)")
     return bar, spread / base
@@ -112,12 +127,14 @@ def action_sources(A, K, H):
 
 
 class Case:
-    """One (S, A, net, K, H): inputs, the oracle's states and costs per action source, and the per-entry bar."""
+    """One (S, A, net, K, H): inputs, the oracle's states and costs per action source, and the per-entry bar.
+    ``net``: a name of NETS or a spec tuple (net_spec); ``self.net`` is its name either way.  ``check=False``
+    builds the case even where its widened bar passes the cap (state_bar), for measuring a net before it is taken."""
 
-    def __init__(self, S, A, net, K, H):
+    def __init__(self, S, A, net, K, H, check=True):
         from oracle import mpc_oracle as orc
-        self.S, self.A, self.net, self.K, self.H = S, A, net, K, H
-        self.hidden, self.L, self.act, self.ln = NETS[net]
+        self.S, self.A, self.net, self.K, self.H = S, A, net_name(net), K, H
+        self.hidden, self.L, self.act, self.ln = net_spec(net)[:4]
         self.w = weights(S, A, net)
         self.norm = normalization(S, A)
         self.state = orc.synthetic_state(self.norm)
@@ -135,7 +152,8 @@ class Case:
         # the five other roundings, all sources in one rollout each (candidates are independent rows)
         cat = np.ascontiguousarray(np.concatenate([self.acts[s] for s in SOURCES], axis=1))
         want = np.concatenate([self.states[s] for s in SOURCES], axis=1)
-        bar, spread = state_bar(self.w, self.norm, self.state, cat, want, f"S={S} A={A} {net} K={K} H={H}")
+        bar, spread = state_bar(self.w, self.norm, self.state, cat, want, f"S={S} A={A} {self.net} K={K} H={H}",
+                                check=check)
         self._bar = {s: bar[:, i * K:(i + 1) * K] for i, s in enumerate(SOURCES)}
         self._spread = {s: float(np.max(spread[:, i * K:(i + 1) * K])) for i, s in enumerate(SOURCES)}
         for d in (self.acts, self.costs, self.states, self._bar):

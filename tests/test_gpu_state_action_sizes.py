@@ -168,17 +168,24 @@ def check_states(c, src, got, label):
     return worst
 
 
-def run_case(kernel, net, S, A, K, H, monkeypatch):
+def sizes_line(kernel, ran, c, worst):
+    return f"[sizes-case] kernel={kernel} ran={ran} {c.net} S={c.S} A={c.A} K={c.K} H={c.H} worst={worst:.3f}"
+
+
+def run_case(kernel, c, monkeypatch, refusal=create_refusal, line=sizes_line):
+    """Checks 1 - 3 of the module docstring on one size_cases.Case.  ``refusal(kernel, c)``: the message of a stated
+    refusal of bcmpc_create; ``line``: the case's one line of output.  Returns (the kernel that ran, the worst
+    |dstate| / bar)."""
     from oracle import mpc_oracle as orc
     from test_gpu_parity import assert_costs_close
-    c = sc.case(S, A, net, K, H)
+    net, S, A, K, H = c.net, c.S, c.A, c.K, c.H
     label = f"{kernel} {net} S={S} A={A} K={K} H={H}"
     name = "auto" if kernel == "pp3" else kernel
     monkeypatch.delenv("BCMPC_SPLIT_PP", raising=False)
     if kernel == "pp3":
         monkeypatch.setenv("BCMPC_SPLIT_PP", "1")
     cost = "cheetah" if c.cheetah else "none"
-    refused = create_refusal(kernel, c)
+    refused = refusal(kernel, c)
     if refused:
         with pytest.raises(ValueError, match=refused):
             make_engine(c, kernel, cost)
@@ -228,7 +235,8 @@ def run_case(kernel, net, S, A, K, H, monkeypatch):
             if c.cheetah:
                 assert_costs_close(cem(eng, Padded(K, PAD)), c.costs["cem"], orc.near_threshold_mask(c.states["cem"]),
                                    f"{label} cem", env=envelope(c.ln, c.L, c.hidden, H))
-        print(f"[sizes-case] kernel={kernel} ran={info['kernel']} {net} S={S} A={A} K={K} H={H} worst={worst:.3f}")
+        print(line(kernel, info["kernel"], c, worst))
+        return info["kernel"], worst
     finally:
         eng.close()
         terms_eng.close()
@@ -241,20 +249,20 @@ KERNEL_NET = [(k, n) for k, nets in sc.KERNEL_NETS.items() for n in nets]
 @pytest.mark.parametrize("kernel,net", KERNEL_NET)
 @a_gpu_fault_stops_the_run
 def test_rollout_matches_oracle(kernel, net, shape, monkeypatch):
-    run_case(kernel, net, shape[0], shape[1], sc.K, sc.H, monkeypatch)
+    run_case(kernel, sc.case(shape[0], shape[1], net, sc.K, sc.H), monkeypatch)
 
 
 @pytest.mark.parametrize("shape", sc.SHAPES, ids=lambda v: f"S{v[0]}A{v[1]}")
 @a_gpu_fault_stops_the_run
 def test_pp3_partly_empty_second_group(shape, monkeypatch):
-    run_case("pp3", "2x500tanh", shape[0], shape[1], sc.K_PP, sc.H, monkeypatch)
+    run_case("pp3", sc.case(shape[0], shape[1], "2x500tanh", sc.K_PP, sc.H), monkeypatch)
 
 
 @pytest.mark.parametrize("shape", sc.TINY_SHAPES, ids=lambda v: f"S{v[0]}A{v[1]}")
 @pytest.mark.parametrize("kernel,net", KERNEL_NET)
 @a_gpu_fault_stops_the_run
 def test_one_candidate_one_step(kernel, net, shape, monkeypatch):
-    run_case(kernel, net, shape[0], shape[1], 1, 1, monkeypatch)
+    run_case(kernel, sc.case(shape[0], shape[1], net, 1, 1), monkeypatch)
 
 
 # ------------------------------------------------------------------ the guard against a vacuous comparison
@@ -302,24 +310,24 @@ REWARD_SHAPES = [(16, 1), (23, 9), (24, 8), (31, 1)]
 REWARD_ATOL, REWARD_RTOL, GAMMA = 1e-4, 1e-5, 0.95     # test_gpu_sweep.test_split_reward_shapes' bar
 
 
-def reward_case(S, A, ln, kernel, want_kernel=None):
+def reward_case(S, A, ln, kernel, want_kernel=None, hidden=500, K=sc.K, H=sc.H):
     from bc_mpc_amd.engine import MLPSpec, RolloutEngine
     from oracle import mpc_oracle as orc
     norm = sc.normalization(S, A, reward=True)
-    w = orc.synthetic_reward_weights(S, A, 500, ln)
+    w = orc.synthetic_reward_weights(S, A, hidden, ln)
     state = orc.synthetic_state(norm)
     low, high = sc.bounds(A)
-    eng = RolloutEngine(S, A, 500, 2, "tanh", ln, sc.H, sc.K, cost="reward", model="reward", kernel=kernel)
+    eng = RolloutEngine(S, A, hidden, 2, "tanh", ln, H, K, cost="reward", model="reward", kernel=kernel)
     try:
         assert eng.info()["kernel"] == (want_kernel or kernel), eng.info()
         eng.set_weights(MLPSpec(w.kernels, w.biases, "tanh", w.ln_gamma, w.ln_beta, model="reward"), norm, 1)
         eng.set_action_bounds(low, high)
         eng.set_discount(GAMMA)
         res = eng.get_action(state, None, seed=sc.SEED, cand_offset=sc.OFF, return_costs=True)
-        ap = orc.device_rng_actions(sc.SEED, sc.OFF, sc.K, sc.H, low, high)
+        ap = orc.device_rng_actions(sc.SEED, sc.OFF, K, H, low, high)
         want, _ = orc.reward_rollout(orc.NumpyRewardDynamics(w, norm), state, ap, GAMMA)
         d = np.abs(res.costs - want)
-        print(f"[sizes-reward] {kernel}{' LN' if ln else ''} S={S} A={A}: max|dr|={d.max():.2e} "
+        print(f"[sizes-reward] {kernel}{' LN' if ln else ''} hidden={hidden} S={S} A={A}: max|dr|={d.max():.2e} "
               f"(bar at the worst entry {float((REWARD_ATOL + REWARD_RTOL * np.abs(want))[np.argmax(d)]):.2e})")
         assert np.isfinite(res.costs).all()
         assert (d <= REWARD_ATOL + REWARD_RTOL * np.abs(want)).all()
@@ -361,24 +369,29 @@ def test_policy_stochastic_mode_every_step(shape, kernel):
     """test_gpu_parity.test_policy_stochastic_mode_pinned_every_step's method across shapes: at every step the
     rolled-out action is mean(s_h) + exp(logstd) z_h and s_{h+1} = predict(s_h, a_h), from the device's own s_h.
     Action j is output row S - 16 + j of the policy's one 16-row tile."""
+    policy_case(shape, kernel)
+
+
+def policy_case(shape, kernel, policy_layers=2, policy_hidden=128, K=sc.K, H=sc.H):
+    """``kernel``: "fp32" (the 2x256 relu net on the fp32 group kernel), else a kernel name for the 2x500 tanh net
+    ("auto": whatever the engine picks).  Returns the kernel that ran."""
     from bc_mpc_amd import _lib
     from bc_mpc_amd.engine import MLPSpec, PolicySpec, RolloutEngine
     from oracle import mpc_oracle as orc
     torch, dev = _t()
     S, A = shape
-    K, H = sc.K, sc.H
     if kernel == "fp32":
         w, kw = orc.synthetic_weights(S, A, 256, 2, "relu", False), dict(precision="fp32")
     else:
         w, kw = orc.synthetic_weights(S, A, 500, 2, "tanh", False), dict(kernel=kernel)
-    p = orc.synthetic_policy(S, A, 128, 2)
+    p = orc.synthetic_policy(S, A, policy_hidden, policy_layers)
     norm = sc.normalization(S, A)
     state = orc.synthetic_state(norm)
     dyn, pol = orc.NumpyDynamics(w, norm), orc.NumpyPolicy(p)
-    eng = RolloutEngine(S, A, w.hidden, 2, w.activation, False, H, K, policy_hidden=128, policy_layers=2,
-                        policy_mode="stochastic", **kw)
+    eng = RolloutEngine(S, A, w.hidden, 2, w.activation, False, H, K, policy_hidden=policy_hidden,
+                        policy_layers=policy_layers, policy_mode="stochastic", **kw)
     try:
-        if kernel != "fp32":
+        if kernel not in ("fp32", "auto"):
             assert eng.info()["kernel"] == kernel, eng.info()
         eng.set_weights(MLPSpec(w.kernels, w.biases, w.activation), norm, 1)
         eng.set_policy(PolicySpec(p.kernels, p.biases, p.ob_mean, p.ob_std, p.logstd), 0.5, 1)
@@ -404,10 +417,12 @@ def test_policy_stochastic_mode_every_step(shape, kernel):
             assert (ds <= 1e-6 * (1 + np.abs(nxt))).all(), (
                 f"step {h}: state off by {ds.max():.3e}, dims {sorted(set(np.argwhere(ds > 1e-6 * (1 + np.abs(nxt)))[:, 1].tolist()))}")
             worst_a, worst_s = max(worst_a, da.max()), max(worst_s, ds.max())
-        print(f"[sizes-policy] {kernel} S={S} A={A}: max|da|={worst_a:.2e} max|ds|={worst_s:.2e}")
+        print(f"[sizes-policy] {kernel} policy {policy_layers}x{policy_hidden} S={S} A={A}: max|da|={worst_a:.2e} "
+              f"max|ds|={worst_s:.2e}")
         raw = d_res.cpu().numpy()
         best = int(raw[:8].view(np.int64)[0]) - sc.OFF
         assert best == int(np.argmin(cs)) and np.array_equal(raw[16:16 + 8 * A].view(np.float64), acts[0, best])
+        return eng.info()["kernel"]
     finally:
         eng.close()
 
