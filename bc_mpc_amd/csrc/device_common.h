@@ -102,9 +102,13 @@ __device__ __forceinline__ float tanh_fast(float x) {
     return ax < 0.4f ? small : big;
 }
 
+// relu as the reference forms it (tf.nn.relu, np.maximum): a NaN stays a NaN, so that a candidate with a NaN input
+// costs NaN and wins the argmin.  fmaxf returns 0 for it.  IEEE-754 maximum: one v_maximum3_f32.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 template <int ACT>
 __device__ __forceinline__ float activate(float v) {
-    if constexpr (ACT == BCMPC_ACT_RELU) return fmaxf(v, 0.f);
+    if constexpr (ACT == BCMPC_ACT_RELU) return relu_nan(v);
     else return tanh_fast(v);
 }
 

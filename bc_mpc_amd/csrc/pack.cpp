@@ -60,6 +60,30 @@ float x3_scale(const float* W, size_t n) {
     return std::ldexp(1.0f, std::max(-100, std::min(100, 12 - e)));
 }
 
+std::vector<float> fold_layer0_rows(const float* W, int in, int out, int* row_exp) {
+    std::vector<float> Wf(W, W + (size_t)in * out);
+    std::vector<float> rmx(in, 0.f);
+    float mx = 0.f;
+    for (int k = 0; k < in; ++k) {
+        for (int n = 0; n < out; ++n) rmx[k] = std::max(rmx[k], std::fabs(W[(size_t)k * out + n]));
+        mx = std::max(mx, rmx[k]);
+    }
+    for (int k = 0; k < in; ++k) row_exp[k] = 0;
+    if (!(mx > 0.f) || !std::isfinite(mx)) return Wf;
+    int e = 0;
+    (void)std::frexp(mx, &e);
+    for (int k = 0; k < in; ++k) {
+        if (!(rmx[k] > 0.f)) continue;               // (an all-zero row, or one that holds a NaN: left as it is)
+        int ek = 0;
+        (void)std::frexp(rmx[k], &ek);
+        const int q = std::min(e - ek, kRowFoldMax);
+        if (q < kRowFoldMin) continue;
+        row_exp[k] = q;
+        for (int n = 0; n < out; ++n) Wf[(size_t)k * out + n] = std::ldexp(W[(size_t)k * out + n], q);
+    }
+    return Wf;
+}
+
 float ln_out_scale(const float* gamma, const float* beta, int h) {
     float gm = 0.f, bm = 0.f;
     for (int i = 0; i < h; ++i) {
@@ -89,8 +113,9 @@ void pack_split_reward(const EnginePlan& p, const bcmpc_weights& w, PackedNet* o
     const bcmpc_config& c = p.cfg;
     const int S = c.state_dim, A = c.action_dim, h = c.hidden, HP = p.HP, T = p.T, P = T / 2;
     const bool ln = c.layer_norm != 0;                // (team kernel only: plan_engine)
-    const float s0 = x3_scale(w.kernels[0], (size_t)(S + A) * h);
-    pack_x3_layer(w.kernels[0], S + A, h, 1, T, p.pack_tb, s0, halves(o, p.w_off[0]));
+    const std::vector<float> w0 = fold_layer0_rows(w.kernels[0], S + A, h, o->row_exp);
+    const float s0 = x3_scale(w0.data(), (size_t)(S + A) * h);
+    pack_x3_layer(w0.data(), S + A, h, 1, T, p.pack_tb, s0, halves(o, p.w_off[0]));
     o->winv[0] = 1.0f / s0;
     // the heads' input: the trunk's tanh x 2^12, or its LayerNorm output x hsc[0] (|LN(x)_i| <=
     // sqrt(h) |gamma_i| + |beta_i|, the power of two that keeps it below 2^12)
@@ -187,11 +212,12 @@ void pack_split_delta(const EnginePlan& p, const bcmpc_weights& w, PackedNet* o)
         fold = std::isfinite(mx) && mx * kTanhKh < 16384.0f;
     }
     o->pp_fold_w = fold;
+    const std::vector<float> w0 = fold_layer0_rows(w.kernels[0], S + A, h, o->row_exp);
     for (int l = 0; l <= L; ++l) {
         const int in = l == 0 ? S + A : h, out = l == L ? S : h;
-        const float sw = fold && l < L ? kTanhKh : x3_scale(w.kernels[l], (size_t)in * out);
+        const float sw = fold && l < L ? kTanhKh : x3_scale(l == 0 ? w0.data() : w.kernels[l], (size_t)in * out);
         // (team kernel: layer 0 in pack_tb = team_layer0_tiles per wave, hidden layers in head_tb = team_layer1_tiles)
-        if (l == 0) pack_x3_layer(w.kernels[0], in, out, 1, T, p.pack_tb, sw, halves(o, p.w_off[0]));
+        if (l == 0) pack_x3_layer(w0.data(), in, out, 1, T, p.pack_tb, sw, halves(o, p.w_off[0]));
         else if (l < L) pack_x3_layer(w.kernels[l], in, out, P, T, p.head_tb, sw, halves(o, p.w_off[l]));
         else pack_x3_layer(w.kernels[L], in, out, P, 2, 2, sw, halves(o, p.w_off[L]));
         // layer 0's input scale is per candidate (kernel); hidden inputs are tanh * 2^12, an LN
@@ -277,6 +303,9 @@ void pack_weights(const EnginePlan& p, const bcmpc_weights& w, PackedNet* out) {
         C[3 * 32 + i] = i < A ? w.std_action[i] + 1e-10 : 1.0;    // dynamics.py:110
         C[4 * 32 + i] = i < S ? w.mean_deltas[i] : 0.0;
         C[5 * 32 + i] = i < S ? w.std_deltas[i] : 0.0;
+        // a layer-0 row's power of two moved out of the packed kernel (fold_layer0_rows) divides its input instead
+        if (i < S) C[1 * 32 + i] = std::ldexp(C[1 * 32 + i], out->row_exp[i]);
+        if (i < A) C[3 * 32 + i] = std::ldexp(C[3 * 32 + i], out->row_exp[S + i]);
         C[8 * 32 + i] = 1.0 / C[1 * 32 + i];
         C[9 * 32 + i] = 1.0 / C[3 * 32 + i];
     }

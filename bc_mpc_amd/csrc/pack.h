@@ -26,6 +26,15 @@ void pack_out_rows(const float* W, int in, int out, int Tin, const int* rowmap, 
 void pack_x3_layer(const float* W, int in, int out, int Pin, int Tout, int TWp, float sw, _Float16* dst);
 // power of two s with max|W| * s in [2^11, 2^12) (1 for an all-zero kernel)
 float x3_scale(const float* W, size_t n);
+// Layer 0's row k multiplies input dimension k alone, so a power of two moves freely between the two: (x 2^-q)(w 2^q)
+// is the same f32 product.  The split kernels scale a whole kernel by one power of two, which leaves a row that sits
+// 2^-p below the kernel's largest entry with a subnormal lo half from p ~ 15 and no hi half from p ~ 26 -- the row of
+// a near-constant observation (std_obs ~ 0), whose normalised input is as many binades above the others.  A row
+// kRowFoldMin binades or more below the largest entry is therefore returned lifted into the largest entry's binade
+// (row_exp[k] = q, at most kRowFoldMax), and pack_weights multiplies that dimension's normalisation divisor by 2^q.
+// Rows nearer than that keep 22 bits or more as they are, and an ordinary net packs bit for bit as before.
+constexpr int kRowFoldMin = 8, kRowFoldMax = 120;
+std::vector<float> fold_layer0_rows(const float* W, int in, int out, int* row_exp);
 // the scale of a LayerNorm output as the next layer's f16 operand: |LN(x)_i| <= sqrt(h) |gamma_i| + |beta_i|,
 // and the power of two that keeps it below 2^12
 float ln_out_scale(const float* gamma, const float* beta, int h);
@@ -35,6 +44,7 @@ struct PackedNet {                              // bcmpc_set_weights
     double consts[kConstRows * kConstCols]{};   // rows 0..5 and 8, 9 of the consts block (6, 7: the action bounds)
     float winv[BCMPC_MAX_LAYERS + 1]{};         // split kernel: 1 / operand scales per layer
     float hsc[BCMPC_MAX_LAYERS]{};              // split LN nets: output scale of hidden layer l
+    int row_exp[kConstCols]{};                  // split kernels: fold_layer0_rows' power of two per input dimension
     bool pp_fold_w = false;                     // rollout_pp's folded operands hold for these weights
     bool team_defer = false;                    // packed for rollout_team's deferred last LayerNorm
     double mean_reward = 0.0, std_reward = 0.0;

@@ -222,7 +222,7 @@ __device__ __forceinline__ void epi_cols(f4 (&acc)[NTL], float f, const float* _
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float z = fmaf(acc[j][r], f, b[r]);
-            acc[j][r] = RELU ? fmaxf(z, 0.f) : tanh4096(z);              // pad rows: exactly 0
+            acc[j][r] = RELU ? relu_nan(z) : tanh4096(z);                // pad rows: exactly 0
         }
     }
     const int nwr = min(max(hidden - 16 * NTL * x, 0), 16 * NTL);      // this wave's valid rows

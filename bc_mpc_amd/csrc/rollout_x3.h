@@ -247,7 +247,7 @@ __device__ __forceinline__ void epi_colx(f4 (&acc)[TW][NC], const float (&f)[NC]
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float z = fmaf(acc[j][c][r], f[c], b[r]);
-                acc[j][c][r] = RELU ? fmaxf(z, 0.f) : tanh_x4096(z);     // pad rows: exactly 0
+                acc[j][c][r] = RELU ? relu_nan(z) : tanh_x4096(z);       // pad rows: exactly 0
             }
     }
     const int nwr = min(max(hidden - 16 * TW * w, 0), 16 * TW);        // this wave's valid rows

@@ -113,13 +113,17 @@ def state_bar(w, norm, state, acts, want, label="", check=True):
     return bar, spread / base
 
 
-def action_sources(A, K, H):
-    """{source: [H, K, A] f64 actions}, the CEM plan (mu, sigma)."""
+def action_sources(A, K, H, low=None, high=None, plan=None):
+    """{source: [H, K, A] f64 actions}, the CEM plan (mu, sigma).  ``low``, ``high``: other bounds than bounds(A);
+    ``plan``: a function (mu, sigma) -> (mu, sigma) applied to the plan drawn here (range_cases.py)."""
     from oracle import mpc_oracle as orc
-    low, high = bounds(A)
+    if low is None:
+        low, high = bounds(A)
     rs = np.random.RandomState(1000 * K + 10 * H + A)
     mu, sd = rs.uniform(-0.4, 0.6, (H, A)), rs.uniform(0.1, 2.0, (H, A))
     sd[0, 0] = sd[-1, -1] = 2.0
+    if plan is not None:
+        mu, sd = plan(mu, sd)
     acts = {"explicit": rs.uniform(low, high, (H, K, A)),
             "philox": orc.device_rng_actions(SEED, OFF, K, H, low, high),
             "cem": orc.cem_actions(SEED, CEM_IT, OFF, K, H, mu, sd, low, high)}
@@ -129,17 +133,23 @@ def action_sources(A, K, H):
 class Case:
     """One (S, A, net, K, H): inputs, the oracle's states and costs per action source, and the per-entry bar.
     ``net``: a name of NETS or a spec tuple (net_spec); ``self.net`` is its name either way.  ``check=False``
-    builds the case even where its widened bar passes the cap (state_bar), for measuring a net before it is taken."""
+    builds the case even where its widened bar passes the cap (state_bar), for measuring a net before it is taken.
+    ``given``: inputs that stand in for the ones built here (range_cases.py) -- a dict with any of ``w``, ``norm``,
+    ``state``, ``low`` and ``high``, ``plan`` (action_sources) and ``explicit``, a function of the explicit action
+    array that returns the one to use.  References, bar and cap are computed from whatever inputs result."""
 
-    def __init__(self, S, A, net, K, H, check=True):
+    def __init__(self, S, A, net, K, H, check=True, given=None):
         from oracle import mpc_oracle as orc
+        given = given or {}
         self.S, self.A, self.net, self.K, self.H = S, A, net_name(net), K, H
         self.hidden, self.L, self.act, self.ln = net_spec(net)[:4]
-        self.w = weights(S, A, net)
-        self.norm = normalization(S, A)
-        self.state = orc.synthetic_state(self.norm)
-        self.low, self.high = bounds(A)
-        self.acts, self.mu, self.sd = action_sources(A, K, H)
+        self.w = given["w"] if "w" in given else weights(S, A, net)
+        self.norm = given["norm"] if "norm" in given else normalization(S, A)
+        self.state = np.array(given["state"], dtype=np.float64) if "state" in given else orc.synthetic_state(self.norm)
+        self.low, self.high = (given["low"], given["high"]) if "low" in given else bounds(A)
+        self.acts, self.mu, self.sd = action_sources(A, K, H, self.low, self.high, given.get("plan"))
+        if "explicit" in given:
+            self.acts["explicit"] = np.ascontiguousarray(given["explicit"](self.acts["explicit"]))
         if K >= 64:
             c = self.acts["cem"]
             assert (c == self.high).any() and (c == self.low).any(), "the CEM samples do not clip at both bounds"

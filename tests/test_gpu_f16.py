@@ -60,7 +60,8 @@ def _check(got, want, near, H, label):
     if near is not None:
         flip = np.abs(diff - 10.0 * np.round(diff / 10.0)) <= tol
         bad &= ~(near[ok] & flip)
-    worst = float(diff[~(near[ok] if near is not None else np.zeros_like(bad))].max()) if diff.size else 0.0
+    far = diff[~(near[ok] if near is not None else np.zeros_like(bad))]     # (empty where every candidate is near)
+    worst = float(far.max()) if far.size else 0.0
     print(f"[f16 {label}] max|dcost|={worst:.3e} per-step={worst / H:.3e} n={int(ok.sum())} "
           f"over_tol={int(bad.sum())}")
     assert not bad.any(), f"{label}: {int(bad.sum())} costs beyond {tol}"
