@@ -196,6 +196,15 @@ class Proposals(ctypes.Structure):
     ]
 
 
+class Knots(ctypes.Structure):
+    """bcmpc_knots (8 bytes): ``count`` knots per action dimension interpolated to the horizon (bc_mpc_amd/knots.py);
+    ``kind`` indexes ``knots.KINDS`` (hold, linear, cubic); count 0 is off."""
+    _fields_ = [
+        ("count", ctypes.c_int32),
+        ("kind", ctypes.c_int32),
+    ]
+
+
 class MppiStats(ctypes.Structure):
     """One MPPI update's statistics (bcmpc_mppi_stats); no valid candidate: 0, 0, NaN, 0."""
     _fields_ = [
@@ -391,6 +400,42 @@ SIGNATURES = [
     ("bcmpc_rollout_policy_batch_async", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_cem_get_action_k", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.POINTER(Proposals),
+      ctypes.POINTER(Knots), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result)]),
+    ("bcmpc_mppi_get_action_k", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt),
+      ctypes.POINTER(Proposals), ctypes.POINTER(Knots), ctypes.c_uint64, _DP, _DP, ctypes.POINTER(Result),
+      ctypes.POINTER(MppiStats)]),
+    ("bcmpc_cem_get_actions_batch_k", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Cem), ctypes.POINTER(Sampling), ctypes.POINTER(Proposals),
+      ctypes.POINTER(Knots), ctypes.c_uint64, ctypes.c_int64, _DP, _DP, ctypes.POINTER(Result), _DP]),
+    ("bcmpc_mppi_get_actions_batch_k", ctypes.c_int,
+     [ctypes.c_void_p, _DP, ctypes.c_int32, ctypes.POINTER(Mppi), ctypes.POINTER(Sampling), ctypes.POINTER(MppiExt),
+      ctypes.POINTER(Proposals), ctypes.POINTER(Knots), ctypes.c_uint64, ctypes.c_int64, _DP, _DP,
+      ctypes.POINTER(Result), ctypes.POINTER(MppiStats), _DP]),
+    ("bcmpc_plan_sample_knots_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("bcmpc_cem_refit_batch_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+      ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_mppi_update_batch_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
+      ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_plan_keep_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+      ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_mppi_control_cost_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    ("bcmpc_mppi_sigma_update_steps_async", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+      ctypes.c_void_p]),
     ("bcmpc_ensemble_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     ("bcmpc_ensemble_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("bcmpc_ensemble_size", ctypes.c_int, [ctypes.c_void_p]),

@@ -49,7 +49,12 @@ class CEMcontroller(Planner):
     DESIGN.md 9j; both are read on every call, one rank and one dynamics model only).  ``proposals=`` on a call
     and ``policy_prior`` / ``policy_paths`` / ``policy_stochastic`` / ``policy_explore``: given action sequences, and
     a policy net's closed-loop rollouts, in the last candidates of every iteration (proposals.py; one
-    rank and one dynamics model only); ``last_proposal_costs`` / ``last_best_from_proposal`` report on them."""
+    rank and one dynamics model only); ``last_proposal_costs`` / ``last_best_from_proposal`` report on them.
+    ``knots`` (M in ``[1, horizon]``) / ``knot_interp`` (``"hold" | "linear" | "cubic"``): the plan is sampled at M
+    knots and interpolated to the horizon (knots.py; read on every call, one rank and one dynamics
+    model only, not with proposals or a policy prior).  ``last_mu`` / ``last_sigma`` and the warm start are then in
+    KNOT space, ``[M, A]`` (batched ``[B, M, A]``); ``last_plan`` is the ``[H, A]`` sequence ``last_mu`` expands to
+    (without knots it equals ``last_mu``)."""
     _KIND = "CEM"
 
     def __init__(self,
@@ -76,12 +81,15 @@ class CEMcontroller(Planner):
                  policy_prior=None,
                  policy_paths: int = 0,
                  policy_stochastic: bool = True,
-                 policy_explore: float = 0.0):
+                 policy_explore: float = 0.0,
+                 knots: Optional[int] = None,
+                 knot_interp: str = "linear"):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0xCE5EED if seed is None else seed, device, process_group,
                          terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho,
                          keep_elites=keep_elites, policy_prior=policy_prior, policy_paths=policy_paths,
-                         policy_stochastic=policy_stochastic, policy_explore=policy_explore)
+                         policy_stochastic=policy_stochastic, policy_explore=policy_explore, knots=knots,
+                         knot_interp=knot_interp)
         self.elite_frac = float(elite_frac)
         self._n_elite = n_elite
         self.alpha = float(alpha)
@@ -95,7 +103,7 @@ class CEMcontroller(Planner):
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_action(state, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed,
-                                         **self._sampling_args())
+                                         **self._sampling_args(), **self._knot_args())
         self._note_planner_value(eng, res.best_index, K)
         return self._publish(res.best_cost, res.best_index, res.first_action, mu, sd)
 
@@ -133,7 +141,7 @@ class CEMcontroller(Planner):
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, sd = eng.cem_get_actions(states, mu0, sd0, self.iterations, min(self.n_elite, K), self.alpha, seed,
-                                          **self._sampling_args())
+                                          **self._sampling_args(), **self._knot_args())
         self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu, self.last_sigma = mu, sd

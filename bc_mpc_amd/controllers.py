@@ -44,6 +44,7 @@ import numpy as np
 
 from . import _lib
 from . import distributed as _dist
+from . import knots as _knots
 from . import policy as _policy
 from . import proposals as _proposals
 from . import sampling as _sampling
@@ -329,6 +330,18 @@ class Planner(_TerminalValue, Controller):
     # what is sampled (sampling.py): read on every call, never an engine constructor argument
     noise_rho = 0.0
     keep_elites = False
+    # knot plans (knots.py): ``knots`` = M in [1, horizon] samples the plan at M knots and interpolates it
+    # (``knot_interp``: "hold" | "linear" | "cubic"); None: off.  Read on every call, like noise_rho.  With knots
+    # the plans -- last_mu, last_sigma, the warm start -- are in KNOT space, [M, A]; last_plan is the [H, A] view
+    knots = None
+    knot_interp = "linear"
+    _plan_view = None       # what last_plan returns
+
+    @property
+    def last_plan(self):
+        """``knots.expand_plan(last_mu)`` of the last call, ``[H, A]`` / ``[B, H, A]``; without knots it is
+        ``last_mu``.  (A property: the instance's ``last_*`` attributes are what they were before knots.)"""
+        return self._plan_view
 
     # proposals (proposals.py): a policy net rolled through the model gives every call's last candidates
     policy_prior = None
@@ -340,11 +353,14 @@ class Planner(_TerminalValue, Controller):
 
     def __init__(self, env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                  warm_start, seed, device, process_group, terminal_value=None, terminal_weight=-1.0, noise_rho=0.0,
-                 keep_elites=False, policy_prior=None, policy_paths=0, policy_stochastic=True, policy_explore=0.0):
+                 keep_elites=False, policy_prior=None, policy_paths=0, policy_stochastic=True, policy_explore=0.0,
+                 knots=None, knot_interp="linear"):
         self._init_terminal_value(terminal_value, terminal_weight)
         self._init_policy_prior(policy_prior, policy_paths, policy_stochastic, policy_explore)
         self.noise_rho = _sampling.check_rho(noise_rho)
         self.keep_elites = _sampling.check_keep_elites(keep_elites)
+        self.knots = _knots.check_knots(knots, horizon)
+        self.knot_interp = _knots.check_interp(knot_interp)
         self.env = env
         self.dyn_model = dyn_model
         self.horizon = horizon
@@ -361,8 +377,8 @@ class Planner(_TerminalValue, Controller):
         self._group = process_group
         self._engine: Optional[RolloutEngine] = None
         self._batch_engine: Optional[RolloutEngine] = None
-        self._mu = None         # [H, A]: get_action's last plan
-        self._bmu = None        # [B, H, A]: the last batched call's plans
+        self._mu = None         # [H, A] ([M, A] with knots): get_action's last plan
+        self._bmu = None        # [B, H, A] ([B, M, A]): the last batched call's plans
         self._bkeep = None      # [B] bool: plan b is shifted and reused (False after reset([b]))
         self.last_mu = None
         self.last_cost = None
@@ -398,6 +414,14 @@ class Planner(_TerminalValue, Controller):
         H = int(self.horizon)
         mid = (low + high) / 2.0
         sd = np.full_like(low, self.init_std) if self.init_std is not None else (high - low) / 4.0
+        kn = self._knot_args()
+        if kn:              # a knot plan [M, A]: the previous plan's interpolant one step later (knots.shift_plan)
+            M = kn["knots"]
+            if self.warm_start and self._mu is not None and self._mu.shape == (M, low.shape[0]):
+                mu = _knots.shift_plan(self._mu, H, kn["knot_interp"], mid)
+            else:
+                mu = np.tile(mid, (M, 1))
+            return mu, np.tile(sd, (M, 1))
         if self.warm_start and self._mu is not None and self._mu.shape == (H, low.shape[0]):
             mu = np.vstack([self._mu[1:], mid[None]])
         else:
@@ -412,6 +436,14 @@ class Planner(_TerminalValue, Controller):
         H, B = int(self.horizon), int(n_envs)
         mid = (low + high) / 2.0
         sd = np.full_like(low, self.init_std) if self.init_std is not None else (high - low) / 4.0
+        kn = self._knot_args()
+        if kn:              # knot plans [B, M, A], each shifted by knots.shift_plan
+            M = kn["knots"]
+            mu = np.tile(mid, (B, M, 1))
+            if self.warm_start and self._bmu is not None and self._bmu.shape == mu.shape:
+                for b in np.flatnonzero(self._bkeep):
+                    mu[b] = _knots.shift_plan(self._bmu[b], H, kn["knot_interp"], mid)
+            return mu, np.tile(sd, (B, M, 1))
         mu = np.tile(mid, (B, H, 1))
         if self.warm_start and self._bmu is not None and self._bmu.shape == mu.shape:
             mu[self._bkeep, :-1] = self._bmu[self._bkeep, 1:]
@@ -461,6 +493,29 @@ class Planner(_TerminalValue, Controller):
         """Correlated noise and elite carry-over run on one engine of one rank; raised before a seed is drawn."""
         if self._sampling_args():
             raise NotImplementedError(f"{self._KIND}controller: noise_rho / keep_elites are not built {where}")
+
+    # ------------------------------------------------------------------ knot plans (knots.py, DESIGN.md 9n)
+    def _knot_args(self) -> dict:
+        """The engine calls' ``knots`` / ``knot_interp``, passed only with knots on (the call with ``knots=None`` is
+        the call it has always been); ValueError for a count outside ``[1, horizon]`` or an unknown kind."""
+        M, kind = _knots.check_knots(self.knots, self.horizon), _knots.check_interp(self.knot_interp)
+        return {} if M is None else {"knots": M, "knot_interp": kind}
+
+    def _refuse_knots(self, where: str) -> None:
+        """Knot plans run on one engine of one rank, without proposals; raised before a seed is drawn."""
+        if self._knot_args():
+            raise NotImplementedError(f"{self._KIND}controller: knots are not built {where}")
+
+    def _publish_plan(self) -> None:
+        """``last_plan``: the ``[H, A]`` / ``[B, H, A]`` view of ``last_mu`` (with knots: its expansion, clipped)."""
+        kn = self._knot_args()
+        mu = self.last_mu
+        if not kn or mu is None:
+            self._plan_view = mu
+            return
+        low, high = self._bounds()
+        one = lambda m: _knots.expand_plan(m, int(self.horizon), kn["knot_interp"], low, high)   # noqa: E731
+        self._plan_view = one(mu) if np.ndim(mu) == 2 else np.stack([one(m) for m in mu])
 
     # ------------------------------------------------------------------ proposals (proposals.py, DESIGN.md 9m)
     def _init_policy_prior(self, policy_prior, policy_paths, policy_stochastic, policy_explore) -> None:
@@ -618,18 +673,28 @@ class Planner(_TerminalValue, Controller):
         """``reference`` (``[R]`` or ``[H, R]``) and ``previous_action`` (``[A]``): the inputs of a ``TermCost``
         with ``ref(c)`` values / ``rate`` terms (cost_functions.py), explicit on every call.  ``proposals``
         (``[P, H, A]``): action sequences that sit, clipped to the box, in the last P candidates of every
-        iteration (proposals.py); with a ``policy_prior`` the policy's ``policy_paths`` rollouts follow them."""
+        iteration (proposals.py); with a ``policy_prior`` the policy's ``policy_paths`` rollouts follow them.
+        With ``knots`` the plan is sampled at M knots (knots.py): ``last_mu`` / ``last_sigma`` are ``[M, A]`` and
+        ``last_plan`` is the ``[H, A]`` sequence they expand to."""
+        action = self._get_action(state, reference, previous_action, proposals)
+        self._publish_plan()
+        return action
+
+    def _get_action(self, state, reference, previous_action, proposals):
         self._inputs = _cost_inputs(self, reference, previous_action, False)
         S, A, K = _shape(self)
         if K == 0:
             raise ValueError("attempt to get argmin of an empty sequence")
         user = self._user_proposals(proposals, A, None)
         self._forget_proposal_report()
+        if self._knot_args():
+            self._refuse_proposals(user, "together with knots (a given sequence has no knot representation)")
         if getattr(self.dyn_model, "is_ensemble", False):
             # an EnsembleDynamicsModel (ensemble.py): its engine has RolloutEngine's planner calls, scored on the
             # members' combined value; it refuses ranks, costs and members itself, before anything is drawn
             from . import ensemble as _ensemble
             self._refuse_sampling("over an EnsembleDynamicsModel")
+            self._refuse_knots("over an EnsembleDynamicsModel")
             self._refuse_proposals(user, "over an EnsembleDynamicsModel")
             state = np.asarray(state, dtype=np.float64).reshape(-1)
             eng = _ensemble._ctrl_engine(self, S, A, K, "single")
@@ -639,6 +704,7 @@ class Planner(_TerminalValue, Controller):
         if ws > 1:
             self._refuse_ranks(ws)
             self._refuse_sampling(f"for more than one rank (world size {ws})")
+            self._refuse_knots(f"for more than one rank (world size {ws})")
             self._refuse_proposals(user, f"for more than one rank (world size {ws})")
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         spec, norm, version, terms = self._model(S, A)
@@ -666,7 +732,13 @@ class Planner(_TerminalValue, Controller):
         rank only.  ``reference`` (``[B, R]`` or ``[B, H, R]``) and ``previous_action`` (``[B, A]``): every
         environment's inputs of a ``TermCost`` with ``ref(c)`` values / ``rate`` terms.  ``proposals``
         (``[B, P, H, A]``): every environment's own sequences, as in ``get_action``; a ``policy_prior`` is rolled
-        out from every environment's state (``B * policy_paths`` rollouts in one launch)."""
+        out from every environment's state (``B * policy_paths`` rollouts in one launch).  With ``knots``:
+        ``last_mu`` ``[B, M, A]``, ``last_plan`` ``[B, H, A]``."""
+        actions = self._get_actions(states, reference, previous_action, proposals)
+        self._publish_plan()
+        return actions
+
+    def _get_actions(self, states, reference, previous_action, proposals):
         if getattr(self.dyn_model, "is_ensemble", False):
             raise NotImplementedError(f"batched {self._KIND} over an EnsembleDynamicsModel is not built yet: "
                                       "use get_action")
@@ -679,6 +751,8 @@ class Planner(_TerminalValue, Controller):
         B = states.shape[0]
         user = self._user_proposals(proposals, A, B)
         self._forget_proposal_report()
+        if self._knot_args():
+            self._refuse_proposals(user, "together with knots (a given sequence has no knot representation)")
         spec, norm, version, terms = self._model(S, A)
         prior_args = ("prior_batch", spec, norm, version, S, A, B, user, K)
         peng = self._prior_engine(*prior_args)

@@ -175,7 +175,7 @@ int bcmpc_destroy(bcmpc_engine* e) {
                     (void*)e->d_mt_polys, (void*)e->d_mt_chunks, (void*)e->d_mt_part, (void*)e->d_tiled,
                     (void*)e->d_bstates, (void*)e->d_bresults, (void*)e->d_bmu, (void*)e->d_bsigma, (void*)e->d_bcount,
                     (void*)e->d_bstats, (void*)e->d_belite, (void*)e->d_keep, (void*)e->d_keep_count, (void*)e->d_prop,
-                    (void*)e->d_tc_traj,
+                    (void*)e->d_knots, (void*)e->d_tc_traj,
                     (void*)e->d_vw, (void*)e->d_vparams, (void*)e->d_vvalues, (void*)e->d_tc_steps,
                     (void*)e->d_tc_ref, (void*)e->d_tc_prev})
         if (p) (void)hipFree(p);

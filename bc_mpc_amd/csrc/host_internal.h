@@ -100,6 +100,8 @@ struct bcmpc_engine : bcmpc::host::EnginePlan {   // (the plan: config, kernel, 
     int32_t* d_keep_count = nullptr; int32_t keep_count_cap = 0;
     // proposals (plan_prop.hip): a synchronous call's host sequences [n_envs][P][H][A], uploaded with the plans
     double* d_prop = nullptr; size_t prop_cap = 0;
+    // knot plans (plan_knots.hip): a synchronous call's clipped knot values [M][num_paths][A]; it only grows
+    double* d_knots = nullptr; size_t knots_cap = 0;
     // policy engines' batched rollout (bcmpc_rollout_policy_batch_async) tiles its states into d_tiled, above
     // team kernel (rollout_team.hip): exchange granules, {ticket, generation}, mapped timeout flag
     unsigned long long* d_team = nullptr;

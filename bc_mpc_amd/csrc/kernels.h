@@ -340,6 +340,14 @@ struct PlanSamplePropArgs {                  // plan_sample_corr, then column K 
 };
 hipError_t launch_plan_sample_prop(const PlanSamplePropArgs& a, hipStream_t st);
 
+// ---- knot plans: M <= H sampled knots per column, interpolated to H steps (plan_knots.hip; bc_mpc_amd/knots.py) ----
+struct PlanSampleKnotsArgs {                 // s: plan_sample_corr's block with mu / sigma [n_envs][M][A], keep
+    PlanSampleCorrArgs s;                    //   [n_envs][n_elite][M][A]; s.H the horizon, s.out the actions [H][Ktot][A]
+    double* knots;                           // [M][Ktot][A] the clipped knot values (what refit / update / keep read)
+    int32_t M, kind;                         // 1 <= M <= H; bcmpc_knots.kind
+};
+hipError_t launch_plan_sample_knots(const PlanSampleKnotsArgs& a, hipStream_t st);
+
 // ---- MPPI's control-cost term and weighted sigma update (mppi_ext.hip; bc_mpc_amd/mppi_update.py) ----
 // Both read the iteration's stored actions [H][n_envs * K][A]; environment b: costs / scores / out + b K,
 // mu / sigma / mu_new + b H A.

@@ -176,6 +176,21 @@ static int proposals_check(const bcmpc_proposals* q, const bcmpc_engine* e, int3
     return prop_strides_check(n_envs, q->count, H, A, q->env_stride, q->seq_stride, q->step_stride);
 }
 
+// Knot plans (bcmpc_knots; nullptr or count == 0: off -- the plans are [H][A] and every step is sampled)
+static bool knots_none(const bcmpc_knots* k) { return !k || k->count == 0; }
+static int knots_check(int32_t count, int32_t kind, int32_t horizon) {
+    if (count < 1 || count > horizon)
+        return fail(BCMPC_ERR_ARG, "knots: count must be in [1, horizon = " + std::to_string(horizon) + "]");
+    if (kind < BCMPC_KNOTS_HOLD || kind > BCMPC_KNOTS_CUBIC)
+        return fail(BCMPC_ERR_ARG, "knots: kind must be 0 (hold), 1 (linear) or 2 (cubic)");
+    return BCMPC_OK;
+}
+static int steps_check(int32_t steps, int32_t horizon) {
+    if (steps < 1 || steps > horizon)
+        return fail(BCMPC_ERR_ARG, "steps must be in [1, horizon = " + std::to_string(horizon) + "]");
+    return BCMPC_OK;
+}
+
 // a synchronous planner call's input plans, kept on a team engine for the rerun after a give-up: n doubles of
 // mu, and of sigma where the call writes it back (CEM)
 struct PlanInputs {
@@ -285,13 +300,31 @@ static int plan_sample_prop_impl(bcmpc_engine* e, const double* d_mu, const doub
     return BCMPC_OK;
 }
 
+// ... in knot space (plan_knots.hip): the plans [n_envs][M][A], d_keep [n_envs][n_elite][M][A]; the clipped knots
+// into d_knots [M][n_envs * K][A], their expansion into d_actions [H][n_envs * K][A]
+static int plan_sample_knots_impl(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                  uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                  const int32_t* d_keep_count, int32_t n_elite, int32_t M, int32_t kind, double* d_knots,
+                                  double* d_actions, hipStream_t st) {
+    PlanSampleKnotsArgs p{};
+    PlanSampleCorrArgs& a = p.s;
+    a.mu = d_mu; a.sigma = d_sigma; a.consts = e->d_consts; a.out = d_actions;
+    a.keep = d_keep; a.keep_count = d_keep_count;
+    a.seed = seed; a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
+    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim; a.n_elite = n_elite;
+    a.rho = rho; a.c = std::sqrt(1.0 - rho * rho);
+    p.knots = d_knots; p.M = M; p.kind = kind;
+    HIP_TRY(launch_plan_sample_knots(p, st));
+    return BCMPC_OK;
+}
+
 static int plan_keep_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, const double* d_actions,
                           int32_t n_envs, int64_t K, int64_t cand_offset, int32_t n_elite, double* d_keep,
-                          int32_t* d_keep_count, hipStream_t st) {
+                          int32_t* d_keep_count, hipStream_t st, int32_t steps = 0) {
     PlanKeepArgs a{};
     a.elite = d_elite; a.count = d_count; a.actions = d_actions; a.keep = d_keep; a.keep_count = d_keep_count;
     a.cand_offset = cand_offset; a.K = K; a.Ktot = K * n_envs;
-    a.n_envs = n_envs; a.n_elite = n_elite; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.n_envs = n_envs; a.n_elite = n_elite; a.H = steps ? steps : e->cfg.horizon; a.A = e->cfg.action_dim;
     HIP_TRY(launch_plan_keep(a, st));
     return BCMPC_OK;
 }
@@ -320,10 +353,11 @@ static int select_batch_impl(bcmpc_engine* e, const double* d_costs, int32_t n_e
 // d_actions (optional): the iteration's stored actions [H][n_envs * K][A], column 0 = candidate cand_offset
 static int refit_batch_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count, int32_t n_envs,
                             int32_t n_elite, uint64_t seed, int32_t iteration, double alpha, double* d_mu,
-                            double* d_sigma, const double* d_actions, int64_t K, int64_t cand_offset, hipStream_t st) {
+                            double* d_sigma, const double* d_actions, int64_t K, int64_t cand_offset, hipStream_t st,
+                            int32_t steps = 0) {
     RefitBatchArgs a{};
     a.one.elite = d_elite; a.one.count = d_count; a.one.mu = d_mu; a.one.sigma = d_sigma; a.one.consts = e->d_consts;
-    a.one.seed = seed; a.one.iter = iteration; a.one.H = e->cfg.horizon; a.one.A = e->cfg.action_dim;
+    a.one.seed = seed; a.one.iter = iteration; a.one.H = steps ? steps : e->cfg.horizon; a.one.A = e->cfg.action_dim;
     a.one.alpha = alpha;
     a.one.actions = d_actions; a.one.act_cols = d_actions ? K * n_envs : 0; a.one.act_g0 = cand_offset;
     a.n_envs = n_envs; a.n_elite = n_elite;
@@ -334,11 +368,11 @@ static int refit_batch_impl(bcmpc_engine* e, const bcmpc_elite* d_elite, const i
 static int mppi_update_batch_impl(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K,
                                   int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda, double* d_mu,
                                   const double* d_sigma, bcmpc_mppi_stats* d_stats, const double* d_actions,
-                                  hipStream_t st) {
+                                  hipStream_t st, int32_t steps = 0) {
     if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
     const int64_t parts = mppi_parts(K);
     if (parts * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one update");
-    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+    const int32_t H = steps ? steps : e->cfg.horizon, ha = H * e->cfg.action_dim;
     const size_t need = mppi_batch_scratch(K, n_envs, ha);
     if (need > e->mppi_cap) {
         if (e->d_mppi) (void)hipFree(e->d_mppi);
@@ -355,7 +389,7 @@ static int mppi_update_batch_impl(bcmpc_engine* e, const double* d_costs, int32_
     a.part = e->d_mppi + 2 * (size_t)n_envs * kMppiMinParts;
     a.stats = d_stats;
     a.seed = seed; a.m = K; a.cand_offset = cand_offset; a.nparts = parts;
-    a.iter = iteration; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.iter = iteration; a.H = H; a.A = e->cfg.action_dim;
     a.cpl = mppi_cpl(K); a.nmin = mppi_min_blocks(K);          // (the workgroup size rule follows K, not n_envs * K)
     a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
     a.lambda = lambda;
@@ -368,15 +402,15 @@ static int mppi_update_batch_impl(bcmpc_engine* e, const double* d_costs, int32_
 // c~ = costs +- weight q into d_scores (mppi_ext.hip): the plans are the ones the actions were sampled from
 static int control_cost_impl(bcmpc_engine* e, const double* d_costs, const double* d_actions, int32_t n_envs, int64_t K,
                              const double* d_mu, const double* d_sigma, double weight, double* d_scores,
-                             hipStream_t st) {
-    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+                             hipStream_t st, int32_t steps = 0) {
+    const int32_t H = steps ? steps : e->cfg.horizon, ha = H * e->cfg.action_dim;
     if (mppi_control_lds(ha) > kMppiControlMaxLds)
         return fail(BCMPC_ERR_UNSUPPORTED, "horizon * action_dim is too large for the control-cost kernel's table");
     if ((K + 255) / 256 * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one launch");
     MppiControlArgs a{};
     a.costs = d_costs; a.actions = d_actions; a.mu = d_mu; a.sigma = d_sigma; a.out = d_scores;
     a.K = K; a.Ktot = K * n_envs; a.bpe = (K + 255) / 256;
-    a.n_envs = n_envs; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.n_envs = n_envs; a.H = H; a.A = e->cfg.action_dim;
     a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
     a.weight = weight;
     HIP_TRY(launch_mppi_control_cost(a, st));
@@ -386,10 +420,10 @@ static int control_cost_impl(bcmpc_engine* e, const double* d_costs, const doubl
 // sigma' from the weights of d_scores about d_mu_new (mppi_ext.hip); the scratch is the update's, grown like it
 static int sigma_update_impl(bcmpc_engine* e, const double* d_scores, const double* d_actions, int32_t n_envs, int64_t K,
                              double lambda, const double* d_mu_new, double* d_sigma, double alpha, double min_std,
-                             double max_std, hipStream_t st) {
+                             double max_std, hipStream_t st, int32_t steps = 0) {
     const int64_t parts = mppi_parts(K);
     if (parts * n_envs > 0x7fffffff) return fail(BCMPC_ERR_UNSUPPORTED, "n_envs * K is too large for one update");
-    const int32_t ha = e->cfg.horizon * e->cfg.action_dim;
+    const int32_t H = steps ? steps : e->cfg.horizon, ha = H * e->cfg.action_dim;
     const size_t need = mppi_sigma_scratch(K, n_envs, ha);
     if (need > e->mppi_cap) {
         if (e->d_mppi) (void)hipFree(e->d_mppi);
@@ -404,7 +438,7 @@ static int sigma_update_impl(bcmpc_engine* e, const double* d_scores, const doub
     a.pcnt = reinterpret_cast<int64_t*>(e->d_mppi + (size_t)n_envs * kMppiMinParts);
     a.part = e->d_mppi + 2 * (size_t)n_envs * kMppiMinParts;
     a.K = K; a.Ktot = K * n_envs; a.nparts = parts;
-    a.n_envs = n_envs; a.H = e->cfg.horizon; a.A = e->cfg.action_dim;
+    a.n_envs = n_envs; a.H = H; a.A = e->cfg.action_dim;
     a.cpl = mppi_cpl(K); a.nmin = mppi_min_blocks(K);
     a.maximize = e->cfg.cost == BCMPC_COST_REWARD;
     a.lambda = lambda; a.alpha = alpha; a.min_std = min_std; a.max_std = max_std;
@@ -553,6 +587,99 @@ int bcmpc_mppi_update_batch_async(bcmpc_engine* e, const double* d_costs, int32_
                                   d_actions, (hipStream_t)stream);
 }
 
+// ---- knot plans (plan_knots.hip): the sampler, and the outer-loop blocks with the step count given ----
+int bcmpc_plan_sample_knots_async(bcmpc_engine* e, const double* d_mu, const double* d_sigma, int32_t n_envs, int64_t K,
+                                  uint64_t seed, int32_t iteration, int64_t cand_offset, double rho, const double* d_keep,
+                                  const int32_t* d_keep_count, int32_t n_elite, int32_t knots, int32_t kind,
+                                  double* d_knots, double* d_actions, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_mu || !d_sigma || !d_knots || !d_actions) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = knots_check(knots, kind, e->cfg.horizon)) return rc;
+    if (const int rc = rho_check(rho)) return rc;
+    if ((d_keep != nullptr) != (d_keep_count != nullptr))
+        return fail(BCMPC_ERR_ARG, "d_keep and d_keep_count go together (both, or both NULL)");
+    if (d_keep && n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_sample_knots_impl(e, d_mu, d_sigma, n_envs, K, seed, iteration, cand_offset, rho, d_keep, d_keep_count,
+                                  n_elite, knots, kind, d_knots, d_actions, (hipStream_t)stream);
+}
+
+int bcmpc_cem_refit_batch_steps_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count,
+                                      int32_t n_envs, int32_t n_elite, uint64_t seed, int32_t iteration, double alpha,
+                                      double* d_mu, double* d_sigma, const double* d_actions, int64_t K,
+                                      int64_t cand_offset, int32_t steps, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_elite || !d_count || !d_mu || !d_sigma || !d_actions) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = steps_check(steps, e->cfg.horizon)) return rc;
+    if (n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return refit_batch_impl(e, d_elite, d_count, n_envs, n_elite, seed, iteration, alpha, d_mu, d_sigma, d_actions, K,
+                            cand_offset, (hipStream_t)stream, steps);
+}
+
+int bcmpc_mppi_update_batch_steps_async(bcmpc_engine* e, const double* d_costs, int32_t n_envs, int64_t K,
+                                        int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda,
+                                        double* d_mu, const double* d_sigma, bcmpc_mppi_stats* d_stats,
+                                        const double* d_actions, int32_t steps, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_mu || !d_sigma || !d_stats || !d_actions) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = steps_check(steps, e->cfg.horizon)) return rc;
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (const int rc = plan_block_check(e, n_envs, K, iteration)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return mppi_update_batch_impl(e, d_costs, n_envs, K, cand_offset, seed, iteration, lambda, d_mu, d_sigma, d_stats,
+                                  d_actions, (hipStream_t)stream, steps);
+}
+
+int bcmpc_plan_keep_steps_async(bcmpc_engine* e, const bcmpc_elite* d_elite, const int32_t* d_count,
+                                const double* d_actions, int32_t n_envs, int64_t K, int64_t cand_offset,
+                                int32_t n_elite, double* d_keep, int32_t* d_keep_count, int32_t steps, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_elite || !d_count || !d_actions || !d_keep || !d_keep_count) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = steps_check(steps, e->cfg.horizon)) return rc;
+    if (n_elite < 1) return fail(BCMPC_ERR_ARG, "n_elite must be >= 1");
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return plan_keep_impl(e, d_elite, d_count, d_actions, n_envs, K, cand_offset, n_elite, d_keep, d_keep_count,
+                          (hipStream_t)stream, steps);
+}
+
+int bcmpc_mppi_control_cost_steps_async(bcmpc_engine* e, const double* d_costs, const double* d_actions,
+                                        int32_t n_envs, int64_t K, const double* d_mu, const double* d_sigma,
+                                        double weight, double* d_scores, int32_t steps, void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_costs || !d_actions || !d_mu || !d_sigma || !d_scores) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = steps_check(steps, e->cfg.horizon)) return rc;
+    if (const int rc = control_weight_check(weight)) return rc;
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return control_cost_impl(e, d_costs, d_actions, n_envs, K, d_mu, d_sigma, weight, d_scores, (hipStream_t)stream,
+                             steps);
+}
+
+int bcmpc_mppi_sigma_update_steps_async(bcmpc_engine* e, const double* d_scores, const double* d_actions,
+                                        int32_t n_envs, int64_t K, double lambda, const double* d_mu_new,
+                                        double* d_sigma, double alpha, double min_std, double max_std, int32_t steps,
+                                        void* stream) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !d_scores || !d_actions || !d_mu_new || !d_sigma) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = steps_check(steps, e->cfg.horizon)) return rc;
+    if (!(std::isfinite(lambda) && lambda > 0.0)) return fail(BCMPC_ERR_ARG, "lambda must be finite and > 0");
+    if (const int rc = sigma_step_check(alpha, min_std, max_std)) return rc;
+    if (const int rc = plan_block_check(e, n_envs, K, 0)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    return sigma_update_impl(e, d_scores, d_actions, n_envs, K, lambda, d_mu_new, d_sigma, alpha, min_std, max_std,
+                             (hipStream_t)stream, steps);
+}
+
 // the synchronous calls' device buffers: plans, counts and statistics per environment, the elite records
 static int plan_buffers(bcmpc_engine* e, int32_t n_envs, size_t n_elite_total) {
     const size_t ha = (size_t)e->cfg.horizon * e->cfg.action_dim;
@@ -605,23 +732,37 @@ static int keep_buffers(bcmpc_engine* e, int32_t n_envs, int32_t n_elite) {
 // A non-default ext (MPPI; checked by the caller): the control-cost launch in front of the update, whose augmented
 // scores replace the costs in it (the record stays on the raw costs), and with adapt_sigma the sigma launches
 // behind it; sigma_io is then written back like CEM's.
+// Knots (kn; checked by the caller, never with proposals): the plans are [n_envs][M][A]; plan_sample_knots writes the
+// clipped knots into d_knots and their expansion into d_actions, the rollout and the record read d_actions, and
+// everything behind select -- refit or update, control cost, sigma update, plan_keep -- runs on d_knots with the step
+// count M.
 static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* cem,
                             const bcmpc_mppi* mp, const bcmpc_sampling* smp, uint64_t seed, int64_t cand_offset,
                             double* mu, double* sigma_io, const double* sigma_in, bcmpc_result* out,
                             bcmpc_mppi_stats* stats, double* costs_out, const bcmpc_mppi_ext* ext = nullptr,
-                            const bcmpc_proposals* prop = nullptr) {
+                            const bcmpc_proposals* prop = nullptr, const bcmpc_knots* kn = nullptr) {
     const bcmpc_config& c = e->cfg;
     const int32_t iterations = cem ? cem->iterations : mp->iterations;
     const int64_t K = c.num_paths / n_envs;
     HIP_TRY(hipSetDevice(c.device));
     const SyncCall sync_guard(e);
-    const size_t ha = (size_t)c.horizon * c.action_dim, nplan = (size_t)n_envs * ha;
+    const int32_t M = knots_none(kn) ? 0 : kn->count;   // the outer loop's step count (0: the horizon)
+    const size_t ha = (size_t)c.horizon * c.action_dim, nplan = (size_t)n_envs * (M ? (size_t)M * c.action_dim : ha);
     if (const int rc = batch_buffers(e, n_envs)) return rc;
     if (const int rc = plan_buffers(e, n_envs, cem ? (size_t)n_envs * cem->n_elite : 0)) return rc;
     if (const int rc = actions_buffer(e)) return rc;
     const bool corr = !sampling_default(smp), carry = corr && cem && smp->keep_elites && iterations > 1;
     if (carry)
         if (const int rc = keep_buffers(e, n_envs, cem->n_elite)) return rc;
+    const size_t nknots = (size_t)M * (size_t)c.num_paths * c.action_dim;
+    if (nknots > e->knots_cap) {
+        if (e->d_knots) (void)hipFree(e->d_knots);
+        e->d_knots = nullptr;
+        e->knots_cap = 0;
+        HIP_TRY(hipMalloc(&e->d_knots, nknots * sizeof(double)));
+        e->knots_cap = nknots;
+    }
+    const double* const d_drawn = M ? e->d_knots : e->d_actions;   // what select's followers read
     // proposals (checked by the caller): host sequences go up with the plans, device ones are read where they are
     const int32_t P = proposals_none(prop) ? 0 : prop->count;
     const size_t nprop = (size_t)n_envs * (size_t)P * ha;
@@ -660,7 +801,11 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
     HIP_TRY(launch_tile_states(t, st));
     for (int it = 0; it < iterations; ++it) {
         const bool kept = carry && it > 0;
-        if (const int rc = P ? plan_sample_prop_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+        if (const int rc = M ? plan_sample_knots_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
+                                                      smp ? smp->rho : 0.0, kept ? e->d_keep : nullptr,
+                                                      kept ? e->d_keep_count : nullptr, cem ? cem->n_elite : 0, M,
+                                                      kn->kind, e->d_knots, e->d_actions, st)
+                           : P ? plan_sample_prop_impl(e, e->d_bmu, e->d_bsigma, n_envs, K, seed, it, cand_offset,
                                                      smp ? smp->rho : 0.0, kept ? e->d_keep : nullptr,
                                                      kept ? e->d_keep_count : nullptr, cem ? cem->n_elite : 0, d_prop,
                                                      P, prop_env, prop_seq, prop_step, e->d_actions, st)
@@ -686,20 +831,20 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
         // (MPPI with the control-cost term: the update and the sigma launches read the augmented scores)
         const double* scores = control ? e->d_mppi_scores : e->d_costs;
         if (rc == BCMPC_OK && control)
-            rc = control_cost_impl(e, e->d_costs, e->d_actions, n_envs, K, e->d_bmu, e->d_bsigma, ext->control_weight,
-                                   e->d_mppi_scores, st);
+            rc = control_cost_impl(e, e->d_costs, d_drawn, n_envs, K, e->d_bmu, e->d_bsigma, ext->control_weight,
+                                   e->d_mppi_scores, st, M);
         if (rc == BCMPC_OK)
             rc = cem ? refit_batch_impl(e, e->d_belite, e->d_bcount, n_envs, cem->n_elite, seed, it, cem->alpha, e->d_bmu,
-                                        e->d_bsigma, e->d_actions, K, cand_offset, st)
+                                        e->d_bsigma, d_drawn, K, cand_offset, st, M)
                      : mppi_update_batch_impl(e, scores, n_envs, K, cand_offset, seed, it, mp->lambda, e->d_bmu,
-                                              e->d_bsigma, e->d_bstats, e->d_actions, st);
+                                              e->d_bsigma, e->d_bstats, d_drawn, st, M);
         if (rc == BCMPC_OK && adapt)
-            rc = sigma_update_impl(e, scores, e->d_actions, n_envs, K, mp->lambda, e->d_bmu, e->d_bsigma,
-                                   ext->sigma_alpha, ext->min_std, ext->max_std, st);
+            rc = sigma_update_impl(e, scores, d_drawn, n_envs, K, mp->lambda, e->d_bmu, e->d_bsigma,
+                                   ext->sigma_alpha, ext->min_std, ext->max_std, st, M);
         // the elites' sequences out of the array, before the next iteration's sampling overwrites it
         if (rc == BCMPC_OK && carry && it + 1 < iterations)
-            rc = plan_keep_impl(e, e->d_belite, e->d_bcount, e->d_actions, n_envs, K, cand_offset, cem->n_elite,
-                                e->d_keep, e->d_keep_count, st);
+            rc = plan_keep_impl(e, e->d_belite, e->d_bcount, d_drawn, n_envs, K, cand_offset, cem->n_elite,
+                                e->d_keep, e->d_keep_count, st, M);
         if (rc != BCMPC_OK) return rc;
     }
     if (e->timing) {
@@ -716,7 +861,7 @@ static int plan_get_actions(bcmpc_engine* e, const double* states, int32_t n_env
         if (const int fr = team_fallback(e)) return fr;
         inputs.restore(mu, sigma_io);
         return plan_get_actions(e->fb, states, n_envs, cem, mp, smp, seed, cand_offset, mu, sigma_io, sigma_in, out,
-                                stats, costs_out, ext, prop);
+                                stats, costs_out, ext, prop, kn);
     }
     std::memcpy(out, e->h_bresults, (size_t)n_envs * sizeof(bcmpc_result));
     return BCMPC_OK;
@@ -1241,6 +1386,93 @@ int bcmpc_mppi_get_actions_batch_p(bcmpc_engine* e, const double* states, int32_
                                               stats, costs_out);
     return mppi_proposals_call(e, states, n_envs, p, sampling, ext, prop, seed, cand_offset, mu, sigma, out, stats,
                                costs_out, false);
+}
+
+// ... and with knot plans: off, the calls above; else the batched chain with plan_sample_knots as its
+// sampler and the outer loop in knot space.  One body per planner, as for proposals.
+static int cem_knots_call(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                          const bcmpc_sampling* sampling, const bcmpc_proposals* prop, const bcmpc_knots* kn,
+                          uint64_t seed, int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                          double* costs_out, bool single) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = knots_check(kn->count, kn->kind, e->cfg.horizon)) return rc;
+    if (single && e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "CEM needs a fused objective");
+    if (const int rc = cem_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, false)) return rc;
+    if (!proposals_none(prop))
+        return fail(BCMPC_ERR_UNSUPPORTED, "knots with proposals are not supported (a given action sequence has no "
+                                           "knot representation to refit on)");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    const int64_t K = e->cfg.num_paths / n_envs;
+    if (const int rc = single ? k_global_check(p->k_global, "single-device CEM", K)
+                              : k_global_check(p->k_global, "batched CEM", K, "num_paths / n_envs"))
+        return rc;
+    return plan_get_actions(e, states, n_envs, p, nullptr, sampling, seed, cand_offset, mu, sigma, nullptr, out, nullptr,
+                            costs_out, nullptr, nullptr, kn);
+}
+
+static int mppi_knots_call(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                           const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext, const bcmpc_proposals* prop,
+                           const bcmpc_knots* kn, uint64_t seed, int64_t cand_offset, double* mu, double* sigma,
+                           bcmpc_result* out, bcmpc_mppi_stats* stats, double* costs_out, bool single) {
+    // (arguments first: a bad call is answered before any HIP call)
+    if (const int rc = mppi_ext_check(ext)) return rc;
+    if (n_envs < 1) return fail(BCMPC_ERR_ARG, "n_envs must be >= 1");
+    if (!e || !states || !p || !mu || !sigma || !out || !stats) return fail(BCMPC_ERR_ARG, "null argument");
+    if (const int rc = knots_check(kn->count, kn->kind, e->cfg.horizon)) return rc;
+    if (const int rc = mppi_param_check(p)) return rc;
+    if (const int rc = sampling_check(sampling, true)) return rc;
+    if (single && e->cfg.cost == BCMPC_COST_NONE) return fail(BCMPC_ERR_ARG, "MPPI needs a fused objective");
+    if (!proposals_none(prop))
+        return fail(BCMPC_ERR_UNSUPPORTED, "knots with proposals are not supported (a given action sequence has no "
+                                           "knot representation to refit on)");
+    if (const int rc = batch_check(e, n_envs)) return rc;
+    const int64_t K = e->cfg.num_paths / n_envs;
+    if (const int rc = single ? k_global_check(p->k_global, "single-device MPPI", K)
+                              : k_global_check(p->k_global, "batched MPPI", K, "num_paths / n_envs"))
+        return rc;
+    // (sigma is written back only under adapt_sigma, as in the _x calls)
+    return plan_get_actions(e, states, n_envs, nullptr, p, sampling, seed, cand_offset, mu, sigma, sigma, out, stats,
+                            costs_out, mppi_ext_default(ext) ? nullptr : ext, nullptr, kn);
+}
+
+int bcmpc_cem_get_action_k(bcmpc_engine* e, const double* state, const bcmpc_cem* p, const bcmpc_sampling* sampling,
+                           const bcmpc_proposals* prop, const bcmpc_knots* knots, uint64_t seed, double* mu,
+                           double* sigma, bcmpc_result* out) {
+    if (knots_none(knots)) return bcmpc_cem_get_action_p(e, state, p, sampling, prop, seed, mu, sigma, out);
+    return cem_knots_call(e, state, 1, p, sampling, prop, knots, seed, 0, mu, sigma, out, nullptr, true);
+}
+
+int bcmpc_mppi_get_action_k(bcmpc_engine* e, const double* state, const bcmpc_mppi* p, const bcmpc_sampling* sampling,
+                            const bcmpc_mppi_ext* ext, const bcmpc_proposals* prop, const bcmpc_knots* knots,
+                            uint64_t seed, double* mu, double* sigma, bcmpc_result* out, bcmpc_mppi_stats* stats) {
+    if (knots_none(knots)) return bcmpc_mppi_get_action_p(e, state, p, sampling, ext, prop, seed, mu, sigma, out, stats);
+    return mppi_knots_call(e, state, 1, p, sampling, ext, prop, knots, seed, 0, mu, sigma, out, stats, nullptr, true);
+}
+
+int bcmpc_cem_get_actions_batch_k(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_cem* p,
+                                  const bcmpc_sampling* sampling, const bcmpc_proposals* prop,
+                                  const bcmpc_knots* knots, uint64_t seed, int64_t cand_offset, double* mu,
+                                  double* sigma, bcmpc_result* out, double* costs_out) {
+    if (knots_none(knots))
+        return bcmpc_cem_get_actions_batch_p(e, states, n_envs, p, sampling, prop, seed, cand_offset, mu, sigma, out,
+                                             costs_out);
+    return cem_knots_call(e, states, n_envs, p, sampling, prop, knots, seed, cand_offset, mu, sigma, out, costs_out,
+                          false);
+}
+
+int bcmpc_mppi_get_actions_batch_k(bcmpc_engine* e, const double* states, int32_t n_envs, const bcmpc_mppi* p,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                                   const bcmpc_proposals* prop, const bcmpc_knots* knots, uint64_t seed,
+                                   int64_t cand_offset, double* mu, double* sigma, bcmpc_result* out,
+                                   bcmpc_mppi_stats* stats, double* costs_out) {
+    if (knots_none(knots))
+        return bcmpc_mppi_get_actions_batch_p(e, states, n_envs, p, sampling, ext, prop, seed, cand_offset, mu, sigma,
+                                              out, stats, costs_out);
+    return mppi_knots_call(e, states, n_envs, p, sampling, ext, prop, knots, seed, cand_offset, mu, sigma, out, stats,
+                           costs_out, false);
 }
 
 int bcmpc_ensemble_cem_get_action(bcmpc_ensemble* s, const double* state, const bcmpc_cem* p, uint64_t seed,

@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from . import knots as _knots
 from . import mppi_update as _mppi_update
 from . import proposals as _proposals
 from . import sampling as _sampling
@@ -214,6 +215,7 @@ class _EngineCalls:
     _CEM_S, _MPPI_S = "bcmpc_cem_get_action_s", "bcmpc_mppi_get_action_s"     # (None: no such entry)
     _MPPI_X = "bcmpc_mppi_get_action_x"
     _CEM_P, _MPPI_P = "bcmpc_cem_get_action_p", "bcmpc_mppi_get_action_p"
+    _CEM_K, _MPPI_K = "bcmpc_cem_get_action_k", "bcmpc_mppi_get_action_k"
 
     def _fresh(self) -> None:
         """The wrapper's host state for a handle nothing has been set on yet."""
@@ -276,6 +278,18 @@ class _EngineCalls:
         P = _proposals.check_count(arr.shape[-3], K, n_elite)
         return _lib.Proposals(arr.ctypes.data, P, 0, *_proposals.canonical_strides(P, self.horizon, self.action_dim)), arr
 
+    def _knots(self, knots, knot_interp, proposals):
+        """The ``_lib.Knots`` of a planner call's ``knots`` / ``knot_interp`` (knots.py), or None with ``knots=None``:
+        the call then goes to the entry point it has always gone to.  Knots with proposals are refused here."""
+        M = _knots.check_knots(knots, self.horizon)
+        kind = _knots.check_interp(knot_interp)
+        if M is None:
+            return None
+        if proposals is not None:
+            raise NotImplementedError(f"{type(self).__name__}: knots with proposals are not built (a given action "
+                                      "sequence has no knot representation to refit on)")
+        return _lib.Knots(M, _knots.KINDS.index(kind))
+
     def _step_result(self, res, costs=None) -> StepResult:
         return StepResult(int(res.best_index), float(res.best_cost),
                           np.array(res.first_action[: self.action_dim], dtype=np.float64), costs)
@@ -287,23 +301,31 @@ class _EngineCalls:
         return getattr(self._lib, name)
 
     def cem_get_action(self, state, mu, sigma, iterations: int, n_elite: int, alpha: float,
-                       seed: int, rho: float = 0.0, keep_elites: bool = False, proposals=None
+                       seed: int, rho: float = 0.0, keep_elites: bool = False, proposals=None,
+                       knots: Optional[int] = None, knot_interp: str = "linear"
                        ) -> Tuple[StepResult, np.ndarray, np.ndarray]:
         """All CEM iterations on this device (bcmpc_cem_get_action; an ensemble: bcmpc_ensemble_cem_get_action,
         the elites of every iteration chosen by the combined value).  ``mu``/``sigma`` are ``[H, A]``; returns
         (result with best_index = iteration*K + candidate, mu', sigma').  ``rho`` / ``keep_elites``:
         temporally correlated noise and elite carry-over (sampling.py; bcmpc_cem_get_action_s).  ``proposals``
         (``[P, H, A]`` or ``DeviceProposals``): given sequences in the last P columns of every iteration's
-        population (proposals.py; bcmpc_cem_get_action_p)."""
+        population (proposals.py; bcmpc_cem_get_action_p).  ``knots`` (M in ``[1, H]``) / ``knot_interp``: the
+        plan is sampled at M knots and interpolated (knots.py; bcmpc_cem_get_action_k); ``mu`` / ``sigma`` and
+        the returned plan are then ``[M, A]``."""
         smp = self._sampling(rho, keep_elites)
+        kn = self._knots(knots, knot_interp, proposals)
         prop, _alive = self._proposals(proposals, None, int(n_elite) if smp is not None and smp.keep_elites else 0)
         st = self._state(state)
-        shape = (self.horizon, self.action_dim)
+        shape = (self.horizon if kn is None else kn.count, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.array(sigma, dtype=np.float64, copy=True).reshape(shape)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = _lib.Result()
-        if prop is not None:
+        if kn is not None:
+            _lib.check(self._s_entry(self._CEM_K, "cem_get_action", "knot plans")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None, None,
+                ctypes.byref(kn), ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res)))
+        elif prop is not None:
             _lib.check(self._s_entry(self._CEM_P, "cem_get_action", "proposals")(
                 self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None, ctypes.byref(prop),
                 ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res)))
@@ -320,7 +342,7 @@ class _EngineCalls:
     def mppi_get_action(self, state, mu, sigma, iterations: int, temperature: float,
                         seed: int, rho: float = 0.0, control_cost=0.0, adapt_sigma: bool = False,
                         sigma_alpha: float = 0.0, min_std: float = 0.0, max_std: Optional[float] = None,
-                        proposals=None):
+                        proposals=None, knots: Optional[int] = None, knot_interp: str = "linear"):
         """``iterations`` rounds of CEM-style rollout + MPPI update on this device (bcmpc_mppi_get_action; an
         ensemble: bcmpc_ensemble_mppi_get_action, the softmin weights from the combined value; DESIGN.md "MPPI").
         ``mu``/``sigma`` are ``[H, A]``; returns (the best single candidate over all rounds, best_index =
@@ -336,16 +358,29 @@ class _EngineCalls:
 
         ``proposals`` (``[P, H, A]`` or ``DeviceProposals``): given sequences in the last P columns of every round's
         population (proposals.py; bcmpc_mppi_get_action_p).  A proposal is weighted like a sample although it is
-        not a draw from ``N(mu, sigma)``."""
+        not a draw from ``N(mu, sigma)``.
+
+        ``knots`` (M in ``[1, H]``) / ``knot_interp``: the plan is sampled at M knots and interpolated (knots.py;
+        bcmpc_mppi_get_action_k); ``mu`` / ``sigma`` and the returned plan(s) are then ``[M, A]``, and row 0 of the
+        plan is still the action to apply (knot 0 sits at step 0)."""
         smp = self._sampling(rho)
         ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
+        kn = self._knots(knots, knot_interp, proposals)
         prop, _alive = self._proposals(proposals, None)
         st = self._state(state)
-        shape = (self.horizon, self.action_dim)
+        shape = (self.horizon if kn is None else kn.count, self.action_dim)
         m = np.array(mu, dtype=np.float64, copy=True).reshape(shape)
         s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(shape))
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res, stats = _lib.Result(), _lib.MppiStats()
+        if kn is not None:
+            s = np.array(s, dtype=np.float64, copy=True)           # (in / out: the caller's array is not written)
+            _lib.check(self._s_entry(self._MPPI_K, "mppi_get_action", "knot plans")(
+                self._h, _dp(st), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(ext) if ext is not None else None, None, ctypes.byref(kn),
+                ctypes.c_uint64(seed & (2**64 - 1)), _dp(m), _dp(s), ctypes.byref(res), ctypes.byref(stats)))
+            adapt = ext is not None and ext.adapt_sigma
+            return (self._step_result(res), m, stats, s) if adapt else (self._step_result(res), m, stats)
         if prop is not None:
             s = np.array(s, dtype=np.float64, copy=True)           # (in / out: the caller's array is not written)
             _lib.check(self._s_entry(self._MPPI_P, "mppi_get_action", "proposals")(
@@ -1032,14 +1067,15 @@ class RolloutEngine(_EngineCalls):
             float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), ctypes.c_void_p(stream)))
 
     # ------------------------------------------------------------------ batched CEM / MPPI
-    def _plan_batch_args(self, states, mu, sigma, copy_sigma: bool):
+    def _plan_batch_args(self, states, mu, sigma, copy_sigma: bool, steps: Optional[int] = None):
         st = _f64(states)
         if st.ndim != 2 or st.shape[1] != self.state_dim:
             raise ValueError(f"states shape {st.shape} != (B, S) = (B, {self.state_dim})")
         B = self._n_envs(st.shape[0])
-        shape = (B, self.horizon, self.action_dim)
+        shape = (B, self.horizon if steps is None else steps, self.action_dim)
         if np.shape(mu) != shape or np.shape(sigma) != shape:
-            raise ValueError(f"mu / sigma shapes {np.shape(mu)} / {np.shape(sigma)} != (B, H, A) = {shape}")
+            raise ValueError(f"mu / sigma shapes {np.shape(mu)} / {np.shape(sigma)} != "
+                             f"{'(B, H, A)' if steps is None else '(B, M, A)'} = {shape}")
         m = np.array(mu, dtype=np.float64, copy=True, order="C")
         s = (np.array(sigma, dtype=np.float64, copy=True, order="C") if copy_sigma
              else np.ascontiguousarray(sigma, dtype=np.float64))
@@ -1052,21 +1088,29 @@ class RolloutEngine(_EngineCalls):
 
     def cem_get_actions(self, states, mu, sigma, iterations: int, n_elite: int, alpha: float, seed: int,
                         cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0,
-                        keep_elites: bool = False, proposals=None) -> Tuple[BatchResult, np.ndarray, np.ndarray]:
+                        keep_elites: bool = False, proposals=None, knots: Optional[int] = None,
+                        knot_interp: str = "linear") -> Tuple[BatchResult, np.ndarray, np.ndarray]:
         """Batched CEM (bcmpc_cem_get_actions_batch): ``states`` ``[B, S]``, ``mu`` / ``sigma``
         ``[B, H, A]``, ``K = num_paths // B`` candidates and ``n_elite`` elites per environment, columns
         as for get_actions.  Returns (records with ``best_index = iteration*K + candidate`` per
         environment and ``costs`` ``[iterations, B, K]`` when asked for, mu' ``[B, H, A]``, sigma').
         ``rho`` / ``keep_elites``: temporally correlated noise and elite carry-over (sampling.py;
         bcmpc_cem_get_actions_batch_s).  ``proposals`` (``[B, P, H, A]`` or ``DeviceProposals``): every
-        environment's given sequences in its last P columns (proposals.py; bcmpc_cem_get_actions_batch_p)."""
+        environment's given sequences in its last P columns (proposals.py; bcmpc_cem_get_actions_batch_p).
+        ``knots`` / ``knot_interp``: as cem_get_action, the plans ``[B, M, A]`` (bcmpc_cem_get_actions_batch_k)."""
         smp = self._sampling(rho, keep_elites)
-        st, B, m, s = self._plan_batch_args(states, mu, sigma, True)
+        kn = self._knots(knots, knot_interp, proposals)
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, True, None if kn is None else kn.count)
         prop, _alive = self._proposals(proposals, B, int(n_elite) if smp is not None and smp.keep_elites else 0)
         p = _lib.Cem(int(iterations), int(n_elite), float(alpha), 0)
         res = (_lib.Result * B)()
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
-        if prop is not None:
+        if kn is not None:
+            _lib.check(self._lib.bcmpc_cem_get_actions_batch_k(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                None, ctypes.byref(kn), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m),
+                _dp(s), res, _dp(costs) if costs is not None else None))
+        elif prop is not None:
             _lib.check(self._lib.bcmpc_cem_get_actions_batch_p(
                 self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
                 ctypes.byref(prop), ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s),
@@ -1085,7 +1129,8 @@ class RolloutEngine(_EngineCalls):
     def mppi_get_actions(self, states, mu, sigma, iterations: int, temperature: float, seed: int,
                          cand_offset: int = 0, return_costs: bool = False, rho: float = 0.0, control_cost=0.0,
                          adapt_sigma: bool = False, sigma_alpha: float = 0.0, min_std: float = 0.0,
-                         max_std: Optional[float] = None, proposals=None):
+                         max_std: Optional[float] = None, proposals=None, knots: Optional[int] = None,
+                         knot_interp: str = "linear"):
         """Batched MPPI (bcmpc_mppi_get_actions_batch): as cem_get_actions, with the softmin update of
         mppi_get_action per environment.  Returns (records, mu' ``[B, H, A]`` whose rows ``[b, 0]`` are the
         actions to apply, the last round's statistics as a ``[B]`` array of MPPI_STATS).  sigma is not
@@ -1093,16 +1138,26 @@ class RolloutEngine(_EngineCalls):
         ``control_cost`` / ``adapt_sigma`` / ``sigma_alpha`` / ``min_std`` / ``max_std``: as mppi_get_action
         (bcmpc_mppi_get_actions_batch_x); the returned costs stay the raw ones, and with ``adapt_sigma`` a fourth
         element, sigma' ``[B, H, A]``, is returned.  ``proposals`` (``[B, P, H, A]`` or ``DeviceProposals``): every
-        environment's given sequences in its last P columns (proposals.py; bcmpc_mppi_get_actions_batch_p)."""
+        environment's given sequences in its last P columns (proposals.py; bcmpc_mppi_get_actions_batch_p).
+        ``knots`` / ``knot_interp``: as mppi_get_action, the plans ``[B, M, A]`` (bcmpc_mppi_get_actions_batch_k)."""
         smp = self._sampling(rho)
         ext = self._mppi_ext(control_cost, adapt_sigma, sigma_alpha, min_std, max_std, temperature)
-        st, B, m, s = self._plan_batch_args(states, mu, sigma, ext is not None or proposals is not None)
+        kn = self._knots(knots, knot_interp, proposals)
+        st, B, m, s = self._plan_batch_args(states, mu, sigma, ext is not None or proposals is not None or kn is not None,
+                                            None if kn is None else kn.count)
         prop, _alive = self._proposals(proposals, B)
         p = _lib.Mppi(int(iterations), float(temperature), 0)
         res = (_lib.Result * B)()
         stats = np.zeros(B, dtype=MPPI_STATS)
         costs = np.empty((max(int(iterations), 0), self.num_paths), dtype=np.float64) if return_costs else None
         d_stats, d_costs = stats.ctypes.data_as(ctypes.POINTER(_lib.MppiStats)), _dp(costs) if costs is not None else None
+        if kn is not None:
+            _lib.check(self._lib.bcmpc_mppi_get_actions_batch_k(
+                self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
+                ctypes.byref(ext) if ext is not None else None, None, ctypes.byref(kn),
+                ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(cand_offset), _dp(m), _dp(s), res, d_stats, d_costs))
+            out = self._batch_result(res, B, costs, int(iterations))
+            return (out, m, stats, s) if ext is not None and ext.adapt_sigma else (out, m, stats)
         if prop is not None:
             _lib.check(self._lib.bcmpc_mppi_get_actions_batch_p(
                 self._h, _dp(st), ctypes.c_int32(B), ctypes.byref(p), ctypes.byref(smp) if smp is not None else None,
@@ -1178,6 +1233,78 @@ class RolloutEngine(_EngineCalls):
         _lib.check(self._lib.bcmpc_plan_keep_async(
             self._h, vp(d_elite), vp(d_count), vp(d_actions), int(n_envs), int(K), int(cand_offset), int(n_elite),
             vp(d_keep), vp(d_keep_count), ctypes.c_void_p(stream)))
+
+    def plan_sample_knots_async(self, d_mu: int, d_sigma: int, n_envs: int, K: int, seed: int, iteration: int,
+                                cand_offset: int, rho: float, knots: int, knot_interp, d_knots: int, d_actions: int,
+                                d_keep: Optional[int] = None, d_keep_count: Optional[int] = None, n_elite: int = 0,
+                                stream: Optional[int] = None) -> None:
+        """bcmpc_plan_sample_knots_async: plan_sample_corr_async in knot space (knots.py).  The plans ``d_mu`` /
+        ``d_sigma`` are ``[n_envs, M, A]`` with ``M = knots``, ``d_keep`` ``[n_envs, n_elite, M, A]``; it writes the
+        clipped knots ``d_knots`` ``[M, n_envs*K, A]`` (knots.knot_values) and their expansion ``d_actions``
+        ``[H, n_envs*K, A]`` (knots.expand).  ``knot_interp``: a name of ``knots.KINDS`` or its index."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        kind = _knots.KINDS.index(knot_interp) if isinstance(knot_interp, str) and knot_interp in _knots.KINDS \
+            else int(knot_interp)
+        _lib.check(self._lib.bcmpc_plan_sample_knots_async(
+            self._h, vp(d_mu), vp(d_sigma), int(n_envs), int(K), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), int(cand_offset), float(rho), vp(d_keep), vp(d_keep_count), int(n_elite), int(knots),
+            kind, vp(d_knots), vp(d_actions), ctypes.c_void_p(stream)))
+
+    def cem_refit_batch_steps_async(self, d_elite: int, d_count: int, n_envs: int, n_elite: int, seed: int,
+                                    iteration: int, alpha: float, d_mu: int, d_sigma: int, d_actions: int, K: int,
+                                    cand_offset: int, steps: int, stream: Optional[int] = None) -> None:
+        """bcmpc_cem_refit_batch_steps_async: cem_refit_batch_async on ``d_actions`` ``[steps, n_envs*K, A]`` and
+        plans ``[n_envs, steps, A]`` (a knot array: ``steps = M``)."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_cem_refit_batch_steps_async(
+            self._h, vp(d_elite), vp(d_count), int(n_envs), int(n_elite), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), float(alpha), vp(d_mu), vp(d_sigma), vp(d_actions), int(K), int(cand_offset), int(steps),
+            ctypes.c_void_p(stream)))
+
+    def mppi_update_batch_steps_async(self, d_costs: int, n_envs: int, K: int, cand_offset: int, seed: int,
+                                      iteration: int, temperature: float, d_mu: int, d_sigma: int, d_stats: int,
+                                      d_actions: int, steps: int, stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_update_batch_steps_async: mppi_update_batch_async on ``d_actions`` ``[steps, n_envs*K, A]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_update_batch_steps_async(
+            self._h, vp(d_costs), int(n_envs), int(K), int(cand_offset), ctypes.c_uint64(seed & (2**64 - 1)),
+            int(iteration), float(temperature), vp(d_mu), vp(d_sigma), vp(d_stats), vp(d_actions), int(steps),
+            ctypes.c_void_p(stream)))
+
+    def plan_keep_steps_async(self, d_elite: int, d_count: int, d_actions: int, n_envs: int, K: int, cand_offset: int,
+                              n_elite: int, d_keep: int, d_keep_count: int, steps: int,
+                              stream: Optional[int] = None) -> None:
+        """bcmpc_plan_keep_steps_async: plan_keep_async on ``d_actions`` ``[steps, n_envs*K, A]`` into ``d_keep``
+        ``[n_envs, n_elite, steps, A]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_plan_keep_steps_async(
+            self._h, vp(d_elite), vp(d_count), vp(d_actions), int(n_envs), int(K), int(cand_offset), int(n_elite),
+            vp(d_keep), vp(d_keep_count), int(steps), ctypes.c_void_p(stream)))
+
+    def mppi_control_cost_steps_async(self, d_costs: int, d_actions: int, n_envs: int, K: int, d_mu: int, d_sigma: int,
+                                      weight: float, d_scores: int, steps: int, stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_control_cost_steps_async: mppi_control_cost_async on ``d_actions`` ``[steps, n_envs*K, A]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_control_cost_steps_async(
+            self._h, vp(d_costs), vp(d_actions), int(n_envs), int(K), vp(d_mu), vp(d_sigma), float(weight),
+            vp(d_scores), int(steps), ctypes.c_void_p(stream)))
+
+    def mppi_sigma_update_steps_async(self, d_scores: int, d_actions: int, n_envs: int, K: int, temperature: float,
+                                      d_mu_new: int, d_sigma: int, steps: int, alpha: float = 0.0,
+                                      min_std: float = 0.0, max_std: Optional[float] = None,
+                                      stream: Optional[int] = None) -> None:
+        """bcmpc_mppi_sigma_update_steps_async: mppi_sigma_update_async on ``d_actions`` ``[steps, n_envs*K, A]``."""
+        stream = self.stream if stream is None else stream
+        vp = lambda x: ctypes.c_void_p(x) if x else None   # noqa: E731
+        _lib.check(self._lib.bcmpc_mppi_sigma_update_steps_async(
+            self._h, vp(d_scores), vp(d_actions), int(n_envs), int(K), float(temperature), vp(d_mu_new), vp(d_sigma),
+            float(alpha), float(min_std), float("inf") if max_std is None else float(max_std), int(steps),
+            ctypes.c_void_p(stream)))
 
     def plan_argmin_async(self, d_costs: int, d_actions: int, n_envs: int, K: int, iteration: int, merge: bool,
                           d_results: int, stream: Optional[int] = None) -> None:

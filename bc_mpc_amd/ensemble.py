@@ -114,6 +114,7 @@ class EnsembleEngine(_EngineCalls):
     _CEM_S = _MPPI_S = None             # (correlated noise and elite carry-over: single engines only)
     _MPPI_X = None                      # (MPPI's control cost and sigma update: single engines only)
     _CEM_P = _MPPI_P = None             # (proposals: single engines only)
+    _CEM_K = _MPPI_K = None             # (knot plans: single engines only)
 
     def __init__(self, n_members: int, state_dim: int, action_dim: int, hidden: int, n_layers: int,
                  activation: str, layer_norm: bool, horizon: int, num_paths: int, device: int = 0,

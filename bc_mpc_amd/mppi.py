@@ -52,7 +52,12 @@ class MPPIcontroller(Planner):
     ``proposals=`` on a call and ``policy_prior`` / ``policy_paths`` / ``policy_stochastic`` / ``policy_explore``: given
     action sequences, and a policy net's closed-loop rollouts, in the last candidates of every round (proposals.py,
     DESIGN.md 9m; one rank and one dynamics model only).  A proposal is no draw from ``N(mu, sigma)``: its softmin
-    weight and its control-cost term (``eps = a - mu``) are the heuristic TD-MPC uses for its policy trajectories."""
+    weight and its control-cost term (``eps = a - mu``) are the heuristic TD-MPC uses for its policy trajectories.
+    ``knots`` (M in ``[1, horizon]``) / ``knot_interp`` (``"hold" | "linear" | "cubic"``): the plan is sampled at M
+    knots and interpolated to the horizon (knots.py; read on every call, one rank and one dynamics
+    model only, not with proposals or a policy prior).  ``last_mu`` / ``last_sigma`` and the warm start are then in
+    KNOT space, ``[M, A]`` (batched ``[B, M, A]``); the answer is still ``mu'[0]`` (knot 0 sits at step 0) and
+    ``last_plan`` is the ``[H, A]`` sequence ``last_mu`` expands to (without knots it equals ``last_mu``)."""
     _KIND = "MPPI"
     # what the update adds (mppi_update.py): read on every call, never an engine constructor argument
     control_cost = 0.0
@@ -87,12 +92,14 @@ class MPPIcontroller(Planner):
                  policy_prior=None,
                  policy_paths: int = 0,
                  policy_stochastic: bool = True,
-                 policy_explore: float = 0.0):
+                 policy_explore: float = 0.0,
+                 knots: Optional[int] = None,
+                 knot_interp: str = "linear"):
         super().__init__(env, dyn_model, horizon, cost_fn, num_simulated_paths, gamma, iterations, init_std,
                          warm_start, 0x3B9AC1 if seed is None else seed, device, process_group,
                          terminal_value=terminal_value, terminal_weight=terminal_weight, noise_rho=noise_rho,
                          policy_prior=policy_prior, policy_paths=policy_paths, policy_stochastic=policy_stochastic,
-                         policy_explore=policy_explore)
+                         policy_explore=policy_explore, knots=knots, knot_interp=knot_interp)
         if not (math.isfinite(temperature) and temperature > 0):
             raise ValueError("temperature must be finite and > 0")
         self.temperature = float(temperature)
@@ -126,7 +133,7 @@ class MPPIcontroller(Planner):
 
     def _solve(self, eng, state, mu0, sd0, seed, K):
         res, mu, stats, *sd = eng.mppi_get_action(state, mu0, sd0, self.iterations, self.temperature, seed,
-                                                  **self._sampling_args(), **self._update_args())
+                                                  **self._sampling_args(), **self._update_args(), **self._knot_args())
         self._note_planner_value(eng, res.best_index, K)
         self._mu = mu
         self.last_mu = mu
@@ -161,7 +168,7 @@ class MPPIcontroller(Planner):
 
     def _solve_batch(self, eng, states, mu0, sd0, seed, K):
         res, mu, stats, *sd = eng.mppi_get_actions(states, mu0, sd0, self.iterations, self.temperature, seed,
-                                                   **self._sampling_args(), **self._update_args())
+                                                   **self._sampling_args(), **self._update_args(), **self._knot_args())
         self._note_planner_value(eng, res.best_index, K)
         self._store_plans(mu)
         self.last_mu = mu

@@ -15,7 +15,8 @@ nothing itself: the independent normals ``z`` are the planners' Irwin-Hall draws
 
 Not built: power-law (FFT) noise, carrying a fraction of the elites, ensembles and more than one rank.  The
 library itself carries no elites from one control step to the next; a caller who keeps them passes them (shifted)
-as ``proposals=`` of the next call (proposals.py).  (MPPI's control-cost term: mppi_update.py.)
+as ``proposals=`` of the next call (proposals.py).  (MPPI's control-cost term: mppi_update.py; sampling the
+sequence at fewer knots than steps, where the recursion runs over the knots: knots.py.)
 """
 from __future__ import annotations
 

@@ -877,6 +877,88 @@ int bcmpc_rollout_policy_batch_async(bcmpc_engine* eng, const double* d_states, 
                                      double* d_traj, double* d_actions_out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Knot plans: the planners sample M <= H knots per action dimension and interpolate them to the H steps (additive to
+ * ABI 5; callers detect them by the symbol bcmpc_cem_get_action_k; semantics in DESIGN.md 9n, defined bit for bit by
+ * bc_mpc_amd/knots.py).  The search runs in M * A dimensions, every candidate is smooth by construction, and the plans
+ * a call reads and writes are in knot space:
+ *   mu / sigma : host [n_envs][M][A] (single calls: [M][A]) with M = knots->count
+ *   knot m of candidate g   clip(mu[m][j] + sigma[m][j] * n[m]): the planners' own normal at (seed, g, m, j, iteration)
+ *                -- the knot index in the place of h -- with the AR(1) recursion of bcmpc_sampling.rho over the knots
+ *   step h       kind 0 (hold): knot (h * M) / H (integer division; action repeat).  Kinds 1 (linear) and 2 (cubic,
+ *                Catmull-Rom with the end knots repeated): the knots sit at both ends of the horizon; with
+ *                m0 = h * (M - 1) / (H - 1), r the remainder (both 0 when H == 1 or M == 1), r == 0 gives knot m0
+ *                untouched, else f = (double)r / (double)(H - 1) and the formulas of knots.py, every operation an
+ *                individually rounded f64 one.  Every step's value is clipped to the action box again (the cubic
+ *                overshoots).
+ *   refit / update   select, the CEM refit, the MPPI update, the control cost, the sigma update and the elite carry-over
+ *                run on the clipped KNOT values: the existing kernels launched with the step count M on the knot array
+ *                [M][n_envs * K][A].  The rollout and the record read the expanded array [H][n_envs * K][A]; no rollout
+ *                kernel differs.  MPPI's answer stays mu'[0]: knot 0 sits at step 0 in all three kinds.
+ * The _k entry points take every option of the _p entry points plus the knots.  A NULL knots or count == 0 forwards
+ * to the _p entry point: today's call, bit for bit.  Anything else -- count == H included -- runs the batched chain
+ * (n_envs = 1, cand_offset = 0 for the single calls) with plan_sample_knots as its sampler.
+ * BCMPC_ERR_ARG (before any HIP call): count outside [1, horizon], an unknown kind, and what the _s / _x calls refuse.
+ * BCMPC_ERR_UNSUPPORTED: knots together with proposals (count != 0) -- a given action sequence has no knot
+ * representation to refit on --, a communicator attached, a fused policy.  Ensembles have no _k entry. */
+#define BCMPC_KNOTS_HOLD   0
+#define BCMPC_KNOTS_LINEAR 1
+#define BCMPC_KNOTS_CUBIC  2
+typedef struct bcmpc_knots {
+    int32_t count;           /* M: knots per action dimension, 1 <= M <= horizon; 0: off */
+    int32_t kind;            /* BCMPC_KNOTS_HOLD | _LINEAR | _CUBIC */
+} bcmpc_knots;
+
+int bcmpc_cem_get_action_k(bcmpc_engine* eng, const double* state, const bcmpc_cem* params,
+                           const bcmpc_sampling* sampling, const bcmpc_proposals* proposals, const bcmpc_knots* knots,
+                           uint64_t seed, double* mu, double* sigma, bcmpc_result* out);
+int bcmpc_mppi_get_action_k(bcmpc_engine* eng, const double* state, const bcmpc_mppi* params,
+                            const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                            const bcmpc_proposals* proposals, const bcmpc_knots* knots, uint64_t seed, double* mu,
+                            double* sigma /* in/out */, bcmpc_result* out, bcmpc_mppi_stats* stats);
+int bcmpc_cem_get_actions_batch_k(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_cem* params,
+                                  const bcmpc_sampling* sampling, const bcmpc_proposals* proposals,
+                                  const bcmpc_knots* knots, uint64_t seed, int64_t cand_offset, double* mu,
+                                  double* sigma, bcmpc_result* out, double* costs_out);
+int bcmpc_mppi_get_actions_batch_k(bcmpc_engine* eng, const double* states, int32_t n_envs, const bcmpc_mppi* params,
+                                   const bcmpc_sampling* sampling, const bcmpc_mppi_ext* ext,
+                                   const bcmpc_proposals* proposals, const bcmpc_knots* knots, uint64_t seed,
+                                   int64_t cand_offset, double* mu, double* sigma /* in/out */, bcmpc_result* out,
+                                   bcmpc_mppi_stats* stats, double* costs_out);
+
+/* Their building blocks (device pointers, stream-ordered, no host synchronisation).
+ *   plan_sample_knots  bcmpc_plan_sample_corr_async in knot space: d_mu / d_sigma [n_envs][M][A], d_keep
+ *                [n_envs][n_elite][M][A]; it writes d_knots [M][n_envs * K][A] (the clipped knot values) and d_actions
+ *                [H][n_envs * K][A] (their expansion).  M == H: d_actions holds plan_sample_corr's bits.
+ *   *_steps      bcmpc_cem_refit_batch_async, bcmpc_mppi_update_batch_async, bcmpc_plan_keep_async,
+ *                bcmpc_mppi_control_cost_async and bcmpc_mppi_sigma_update_async with the step count given instead of
+ *                taken from the engine's horizon (1 <= steps <= horizon): d_actions is [steps][n_envs * K][A], the
+ *                plans [n_envs][steps][A], d_keep [n_envs][n_elite][steps][A].  steps == horizon: the call without
+ *                the suffix.  The refit and the update need d_actions here: their Philox form regenerates a full-length
+ *                independent draw, which is not what a knot array holds. */
+int bcmpc_plan_sample_knots_async(bcmpc_engine* eng, const double* d_mu, const double* d_sigma, int32_t n_envs,
+                                  int64_t K, uint64_t seed, int32_t iteration, int64_t cand_offset, double rho,
+                                  const double* d_keep, const int32_t* d_keep_count, int32_t n_elite, int32_t knots,
+                                  int32_t kind, double* d_knots, double* d_actions, void* stream);
+int bcmpc_cem_refit_batch_steps_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const int32_t* d_count,
+                                      int32_t n_envs, int32_t n_elite, uint64_t seed, int32_t iteration, double alpha,
+                                      double* d_mu, double* d_sigma, const double* d_actions, int64_t K,
+                                      int64_t cand_offset, int32_t steps, void* stream);
+int bcmpc_mppi_update_batch_steps_async(bcmpc_engine* eng, const double* d_costs, int32_t n_envs, int64_t K,
+                                        int64_t cand_offset, uint64_t seed, int32_t iteration, double lambda,
+                                        double* d_mu, const double* d_sigma, bcmpc_mppi_stats* d_stats,
+                                        const double* d_actions, int32_t steps, void* stream);
+int bcmpc_plan_keep_steps_async(bcmpc_engine* eng, const bcmpc_elite* d_elite, const int32_t* d_count,
+                                const double* d_actions, int32_t n_envs, int64_t K, int64_t cand_offset,
+                                int32_t n_elite, double* d_keep, int32_t* d_keep_count, int32_t steps, void* stream);
+int bcmpc_mppi_control_cost_steps_async(bcmpc_engine* eng, const double* d_costs, const double* d_actions,
+                                        int32_t n_envs, int64_t K, const double* d_mu, const double* d_sigma,
+                                        double weight, double* d_scores, int32_t steps, void* stream);
+int bcmpc_mppi_sigma_update_steps_async(bcmpc_engine* eng, const double* d_scores, const double* d_actions,
+                                        int32_t n_envs, int64_t K, double lambda, const double* d_mu_new,
+                                        double* d_sigma, double alpha, double min_std, double max_std, int32_t steps,
+                                        void* stream);
+
+/* ------------------------------------------------------------------------
  * Model ensembles (additive to ABI 5; callers detect them by the symbol bcmpc_ensemble_create; not in
  * the reference, semantics in DESIGN.md 9g).  An ensemble holds E dynamics nets of one architecture and
  * one configuration -- E member engines of the same config, hence the same kernel layout.  Candidate k
