@@ -16,10 +16,12 @@ from .engine import BatchResult, MLPSpec, PolicySpec, RolloutEngine, StepResult
 from .ensemble import EnsembleDynamicsModel, EnsembleEngine
 from . import value
 from .value import ValueSpec
+from . import ac_fit
+from .actor_critic import MlpActorCritic
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
            "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult",
-           "EnsembleEngine", "EnsembleDynamicsModel", "ValueSpec"]
+           "EnsembleEngine", "EnsembleDynamicsModel", "ValueSpec", "MlpActorCritic"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

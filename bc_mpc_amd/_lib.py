@@ -242,6 +242,24 @@ class FitConfig(ctypes.Structure):
     ]
 
 
+class AcFitConfig(ctypes.Structure):
+    """bcmpc_acfit_config: one head of the actor-critic fitter (bc_mpc_amd/ac_fit.py)."""
+    _fields_ = [
+        ("state_dim", ctypes.c_int32),
+        ("out_dim", ctypes.c_int32),
+        ("hidden", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32),
+        ("head", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("beta1", ctypes.c_float),
+        ("beta2", ctypes.c_float),
+        ("epsilon", ctypes.c_float),
+    ]
+
+
+ACFIT_POLICY, ACFIT_VALUE = 0, 1
+
 SIGNATURES = [
     ("bcmpc_abi_version", ctypes.c_int, []),
     ("bcmpc_last_error", ctypes.c_char_p, []),
@@ -474,6 +492,19 @@ SIGNATURES = [
     ("bcmpc_fit_last_error", ctypes.c_char_p, []),
     ("bcmpc_fit_set_rewards", ctypes.c_int, [ctypes.c_void_p, _DP, ctypes.c_int64]),
     ("bcmpc_fit_reward_losses", ctypes.c_int, [ctypes.c_void_p, _FP]),
+    ("bcmpc_acfit_create", ctypes.c_int, [ctypes.POINTER(AcFitConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    ("bcmpc_acfit_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_acfit_set_params", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_FP), ctypes.POINTER(_FP)]),
+    ("bcmpc_acfit_get_params", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_FP), ctypes.POINTER(_FP)]),
+    ("bcmpc_acfit_set_filter", ctypes.c_int, [ctypes.c_void_p, _FP, _FP]),
+    ("bcmpc_acfit_set_data", ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_int64]),
+    ("bcmpc_acfit_run", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+      ctypes.c_float, _FP]),
+    ("bcmpc_acfit_is_graph", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_acfit_lds_words", ctypes.c_int64,
+     [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("bcmpc_acfit_last_error", ctypes.c_char_p, []),
     ("bcmpc_comm_unique_id", ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     ("bcmpc_comm_init", ctypes.c_int,
      [ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),

@@ -1071,6 +1071,59 @@ int bcmpc_fit_reward_losses(bcmpc_fitter* f, float* losses);
 const char* bcmpc_fit_last_error(void);
 
 /* ------------------------------------------------------------------------
+ * Actor-critic fitting (bc_mpc_amd/ac_fit.py is the definition): Adam steps on one head of the reference's
+ * MlpPolicy -- BCMPC_ACFIT_POLICY: the BC distillation loss sqrt(mean((ac - ac_mean(ob))^2))
+ * (ppo_bc_policy.py:114, update_op_bc); BCMPC_ACFIT_VALUE: the critic regression mean((vpred - ret)^2)
+ * (ppo_bc_policy.py:108) -- over a tanh stack [S -> hidden x L -> out] behind the observation filter
+ * obz = clip((f32(ob) - ob_mean) / ob_std, -5, 5).  A fitter owns the head's f32 parameters, its Adam slots and
+ * beta powers (they persist across runs like update_op_bc's optimizer variables), the filter and a copy of the
+ * data.  Two launches per step (csrc/ac_fit.hip); a run of equal batch sizes replays one captured graph.
+ * Additive to ABI 5: callers detect the feature by the symbols.
+ *
+ * bcmpc_acfit_create refuses, before any HIP call (csrc/ac_fit_plan.cpp), with BCMPC_ERR_UNSUPPORTED: n_layers
+ * outside [1, 4], hidden outside [1, 256], state_dim outside [1, 32], a policy head's out_dim outside [1, 16], a
+ * value head's out_dim != 1; with BCMPC_ERR_ARG: null pointers, a head other than the two, batch_size < 1, betas
+ * outside [0, 1), epsilon negative or not finite. */
+enum { BCMPC_ACFIT_POLICY = 0, BCMPC_ACFIT_VALUE = 1 };
+#define BCMPC_ACFIT_MAX_LAYERS 4
+#define BCMPC_ACFIT_MAX_HIDDEN 256
+typedef struct bcmpc_acfit_config {
+    int32_t state_dim;     /* S */
+    int32_t out_dim;       /* A (policy head) or 1 (value head) */
+    int32_t hidden;        /* true width, no padding */
+    int32_t n_layers;      /* L hidden layers */
+    int32_t head;          /* BCMPC_ACFIT_POLICY / BCMPC_ACFIT_VALUE */
+    int32_t batch_size;    /* rows per step the buffers are first sized for (a larger batch grows them) */
+    int32_t device;
+    float beta1, beta2, epsilon;   /* tf.train.AdamOptimizer defaults 0.9, 0.999, 1e-8 */
+} bcmpc_acfit_config;
+
+typedef struct bcmpc_acfit bcmpc_acfit;
+
+int bcmpc_acfit_create(const bcmpc_acfit_config* cfg, bcmpc_acfit** out);
+int bcmpc_acfit_destroy(bcmpc_acfit* f);
+/* L + 1 kernels (TF layout [in, out]) and biases; the Adam slots and beta powers are kept */
+int bcmpc_acfit_set_params(bcmpc_acfit* f, const float* const* kernels, const float* const* biases);
+int bcmpc_acfit_get_params(bcmpc_acfit* f, float* const* kernels, float* const* biases);
+/* the observation filter's f32 mean / std [S] (std > 0, both finite: else BCMPC_ERR_ARG) */
+int bcmpc_acfit_set_filter(bcmpc_acfit* f, const float* ob_mean, const float* ob_std);
+/* n rows of observations [n][S] and targets [n][out_dim] (actions / returns), f64, copied to the device */
+int bcmpc_acfit_set_data(bcmpc_acfit* f, const double* obs, const double* targets, int64_t n);
+/* `iterations` Adam steps at `learning_rate` (read from device memory by the kernels: a new rate needs no new
+ * graph); step i uses batch_sizes[i] rows, their indices concatenated in `indices`; losses (optional, host,
+ * [iterations]) = each step's loss before its update.  BCMPC_ERR_ARG: a batch size < 1, an index outside the
+ * data, a learning rate that is not finite.  BCMPC_ERR_STATE: parameters, filter or data not set. */
+int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch_sizes, int32_t iterations,
+                    float learning_rate, float* losses);
+/* 0: the last run launched its steps one by one (ragged batches, BCMPC_ACFIT_GRAPH=0); n >= 1: it replayed a
+ * captured graph, the n-th this fitter has captured (a new capture: another step count or batch size, an index,
+ * loss or data buffer that moved) */
+int bcmpc_acfit_is_graph(const bcmpc_acfit* f);
+/* f32 words of LDS of the row kernel for a net shape, or -1 where bcmpc_acfit_create refuses it.  No device call. */
+int64_t bcmpc_acfit_lds_words(int32_t hidden, int32_t n_layers, int32_t state_dim, int32_t out_dim, int32_t head);
+const char* bcmpc_acfit_last_error(void);
+
+/* ------------------------------------------------------------------------
  * Candidate sharding over GPUs: one process per GPU, rank r owns the
  * global candidates [cand_offset, cand_offset + K).  The library owns the one
  * collective of a control step: a communicator attached to an engine makes every
