@@ -7,9 +7,9 @@ LIB      := bc_mpc_amd/libbcmpc.so
 # objects by how they compile: host units that see the kernels' launch headers (hipcc -x hip), plain C++ (g++),
 # every other one a kernel unit (.hip); OBJ in link order
 HOSTOBJ  := capi cost_terms engine_plan pack mt_draw planners
-CXXOBJ   := mt19937 mt_jump ac_fit_plan
+CXXOBJ   := mt19937 mt_jump ac_fit_plan ac_ppo_plan
 OBJ      := $(patsubst %,build/%.o,rollout rollout_grp rollout_x3 rollout_x3_plain rollout_pp rollout_team cem mppi batch \
-              plan_batch plan_noise plan_prop plan_knots mppi_ext term_cost terminal_value ensemble fit ac_fit $(HOSTOBJ) $(CXXOBJ) mt_device comm)
+              plan_batch plan_noise plan_prop plan_knots mppi_ext term_cost terminal_value ensemble fit ac_fit ac_ppo $(HOSTOBJ) $(CXXOBJ) mt_device comm)
 # header dependencies come from the compiler (build/*.d): a header rebuilds exactly the objects that include it
 DEPFLAGS := -MMD -MP
 

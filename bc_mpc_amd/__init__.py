@@ -17,11 +17,13 @@ from .ensemble import EnsembleDynamicsModel, EnsembleEngine
 from . import value
 from .value import ValueSpec
 from . import ac_fit
+from . import ppo
+from .ppo import gae, standardize
 from .actor_critic import MlpActorCritic
 
 __all__ = ["Controller", "MPCcontroller", "MPCcontrollerPolicyNet", "MPCcontrollerReward",
            "MPCcontrollerPolicyNetReward", "MCTScontrollerPolicyNetReward", "CEMcontroller", "MPPIcontroller", "RandomController", "PolicySpec", "cheetah_cost_fn",
            "trajectory_cost_fn", "TermCost", "cheetah_terms", "MLPSpec", "RolloutEngine", "StepResult", "BatchResult",
-           "EnsembleEngine", "EnsembleDynamicsModel", "ValueSpec", "MlpActorCritic"]
+           "EnsembleEngine", "EnsembleDynamicsModel", "ValueSpec", "MlpActorCritic", "gae", "standardize"]
 
 _lib.load()   # fail loudly at import when the HIP library is missing

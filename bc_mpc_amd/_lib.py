@@ -242,6 +242,15 @@ class FitConfig(ctypes.Structure):
     ]
 
 
+class AcPpoConfig(ctypes.Structure):
+    """bcmpc_acppo_config: the PPO optimizer's Adam constants (bc_mpc_amd/ppo.py)."""
+    _fields_ = [
+        ("beta1", ctypes.c_float),
+        ("beta2", ctypes.c_float),
+        ("epsilon", ctypes.c_float),
+    ]
+
+
 class AcFitConfig(ctypes.Structure):
     """bcmpc_acfit_config: one head of the actor-critic fitter (bc_mpc_amd/ac_fit.py)."""
     _fields_ = [
@@ -505,6 +514,25 @@ SIGNATURES = [
     ("bcmpc_acfit_lds_words", ctypes.c_int64,
      [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     ("bcmpc_acfit_last_error", ctypes.c_char_p, []),
+    ("bcmpc_acppo_create", ctypes.c_int,
+     [ctypes.POINTER(AcPpoConfig), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bcmpc_acppo_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_acppo_set_logstd", ctypes.c_int, [ctypes.c_void_p, _FP]),
+    ("bcmpc_acppo_get_logstd", ctypes.c_int, [ctypes.c_void_p, _FP]),
+    ("bcmpc_acppo_set_old", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_FP), ctypes.POINTER(_FP), _FP, _FP, _FP]),
+    ("bcmpc_acppo_set_data", ctypes.c_int, [ctypes.c_void_p, _DP, _FP, _FP, _FP, ctypes.c_int64]),
+    ("bcmpc_acppo_run", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_float,
+      ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_float,
+      _FP, _FP]),
+    ("bcmpc_acppo_is_graph", ctypes.c_int, [ctypes.c_void_p]),
+    ("bcmpc_acppo_check_pair", ctypes.c_int,
+     [ctypes.POINTER(AcPpoConfig), ctypes.POINTER(AcFitConfig), ctypes.POINTER(AcFitConfig)]),
+    ("bcmpc_acppo_check_run", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
+      ctypes.c_float, ctypes.c_float]),
+    ("bcmpc_acppo_lds_words", ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("bcmpc_acppo_last_error", ctypes.c_char_p, []),
     ("bcmpc_comm_unique_id", ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     ("bcmpc_comm_init", ctypes.c_int,
      [ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),

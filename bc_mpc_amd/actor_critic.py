@@ -3,7 +3,10 @@
 The container the controllers consume (``policy_net=``, ``policy_prior=``, ``terminal_value=``) and the package can
 train: ``fit_bc`` clones (ob, ac) pairs into the policy head (``update_op_bc``, ppo_bc_policy.py:52, 114, 146-151;
 train_mpc_ppo.py:358-372), ``fit_value`` regresses the critic on returns (``vf_loss``, ppo_bc_policy.py:108).  Both
-run on the device (csrc/ac_fit.hip); ``ac_fit.py`` is their definition.
+run on the device (csrc/ac_fit.hip); ``ac_fit.py`` is their definition.  ``fit_ppo`` / ``lossandupdate_ppo`` make
+the clipped-surrogate step of ``lossandupdate_ppo`` (ppo_bc_policy.py:90-144) against the policy frozen by
+``assign_old_eq_new``, optionally interleaved with BC steps (train_mpc_ppo.py:355-372), on the device
+(csrc/ac_ppo.hip); ``ppo.py`` is its definition.
 
 * ``pol/`` and ``vf/`` stacks in TF layout, f32: ``fc1..fcL`` tanh then ``final``; ``normc`` initialisation
   (baselines ``U.normc_initializer``: a standard normal draw, every column scaled to norm ``std``), std 1.0 for the
@@ -15,7 +18,11 @@ run on the device (csrc/ac_fit.hip); ``ac_fit.py`` is their definition.
   ``value.extract`` trust it and the engines' setters re-upload exactly when something changed, without a digest.
 * A BC step moves only ``pol/fc*`` and ``pol/final``; ``logstd``, ``vf/`` and the filter get no gradient (the BC
   loss does not reach them).  A value step moves only ``vf/``.  Each head has its own Adam slots and beta powers,
-  on the device for the container's life.
+  on the device for the container's life.  A PPO step moves ``pol/``, ``vf/`` and ``logstd`` under a third
+  optimizer (``update_op_ppo``) with its own slots and one pair of beta powers; it trains in place on the two
+  heads' device weights.
+* The old policy (``assign_old_eq_new``) is a copy of ``pol/``, ``logstd`` and the filter's mean / std.  The engines
+  do not see it, so taking it does not bump ``version``.
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import ac_fit
+from . import ac_fit, ppo
 from .engine import PolicySpec
 from .value import ValueSpec, terminal_values
 
@@ -82,7 +89,7 @@ def _dim(space) -> int:
 
 class MlpActorCritic:
     def __init__(self, env, hid_size: int = 128, num_hid_layers: int = 2, seed: Optional[int] = None,
-                 device: int = 0):
+                 device: int = 0, clip_param: float = 0.2, entcoeff: float = 0.0):
         S, A = _dim(env.observation_space), _dim(env.action_space)
         ac_fit.check_shape("policy", S, A, int(hid_size), int(num_hid_layers))
         self.ob_dim, self.ac_dim = S, A
@@ -99,7 +106,10 @@ class MlpActorCritic:
         self.logstd = np.zeros(A, np.float32)
         self.version = 0
         self._fitters = {}                                         # head -> [fitter, params stamp, filter stamp]
-        self._stamp = {"policy": 0, "value": 0, "filter": 0}       # what the device copies are compared with
+        self._stamp = {"policy": 0, "value": 0, "filter": 0, "logstd": 0, "old": 0}   # what the device copies are compared with
+        self.clip_param, self.entcoeff = float(clip_param), float(entcoeff)
+        self._old = None                                           # assign_old_eq_new's copies
+        self._ppo = None                                           # [trainer, logstd stamp, old stamp]
         self.ob_rms = RunningMeanStd((S,), on_change=self._bump)
 
     # ------------------------------------------------------------ state ---
@@ -156,6 +166,7 @@ class MlpActorCritic:
             self._stamp["value"] += 1
         if "logstd" in new:
             self.logstd = new["logstd"]
+            self._stamp["logstd"] += 1
         if "ob_rms" in new:
             self.ob_rms.sum, self.ob_rms.sumsq, self.ob_rms.count = new["ob_rms"]
             self._stamp["filter"] += 1
@@ -276,7 +287,101 @@ class MlpActorCritic:
         from .fit import sample_batches
         return self._run("value", o, t, sample_batches(o.shape[0], batch_size, iterations, rng), learning_rate)
 
+    # -------------------------------------------------------------- PPO ---
+    def assign_old_eq_new(self) -> None:
+        """Freeze the current policy as the old one (ppo_bc_policy.py ``assign_old_eq_new``): copies of ``pol/``,
+        ``logstd`` and the filter's mean / std.  ``version`` stands: the engines do not see the old policy."""
+        self._old = dict(kernels=[k.copy() for k in self.pol_kernels], biases=[b.copy() for b in self.pol_biases],
+                         logstd=self.logstd.copy(), ob_mean=self.ob_rms.mean.copy(), ob_std=self.ob_rms.std.copy())
+        self._stamp["old"] += 1
+
+    def _make_trainer(self, policy_fitter, value_fitter) -> "ppo.PpoTrainer":
+        return ppo.PpoTrainer(policy_fitter, value_fitter)
+
+    def _trainer(self) -> "ppo.PpoTrainer":
+        """The device trainer over both heads' fitters with the container's weights, filter, logstd and old policy
+        on the device."""
+        pf, vf = self._fitter("policy"), self._fitter("value")
+        if self._ppo is None:
+            self._ppo = [self._make_trainer(pf, vf), None, None]
+        t = self._ppo[0]
+        if self._ppo[1] != self._stamp["logstd"]:
+            t.set_logstd(self.logstd)
+            self._ppo[1] = self._stamp["logstd"]
+        if self._ppo[2] != self._stamp["old"]:
+            o = self._old
+            t.set_old(o["kernels"], o["biases"], o["ob_mean"], o["ob_std"], o["logstd"])
+            self._ppo[2] = self._stamp["old"]
+        return t
+
+    def _run_ppo(self, data, batches, lr, eps, entcoeff, bc=None) -> np.ndarray:
+        t = self._trainer()
+        t.set_data(*data)
+        if bc is None:
+            losses = t.run(batches, lr, eps, entcoeff)
+        else:
+            (bobs, bacs), bbatches, blr = bc
+            self._fitters["policy"][0].set_data(bobs, bacs)
+            losses, _bc_losses = t.run(batches, lr, eps, entcoeff, bc_batches=bbatches, bc_lr=blr)
+        self.pol_kernels, self.pol_biases = self._fitters["policy"][0].get_params()
+        self.vf_kernels, self.vf_biases = self._fitters["value"][0].get_params()
+        self.logstd = t.get_logstd()
+        self.version += 1                                     # (the device copies are this result: their stamps stand)
+        return losses
+
+    def _checked_ppo(self, what: str, ob, ac, atarg, ret):
+        if self._old is None:
+            raise ValueError(f"{what}: assign_old_eq_new has not been called")
+        o, a = self._checked(what, ob, ac, self.ac_dim)
+        _, at = self._checked(what, o, atarg, 1)
+        _, rt = self._checked(what, o, ret, 1)
+        return o, a, at[:, 0], rt[:, 0]
+
+    def fit_ppo(self, ob, ac, atarg, ret, iterations: int, batch_size: int, learning_rate, clip_param: float = 0.2,
+                entcoeff: float = 0.0, cur_lrmult: float = 1.0, bc_data=None, bc_learning_rate=None,
+                rng=random) -> np.ndarray:
+        """``iterations`` PPO steps (``lossandupdate_ppo``) against the policy of ``assign_old_eq_new`` on batches of
+        the rows ``ob`` [n, S], ``ac`` [n, A], ``atarg`` [n], ``ret`` [n]; with ``bc_data = (obs, acs)`` every PPO
+        step is followed by one BC step at ``bc_learning_rate``.  Per iteration ``rng.sample(range(n), k)`` draws
+        the PPO rows, then (with ``bc_data``) one draw over the BC data: the two ``DataBufferGeneral.sample`` calls
+        of train_mpc_ppo.py:363, 368 in their order.  The learning rates are used as given (the caller multiplies
+        by ``cur_lrmult``, as the reference does); ``cur_lrmult`` scales only the clip range.  Returns the losses
+        [iterations, 6] f32: pol_surr, pol_entpen, vf_loss, kl, ent, bc_loss, each before its update."""
+        iterations, batch_size = self._sizes(iterations, batch_size)
+        o, a, at, rt = self._checked_ppo("fit_ppo", ob, ac, atarg, ret)
+        lr, eps, ec = float(learning_rate), float(clip_param) * float(cur_lrmult), float(entcoeff)
+        if not (np.isfinite(lr) and np.isfinite(eps) and np.isfinite(ec)) or eps < 0:
+            raise ValueError("fit_ppo: learning_rate, clip_param * cur_lrmult >= 0 and entcoeff must be finite")
+        bc = None
+        if bc_data is not None:
+            if not isinstance(bc_data, tuple) or len(bc_data) != 2:
+                raise ValueError("fit_ppo: bc_data is an (obs, acs) tuple")
+            if bc_learning_rate is None or not np.isfinite(float(bc_learning_rate)):
+                raise ValueError("fit_ppo: bc_data needs a finite bc_learning_rate")
+            bc = self._checked("fit_ppo", bc_data[0], bc_data[1], self.ac_dim)
+        n, k = o.shape[0], min(batch_size, o.shape[0])
+        batches, bbatches = [], []
+        for _ in range(iterations):
+            batches.append(np.asarray(rng.sample(range(n), k), dtype=np.int64))
+            if bc is not None:
+                nb = bc[0].shape[0]
+                bbatches.append(np.asarray(rng.sample(range(nb), min(batch_size, nb)), dtype=np.int64))
+        return self._run_ppo((o, a, at, rt), batches, lr, eps, ec,
+                             None if bc is None else (bc, bbatches, float(bc_learning_rate)))
+
+    def lossandupdate_ppo(self, ob, ac, atarg, ret, cur_lrmult, learning_rate) -> np.ndarray:
+        """One PPO step on the whole batch (ppo_bc_policy.py:134-144, its name and argument order) with the
+        container's ``clip_param`` and ``entcoeff``; returns the six losses (before the update)."""
+        o, a, at, rt = self._checked_ppo("lossandupdate_ppo", ob, ac, atarg, ret)
+        lr, eps = float(learning_rate), self.clip_param * float(cur_lrmult)
+        if not (np.isfinite(lr) and np.isfinite(eps)) or eps < 0:
+            raise ValueError("lossandupdate_ppo: learning_rate and clip_param * cur_lrmult >= 0 must be finite")
+        return self._run_ppo((o, a, at, rt), [np.arange(o.shape[0], dtype=np.int64)], lr, eps, self.entcoeff)[0]
+
     def close(self) -> None:
+        if self._ppo is not None:                             # before the fitters it is built over
+            self._ppo[0].close()
+            self._ppo = None
         for ent in self._fitters.values():
             ent[0].close()
         self._fitters = {}

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/bcmpc.h"
+#include "ac_fit_internal.h"
 #include "ac_fit_plan.h"
 
 namespace bcmpc::acfit {
@@ -374,41 +375,15 @@ __global__ __launch_bounds__(256) void acfit_params_kernel(const Args a) {
 using namespace bcmpc::acfit;
 
 // ------------------------------------------------------------------ C ABI ---
-struct bcmpc_acfit {
-    Plan plan;
-    hipStream_t stream = nullptr;
-    float *d_w = nullptr, *d_wt = nullptr, *d_m = nullptr, *d_v = nullptr;
-    float *d_x0 = nullptr, *d_dp = nullptr, *d_act = nullptr, *d_dzs = nullptr, *d_lpart = nullptr;
-    int32_t bcap = 0;                             // rows the activation buffers hold
-    float* d_filt = nullptr;                      // [2][32] ob_mean, ob_std: one address for the fitter's life
-    float* d_state = nullptr;                     // [beta1_power, beta2_power, learning rate]
-    float h_state[3] = {0.f, 0.f, 0.f};           // their host mirror, the upload's source
-    int32_t* d_iter = nullptr;
-    Tile* d_tiles = nullptr;
-    double *d_obs = nullptr, *d_tgt = nullptr;
-    int64_t n_data = 0, data_cap = 0;
-    int64_t* d_idx = nullptr; int64_t idx_cap = 0;
-    float* d_loss = nullptr; int32_t loss_cap = 0;
-    // one captured graph of a whole uniform-batch run, reused while everything it holds by address or by value
-    // stands: the step count and batch size, the index and loss buffers (the key below); the data and activation
-    // buffers (acfit_drop_graph where they are reallocated).  The filter and the learning rate are read from
-    // device memory at fixed addresses: new values need no new graph.
-    hipGraphExec_t graph = nullptr;
-    int32_t graph_iters = 0, graph_b = 0;
-    const void* graph_idx = nullptr;
-    const void* graph_loss = nullptr;
-    int32_t captures = 0;
-    bool last_graph = false;
-    bool has_weights = false, has_filter = false;
-};
+namespace bcmpc::acfit {
 
-static void acfit_drop_graph(bcmpc_acfit* f) {
+void acfit_drop_graph(bcmpc_acfit* f) {
     if (f->graph) (void)hipGraphExecDestroy(f->graph);
     f->graph = nullptr;
 }
 
 // activation buffers for batches of up to `rows` rows (no run is in flight: bcmpc_acfit_run synchronises)
-static bool acfit_reserve(bcmpc_acfit* f, int32_t rows) {
+bool acfit_reserve(bcmpc_acfit* f, int32_t rows) {
     if (rows <= f->bcap) return true;
     acfit_drop_graph(f);
     for (float** p : {&f->d_x0, &f->d_dp, &f->d_act, &f->d_dzs, &f->d_lpart})
@@ -423,6 +398,8 @@ static bool acfit_reserve(bcmpc_acfit* f, int32_t rows) {
     f->bcap = rows;
     return true;
 }
+
+}  // namespace bcmpc::acfit
 
 extern "C" {
 
@@ -553,8 +530,12 @@ int bcmpc_acfit_set_data(bcmpc_acfit* f, const double* obs, const double* target
     return BCMPC_OK;
 }
 
+}  // extern "C"
+
+namespace bcmpc::acfit {
+
 // one Adam step: 2 launches
-static int acfit_step(bcmpc_acfit* f, const int64_t* d_idx, int stride, int B) {
+int acfit_step(bcmpc_acfit* f, hipStream_t stream, const int64_t* d_idx, int stride, int B) {
     const Plan& p = f->plan;
     Args a{};
     a.obs = f->d_obs; a.tgt = f->d_tgt;
@@ -567,22 +548,15 @@ static int acfit_step(bcmpc_acfit* f, const int64_t* d_idx, int stride, int B) {
     a.B = B; a.Bcap = f->bcap; a.S = p.S; a.N = p.N; a.L = p.L; a.h = p.h; a.head = p.cfg.head; a.ld = p.ld;
     a.b1 = p.cfg.beta1; a.b2 = p.cfg.beta2; a.eps = p.cfg.epsilon;
     hipLaunchKernelGGL(acfit_rows_kernel, dim3((B + kRows - 1) / kRows), dim3(64 * kWaves), p.lds_words * 4,
-                       f->stream, a);
+                       stream, a);
     if (hipGetLastError() != hipSuccess) return fail(BCMPC_ERR_HIP, "acfit_rows_kernel launch failed");
-    hipLaunchKernelGGL(acfit_params_kernel, dim3((unsigned)p.tiles.size()), dim3(256), 0, f->stream, a);
+    hipLaunchKernelGGL(acfit_params_kernel, dim3((unsigned)p.tiles.size()), dim3(256), 0, stream, a);
     if (hipGetLastError() != hipSuccess) return fail(BCMPC_ERR_HIP, "acfit_params_kernel launch failed");
     return BCMPC_OK;
 }
 
-int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch_sizes, int32_t iterations,
-                    float learning_rate, float* losses) {
-    if (!f) return fail(BCMPC_ERR_ARG, "null argument");
-    int64_t total = 0;
-    int32_t bmax = 0;
-    if (const int rc = check_run(indices, batch_sizes, iterations, learning_rate, f->n_data, &total, &bmax)) return rc;
-    if (!f->has_weights) return fail(BCMPC_ERR_STATE, "bcmpc_acfit_set_params has not been called");
-    if (!f->has_filter) return fail(BCMPC_ERR_STATE, "bcmpc_acfit_set_filter has not been called");
-    if (iterations == 0) return BCMPC_OK;
+int acfit_prepare(bcmpc_acfit* f, hipStream_t stream, const int64_t* indices, int64_t total, int32_t bmax,
+                  int32_t iterations, float learning_rate) {
     if (hipSetDevice(f->plan.cfg.device) != hipSuccess) return fail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (!acfit_reserve(f, bmax)) return fail(BCMPC_ERR_HIP, "activation buffer allocation failed");
     if (total > f->idx_cap) {
@@ -593,7 +567,7 @@ int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch
             return fail(BCMPC_ERR_HIP, "index buffer allocation failed");
         f->idx_cap = total;
     }
-    if (hipMemcpyAsync(f->d_idx, indices, (size_t)total * 8, hipMemcpyHostToDevice, f->stream) != hipSuccess)
+    if (hipMemcpyAsync(f->d_idx, indices, (size_t)total * 8, hipMemcpyHostToDevice, stream) != hipSuccess)
         return fail(BCMPC_ERR_HIP, "index upload failed");
     if (iterations > f->loss_cap) {
         if (f->d_loss) (void)hipFree(f->d_loss);
@@ -605,22 +579,39 @@ int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch
     }
     // device step state: counter 0, the host mirror's beta powers, this run's learning rate
     f->h_state[2] = learning_rate;
-    if (hipMemsetAsync(f->d_iter, 0, 4, f->stream) != hipSuccess ||
-        hipMemcpyAsync(f->d_state, f->h_state, 12, hipMemcpyHostToDevice, f->stream) != hipSuccess)
+    if (hipMemsetAsync(f->d_iter, 0, 4, stream) != hipSuccess ||
+        hipMemcpyAsync(f->d_state, f->h_state, 12, hipMemcpyHostToDevice, stream) != hipSuccess)
         return fail(BCMPC_ERR_HIP, "step state upload failed");
+    return BCMPC_OK;
+}
+
+int acfit_finish(bcmpc_acfit* f, hipStream_t stream, int32_t iterations, float* losses) {
+    if (losses && hipMemcpyAsync(losses, f->d_loss, (size_t)iterations * 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
+        return fail(BCMPC_ERR_HIP, "loss download failed");
+    if (hipStreamSynchronize(stream) != hipSuccess) return fail(BCMPC_ERR_HIP, "fit failed");
+    for (int i = 0; i < iterations; ++i) {       // host mirror of the device beta powers (same f32 products)
+        f->h_state[0] *= f->plan.cfg.beta1;
+        f->h_state[1] *= f->plan.cfg.beta2;
+    }
+    return BCMPC_OK;
+}
+
+// the steps of a run: a uniform run as one captured graph (a single chain of kernel nodes on one stream),
+// anything else launched step by step
+static int acfit_enqueue(bcmpc_acfit* f, const int32_t* batch_sizes, int32_t iterations) {
     bool uniform = true;
     for (int i = 1; i < iterations; ++i) uniform = uniform && batch_sizes[i] == batch_sizes[0];
     const char* ge = std::getenv("BCMPC_ACFIT_GRAPH");
     const bool use_graph = uniform && !(ge && ge[0] == '0');
     if (use_graph) {
-        // the whole run as one graph: a single chain of kernel nodes on one stream
         if (!(f->graph && f->graph_iters == iterations && f->graph_b == batch_sizes[0] && f->graph_idx == f->d_idx &&
               f->graph_loss == f->d_loss)) {
             acfit_drop_graph(f);
             if (hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
                 return fail(BCMPC_ERR_HIP, "graph capture failed to start");
             int rc = BCMPC_OK;
-            for (int i = 0; i < iterations && rc == BCMPC_OK; ++i) rc = acfit_step(f, f->d_idx, batch_sizes[0], batch_sizes[0]);
+            for (int i = 0; i < iterations && rc == BCMPC_OK; ++i)
+                rc = acfit_step(f, f->stream, f->d_idx, batch_sizes[0], batch_sizes[0]);
             hipGraph_t g = nullptr;
             const hipError_t ec = hipStreamEndCapture(f->stream, &g);
             if (rc != BCMPC_OK || ec != hipSuccess) {
@@ -640,20 +631,27 @@ int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch
     } else {
         int64_t pos = 0;
         for (int i = 0; i < iterations; ++i) {
-            const int rc = acfit_step(f, f->d_idx + pos, 0, batch_sizes[i]);
+            const int rc = acfit_step(f, f->stream, f->d_idx + pos, 0, batch_sizes[i]);
             if (rc != BCMPC_OK) return rc;
             pos += batch_sizes[i];
         }
     }
     f->last_graph = use_graph;
-    if (losses && hipMemcpyAsync(losses, f->d_loss, (size_t)iterations * 4, hipMemcpyDeviceToHost, f->stream) != hipSuccess)
-        return fail(BCMPC_ERR_HIP, "loss download failed");
-    if (hipStreamSynchronize(f->stream) != hipSuccess) return fail(BCMPC_ERR_HIP, "fit failed");
-    for (int i = 0; i < iterations; ++i) {       // host mirror of the device beta powers (same f32 products)
-        f->h_state[0] *= f->plan.cfg.beta1;
-        f->h_state[1] *= f->plan.cfg.beta2;
-    }
     return BCMPC_OK;
 }
 
-}  // extern "C"
+}  // namespace bcmpc::acfit
+
+extern "C" int bcmpc_acfit_run(bcmpc_acfit* f, const int64_t* indices, const int32_t* batch_sizes, int32_t iterations,
+                               float learning_rate, float* losses) {
+    if (!f) return fail(BCMPC_ERR_ARG, "null argument");
+    int64_t total = 0;
+    int32_t bmax = 0;
+    if (const int rc = check_run(indices, batch_sizes, iterations, learning_rate, f->n_data, &total, &bmax)) return rc;
+    if (!f->has_weights) return fail(BCMPC_ERR_STATE, "bcmpc_acfit_set_params has not been called");
+    if (!f->has_filter) return fail(BCMPC_ERR_STATE, "bcmpc_acfit_set_filter has not been called");
+    if (iterations == 0) return BCMPC_OK;
+    if (const int rc = acfit_prepare(f, f->stream, indices, total, bmax, iterations, learning_rate)) return rc;
+    if (const int rc = acfit_enqueue(f, batch_sizes, iterations)) return rc;
+    return acfit_finish(f, f->stream, iterations, losses);
+}

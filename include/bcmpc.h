@@ -1124,6 +1124,60 @@ int64_t bcmpc_acfit_lds_words(int32_t hidden, int32_t n_layers, int32_t state_di
 const char* bcmpc_acfit_last_error(void);
 
 /* ------------------------------------------------------------------------
+ * PPO on the actor-critic (bc_mpc_amd/ppo.py is the definition): the reference's lossandupdate_ppo
+ * (ppo_bc_policy.py:90-144), one Adam step on pol_surr + pol_entpen + vf_loss over pol/, vf/ and logstd against a
+ * frozen old policy.  A trainer is built OVER a policy and a value fitter: it trains in place on their device
+ * weights (and their transposed copies) and uses their activation buffers; it owns the PPO Adam slots of both
+ * stacks, logstd and its slots, one pair of beta powers, the old snapshot (old policy weights, old filter,
+ * oldlogstd, oldmean [n][A]) and the PPO data.  The fitters must outlive the trainer.  Two launches per step
+ * (csrc/ac_ppo.hip: both stacks in one launch pair); with a BC block every PPO step is followed by the policy
+ * fitter's own BC step (its kernels, its Adam state) in the same chain.  A run of equal batch sizes replays one
+ * captured graph, a single chain of kernel nodes; lr, eps, entcoeff and the filter are read from device memory.
+ * Additive to ABI 5: callers detect the feature by the symbols.
+ *
+ * Refusals, before any HIP call (csrc/ac_ppo_plan.cpp): BCMPC_ERR_ARG for null pointers, fitters of the wrong
+ * heads or of different state_dim / hidden / n_layers / device, betas outside [0, 1), a negative or non-finite
+ * epsilon, a non-finite learning rate, eps or entcoeff, eps < 0, non-finite logstd / old policy / data, a batch
+ * size < 1, an index outside the data; BCMPC_ERR_STATE for a run before set_logstd, set_old or set_data. */
+typedef struct bcmpc_acppo_config {
+    float beta1, beta2, epsilon;   /* the PPO optimizer's own Adam constants */
+} bcmpc_acppo_config;
+
+typedef struct bcmpc_acppo bcmpc_acppo;
+
+int bcmpc_acppo_create(const bcmpc_acppo_config* cfg, bcmpc_acfit* policy_fitter, bcmpc_acfit* value_fitter,
+                       bcmpc_acppo** out);
+int bcmpc_acppo_destroy(bcmpc_acppo* t);
+/* logstd [A]; the Adam slots and beta powers are kept */
+int bcmpc_acppo_set_logstd(bcmpc_acppo* t, const float* logstd);
+int bcmpc_acppo_get_logstd(bcmpc_acppo* t, float* logstd);
+/* the old policy (assign_old_eq_new): L + 1 kernels and biases of pol/, its filter [S] and its logstd [A] */
+int bcmpc_acppo_set_old(bcmpc_acppo* t, const float* const* kernels, const float* const* biases,
+                        const float* ob_mean, const float* ob_std, const float* oldlogstd);
+/* n rows: observations [n][S] f64, actions [n][A], advantages [n] and returns [n] as the f32 they are fed as */
+int bcmpc_acppo_set_data(bcmpc_acppo* t, const double* obs, const float* acs, const float* atarg, const float* ret,
+                         int64_t n);
+/* `iterations` PPO steps; step i uses batch_sizes[i] rows of the PPO data.  eps = clip_param * cur_lrmult.
+ * bc_indices != NULL: step i is followed by one BC step of the policy fitter on bc_batch_sizes[i] rows of ITS data
+ * (bcmpc_acfit_set_data) at bc_learning_rate.  losses [iterations][6] = pol_surr, pol_entpen, vf_loss, kl, ent,
+ * bc_loss before each update; bc_losses [iterations] (optional) the BC steps' losses.  oldmean is evaluated once
+ * per call, by the row kernel's forward-only mode over all n rows. */
+int bcmpc_acppo_run(bcmpc_acppo* t, const int64_t* indices, const int32_t* batch_sizes, int32_t iterations,
+                    float learning_rate, float eps, float entcoeff, const int64_t* bc_indices,
+                    const int32_t* bc_batch_sizes, float bc_learning_rate, float* losses, float* bc_losses);
+/* 0: the last run launched its steps one by one (ragged batches, BCMPC_ACPPO_GRAPH=0); n >= 1: it replayed a
+ * captured graph, the n-th this trainer has captured */
+int bcmpc_acppo_is_graph(const bcmpc_acppo* t);
+/* the checks alone, no device call: the pair of fitter configs; a run's arguments; the row kernel's LDS words
+ * (-1 where refused) */
+int bcmpc_acppo_check_pair(const bcmpc_acppo_config* cfg, const bcmpc_acfit_config* policy,
+                           const bcmpc_acfit_config* value);
+int bcmpc_acppo_check_run(const int64_t* indices, const int32_t* batch_sizes, int32_t iterations, int64_t n_data,
+                          float learning_rate, float eps, float entcoeff);
+int64_t bcmpc_acppo_lds_words(int32_t hidden, int32_t n_layers, int32_t state_dim, int32_t action_dim);
+const char* bcmpc_acppo_last_error(void);
+
+/* ------------------------------------------------------------------------
  * Candidate sharding over GPUs: one process per GPU, rank r owns the
  * global candidates [cand_offset, cand_offset + K).  The library owns the one
  * collective of a control step: a communicator attached to an engine makes every
