@@ -18,8 +18,6 @@
 // row blocks' partials in one fixed order and scales its tile's batch sum before Adam: no third launch, no
 // grid-wide barrier, no workgroup waits for another.  The kernel boundary is the only global synchronisation.
 // At loss == 0 the scalar is inf and every sum is 0: NaN parameters, as TF's SqrtGrad gives.
-//
-// The device helpers (rows_gemm and friends) are this unit's own copies of fit.hip's: fit.hip stays as it is.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,14 +29,16 @@
 #include "../../include/bcmpc.h"
 #include "ac_fit_internal.h"
 #include "ac_fit_plan.h"
+#include "train_rows.h"
 
 namespace bcmpc::acfit {
 
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-constexpr int kFK = 8;                      // k-steps (of 4) per weight chunk
-constexpr int kFRing = 4;                   // weight chunks in flight per wave
-constexpr int kPK = 32;                     // batch steps (of 4) per load batch of a weight-gradient tile
+using rows::adam_elem;                      // the row-tile GEMM, the wave sum and Adam: train_rows.h
+using rows::f4v;
+using rows::kPK;
+using rows::rows_gemm;
+using rows::wave_sum_fast;
+static_assert(rows::kWaves == kWaves, "the plan's LDS layout and the row GEMM agree on the workgroup's waves");
 
 struct Args {
     const double* obs; const double* tgt;               // the data [n][S], [n][N]
@@ -53,119 +53,6 @@ struct Args {
     int32_t B, Bcap, S, N, L, h, head, ld;
     float b1, b2, eps;
 };
-
-// one chunk of kFK k-steps of the B operand through a buffer descriptor: one 32-bit lane offset (vo) for the
-// whole GEMM, the chunk position in the scalar offset; rows past the matrix and the masked columns (vo beyond
-// the range) read 0
-__device__ __forceinline__ void rows_load(float* b, __amdgpu_buffer_rsrc_t rsrc, int vo, int kb, int kstride) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s)
-        b[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, (kb + 4 * s) * kstride, 0));
-}
-
-__device__ __forceinline__ f4v rows_mma(f4v acc, const float* b, const float* X, int kb, int K, int r16, int k4,
-                                        int lds) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s) {
-        const int k = kb + 4 * s + k4;
-        const float x = k < K ? X[r16 * lds + k] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, b[s], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-// a real vmcnt(0) once a GEMM's loads are consumed, so that the row phase after it does not wait for its own
-// global stores at register reuse (fit.hip rows_drained)
-__device__ __forceinline__ void rows_drained() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-}
-
-// acc += sum over k in [k0, k1) of X[r][k] W[k*ldw + n] for this lane's column n (a 16-wide tile), kFRing chunks
-// of weights in flight
-__device__ __forceinline__ f4v rows_tile(f4v acc, const float* X, int k0, int k1, __amdgpu_buffer_rsrc_t rsrc,
-                                         int vo, int ldw, int r16, int k4, int lds) {
-    constexpr int CK = 4 * kFK;
-    float ring[kFRing][kFK];
-#pragma unroll
-    for (int j = 0; j < kFRing; ++j)
-        if (k0 + j * CK < k1) rows_load(ring[j], rsrc, vo, k0 + j * CK, 4 * ldw);
-    for (int kb = k0; kb < k1; kb += kFRing * CK) {
-#pragma unroll
-        for (int j = 0; j < kFRing; ++j) {
-            const int kc = kb + j * CK;
-            if (kc < k1) {
-                acc = rows_mma(acc, ring[j], X, kc, k1, r16, k4, lds);
-                if (kc + kFRing * CK < k1) rows_load(ring[j], rsrc, vo, kc + kFRing * CK, 4 * ldw);
-            }
-        }
-    }
-    return acc;
-}
-
-// C[r][n] = sum_k X[r][k] W[k*ldw + n] (+ bias[n]) for the 16 LDS rows X (stride lds), n < N, W row-major
-// [K][ldw].  16-column tiles over the 16 waves; with at most 8 tiles (N <= 128) the K range is split over the
-// idle waves and the partials (LDS, `kp`) are added in wave order.
-__device__ __forceinline__ void rows_gemm(const float* X, int K, const float* __restrict__ W, int ldw, int N,
-                                          const float* __restrict__ bias, float* C, int lds, float* kp) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r16 = lane & 15, k4 = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, K * ldw * 4, 0x00020000);
-    const int nt = (N + 15) / 16;
-    if (nt * 2 > kWaves) {
-        for (int n0 = 16 * wv; n0 < N; n0 += 16 * kWaves) {
-            const int n = n0 + r16;
-            const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-            const float bv = bias && n < N ? bias[n] : 0.f;          // requested before the weights
-            f4v acc = rows_tile((f4v){0.f, 0.f, 0.f, 0.f}, X, 0, K, rsrc, vo, ldw, r16, k4, lds);
-            rows_drained();
-            if (n < N)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) C[(4 * k4 + r) * lds + n] = bias ? acc[r] + bv : acc[r];
-        }
-        return;
-    }
-    // K split: wave wv takes tile wv % nt, K slice wv / nt of ks (whole 4-k-steps)
-    const int ks = kWaves / nt;
-    const int t = wv % nt, q = wv / nt;
-    const int n = 16 * t + r16;
-    if (q < ks) {
-        const int kq = ((K + 4 * ks - 1) / (4 * ks)) * 4;       // slice length, multiple of 4
-        const int k0 = min(K, q * kq), k1 = min(K, k0 + kq);
-        const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-        f4v acc = (f4v){0.f, 0.f, 0.f, 0.f};
-        if (k0 < k1) acc = rows_tile(acc, X, k0, k1, rsrc, vo, ldw, r16, k4, lds);
-        rows_drained();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) kp[(q * nt + t) * 256 + (4 * k4 + r) * 16 + r16] = acc[r];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 16 * nt * 16; i += 64 * kWaves) {
-        const int tt = i / 256, e = i % 256, r = e / 16, c = 16 * tt + e % 16;
-        if (c < N) {
-            float s = 0.f;
-            for (int qq = 0; qq < ks; ++qq) s += kp[(qq * nt + tt) * 256 + e];
-            C[r * lds + c] = bias ? s + bias[c] : s;
-        }
-    }
-}
-
-// wave sum on DPP butterflies inside each 16-lane row, then the four row totals in a fixed order
-template <int CTRL>
-__device__ __forceinline__ float dpp_t(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float wave_sum_fast(float v) {
-    v += dpp_t<0xB1>(v);                    // quad_perm [1,0,3,2]
-    v += dpp_t<0x4E>(v);                    // quad_perm [2,3,0,1]
-    v += dpp_t<0x124>(v);                   // row_ror 4
-    v += dpp_t<0x128>(v);                   // row_ror 8
-    const int b = __builtin_bit_cast(int, v);
-    return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))) +
-           (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48)));
-}
 
 __global__ __launch_bounds__(1024) void acfit_rows_kernel(const Args a) {
     extern __shared__ float sm[];
@@ -282,18 +169,6 @@ __global__ __launch_bounds__(1024) void acfit_rows_kernel(const Args a) {
     }
 }
 
-__device__ __forceinline__ float adam_elem(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                           size_t i, float gi, float w0, float m0, float v0, float lr_t, float b1,
-                                           float b2, float eps) {
-    const float mi = m0 + (gi - m0) * (1.0f - b1);
-    const float vi = v0 + (gi * gi - v0) * (1.0f - b2);
-    const float wi = w0 - __fdiv_rn(mi * lr_t, __fsqrt_rn(vi) + eps);
-    m[i] = mi;
-    v[i] = vi;
-    w[i] = wi;
-    return wi;
-}
-
 // one workgroup per task; its 4 waves take contiguous quarters of the batch and their partials are added in
 // wave order (deterministic)
 __global__ __launch_bounds__(256) void acfit_params_kernel(const Args a) {
@@ -373,37 +248,27 @@ __global__ __launch_bounds__(256) void acfit_params_kernel(const Args a) {
 }  // namespace bcmpc::acfit
 
 using namespace bcmpc::acfit;
+namespace train = bcmpc::train;
 
 // ------------------------------------------------------------------ C ABI ---
 namespace bcmpc::acfit {
 
-void acfit_drop_graph(bcmpc_acfit* f) {
-    if (f->graph) (void)hipGraphExecDestroy(f->graph);
-    f->graph = nullptr;
-}
-
 // activation buffers for batches of up to `rows` rows (no run is in flight: bcmpc_acfit_run synchronises)
 bool acfit_reserve(bcmpc_acfit* f, int32_t rows) {
     if (rows <= f->bcap) return true;
-    acfit_drop_graph(f);
-    for (float** p : {&f->d_x0, &f->d_dp, &f->d_act, &f->d_dzs, &f->d_lpart})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    f->bcap = 0;
+    f->graph.drop();
     const Plan& p = f->plan;
     const size_t B = (size_t)rows, nblk = (B + kRows - 1) / kRows;
-    if (hipMalloc(&f->d_x0, B * p.S * 4) != hipSuccess || hipMalloc(&f->d_dp, B * p.N * 4) != hipSuccess ||
-        hipMalloc(&f->d_act, (size_t)p.L * B * p.h * 4) != hipSuccess ||
-        hipMalloc(&f->d_dzs, (size_t)p.L * B * p.h * 4) != hipSuccess || hipMalloc(&f->d_lpart, nblk * 4) != hipSuccess)
-        return false;
-    f->bcap = rows;
-    return true;
+    return train::grow(&f->bcap, rows, {{&f->d_x0, B * p.S * 4}, {&f->d_dp, B * p.N * 4},
+                                        {&f->d_act, (size_t)p.L * B * p.h * 4},
+                                        {&f->d_dzs, (size_t)p.L * B * p.h * 4}, {&f->d_lpart, nblk * 4}});
 }
 
 }  // namespace bcmpc::acfit
 
 extern "C" {
 
-int bcmpc_acfit_is_graph(const bcmpc_acfit* f) { return f && f->last_graph ? f->captures : 0; }
+int bcmpc_acfit_is_graph(const bcmpc_acfit* f) { return f && f->last_graph ? f->graph.captures : 0; }
 
 int bcmpc_acfit_create(const bcmpc_acfit_config* c, bcmpc_acfit** out) {
     if (!c || !out) return fail(BCMPC_ERR_ARG, "null argument");
@@ -440,7 +305,7 @@ int bcmpc_acfit_create(const bcmpc_acfit_config* c, bcmpc_acfit** out) {
 int bcmpc_acfit_destroy(bcmpc_acfit* f) {
     if (!f) return BCMPC_OK;
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    acfit_drop_graph(f);
+    f->graph.drop();
     for (void* p : {(void*)f->d_w, (void*)f->d_wt, (void*)f->d_m, (void*)f->d_v, (void*)f->d_x0, (void*)f->d_dp,
                     (void*)f->d_act, (void*)f->d_dzs, (void*)f->d_lpart, (void*)f->d_filt, (void*)f->d_state,
                     (void*)f->d_iter, (void*)f->d_tiles, (void*)f->d_obs, (void*)f->d_tgt, (void*)f->d_idx,
@@ -494,10 +359,7 @@ int bcmpc_acfit_set_filter(bcmpc_acfit* f, const float* ob_mean, const float* ob
     if (!f) return fail(BCMPC_ERR_ARG, "null argument");
     if (const int rc = check_filter(ob_mean, ob_std, f->plan.S)) return rc;
     float hf[64];
-    for (int i = 0; i < 32; ++i) {
-        hf[i] = i < f->plan.S ? ob_mean[i] : 0.f;
-        hf[32 + i] = i < f->plan.S ? ob_std[i] : 1.f;
-    }
+    filter_image(ob_mean, ob_std, f->plan.S, hf);
     if (hipSetDevice(f->plan.cfg.device) != hipSuccess ||
         hipMemcpyAsync(f->d_filt, hf, sizeof(hf), hipMemcpyHostToDevice, f->stream) != hipSuccess ||
         hipStreamSynchronize(f->stream) != hipSuccess)
@@ -511,15 +373,10 @@ int bcmpc_acfit_set_data(bcmpc_acfit* f, const double* obs, const double* target
     const Plan& p = f->plan;
     if (hipSetDevice(p.cfg.device) != hipSuccess) return fail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > f->data_cap) {
-        acfit_drop_graph(f);                              // the graph holds the data buffers' addresses
-        for (double** q : {&f->d_obs, &f->d_tgt})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        f->data_cap = 0;
+        f->graph.drop();                                  // the graph holds the data buffers' addresses
         f->n_data = 0;
-        if (hipMalloc(&f->d_obs, (size_t)n * p.S * 8) != hipSuccess ||
-            hipMalloc(&f->d_tgt, (size_t)n * p.N * 8) != hipSuccess)
+        if (!train::grow(&f->data_cap, n, {{&f->d_obs, (size_t)n * p.S * 8}, {&f->d_tgt, (size_t)n * p.N * 8}}))
             return fail(BCMPC_ERR_HIP, "data buffer allocation failed");
-        f->data_cap = n;
     }
     if (n > 0 &&
         (hipMemcpyAsync(f->d_obs, obs, (size_t)n * p.S * 8, hipMemcpyHostToDevice, f->stream) != hipSuccess ||
@@ -559,24 +416,12 @@ int acfit_prepare(bcmpc_acfit* f, hipStream_t stream, const int64_t* indices, in
                   int32_t iterations, float learning_rate) {
     if (hipSetDevice(f->plan.cfg.device) != hipSuccess) return fail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (!acfit_reserve(f, bmax)) return fail(BCMPC_ERR_HIP, "activation buffer allocation failed");
-    if (total > f->idx_cap) {
-        if (f->d_idx) (void)hipFree(f->d_idx);
-        f->d_idx = nullptr;
-        f->idx_cap = 0;
-        if (hipMalloc(&f->d_idx, (size_t)total * 8) != hipSuccess)
-            return fail(BCMPC_ERR_HIP, "index buffer allocation failed");
-        f->idx_cap = total;
-    }
+    if (!train::grow(&f->idx_cap, total, {{&f->d_idx, (size_t)total * 8}}))
+        return fail(BCMPC_ERR_HIP, "index buffer allocation failed");
     if (hipMemcpyAsync(f->d_idx, indices, (size_t)total * 8, hipMemcpyHostToDevice, stream) != hipSuccess)
         return fail(BCMPC_ERR_HIP, "index upload failed");
-    if (iterations > f->loss_cap) {
-        if (f->d_loss) (void)hipFree(f->d_loss);
-        f->d_loss = nullptr;
-        f->loss_cap = 0;
-        if (hipMalloc(&f->d_loss, (size_t)iterations * 4) != hipSuccess)
-            return fail(BCMPC_ERR_HIP, "loss buffer allocation failed");
-        f->loss_cap = iterations;
-    }
+    if (!train::grow(&f->loss_cap, iterations, {{&f->d_loss, (size_t)iterations * 4}}))
+        return fail(BCMPC_ERR_HIP, "loss buffer allocation failed");
     // device step state: counter 0, the host mirror's beta powers, this run's learning rate
     f->h_state[2] = learning_rate;
     if (hipMemsetAsync(f->d_iter, 0, 4, stream) != hipSuccess ||
@@ -604,30 +449,15 @@ static int acfit_enqueue(bcmpc_acfit* f, const int32_t* batch_sizes, int32_t ite
     const char* ge = std::getenv("BCMPC_ACFIT_GRAPH");
     const bool use_graph = uniform && !(ge && ge[0] == '0');
     if (use_graph) {
-        if (!(f->graph && f->graph_iters == iterations && f->graph_b == batch_sizes[0] && f->graph_idx == f->d_idx &&
-              f->graph_loss == f->d_loss)) {
-            acfit_drop_graph(f);
-            if (hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
-                return fail(BCMPC_ERR_HIP, "graph capture failed to start");
-            int rc = BCMPC_OK;
-            for (int i = 0; i < iterations && rc == BCMPC_OK; ++i)
-                rc = acfit_step(f, f->stream, f->d_idx, batch_sizes[0], batch_sizes[0]);
-            hipGraph_t g = nullptr;
-            const hipError_t ec = hipStreamEndCapture(f->stream, &g);
-            if (rc != BCMPC_OK || ec != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                return rc != BCMPC_OK ? rc : fail(BCMPC_ERR_HIP, "graph capture failed");
-            }
-            const hipError_t ei = hipGraphInstantiate(&f->graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (ei != hipSuccess) { f->graph = nullptr; return fail(BCMPC_ERR_HIP, "graph instantiation failed"); }
-            f->graph_iters = iterations;
-            f->graph_b = batch_sizes[0];
-            f->graph_idx = f->d_idx;
-            f->graph_loss = f->d_loss;
-            ++f->captures;
-        }
-        if (hipGraphLaunch(f->graph, f->stream) != hipSuccess) return fail(BCMPC_ERR_HIP, "graph launch failed");
+        const intptr_t key[train::GraphRun::kKey] = {iterations, batch_sizes[0], (intptr_t)f->d_idx,
+                                                     (intptr_t)f->d_loss};
+        const int rc = f->graph.run(f->stream, key, fail, [&] {
+            int rs = BCMPC_OK;
+            for (int i = 0; i < iterations && rs == BCMPC_OK; ++i)
+                rs = acfit_step(f, f->stream, f->d_idx, batch_sizes[0], batch_sizes[0]);
+            return rs;
+        });
+        if (rc != BCMPC_OK) return rc;
     } else {
         int64_t pos = 0;
         for (int i = 0; i < iterations; ++i) {

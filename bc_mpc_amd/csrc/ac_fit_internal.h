@@ -7,6 +7,7 @@
 
 #include "../../include/bcmpc.h"
 #include "ac_fit_plan.h"
+#include "train_run.h"
 
 struct bcmpc_acfit {
     bcmpc::acfit::Plan plan;
@@ -25,13 +26,9 @@ struct bcmpc_acfit {
     float* d_loss = nullptr; int32_t loss_cap = 0;
     // one captured graph of a whole uniform-batch run, reused while everything it holds by address or by value
     // stands: the step count and batch size, the index and loss buffers (the key below); the data and activation
-    // buffers (acfit_drop_graph where they are reallocated).  The filter and the learning rate are read from
+    // buffers (graph.drop() where they are reallocated).  The filter and the learning rate are read from
     // device memory at fixed addresses: new values need no new graph.
-    hipGraphExec_t graph = nullptr;
-    int32_t graph_iters = 0, graph_b = 0;
-    const void* graph_idx = nullptr;
-    const void* graph_loss = nullptr;
-    int32_t captures = 0;
+    bcmpc::train::GraphRun graph;
     bool last_graph = false;
     bool has_weights = false, has_filter = false;
 };
@@ -39,7 +36,6 @@ struct bcmpc_acfit {
 #pragma GCC visibility push(hidden)
 namespace bcmpc::acfit {
 
-void acfit_drop_graph(bcmpc_acfit* f);
 // activation buffers for batches of up to `rows` rows (no run is in flight); a growth drops the fitter's graph
 bool acfit_reserve(bcmpc_acfit* f, int32_t rows);
 // A run in three parts, all on `stream`.  prepare: the activation, index and loss buffers for `total` indices in

@@ -91,6 +91,13 @@ int check_filter(const float* mean, const float* std, int S) {
     return BCMPC_OK;
 }
 
+void filter_image(const float* mean, const float* std, int S, float* out) {
+    for (int i = 0; i < 32; ++i) {
+        out[i] = i < S ? mean[i] : 0.f;
+        out[32 + i] = i < S ? std[i] : 1.f;
+    }
+}
+
 }  // namespace bcmpc::acfit
 
 extern "C" {

@@ -45,6 +45,8 @@ int make_plan(const bcmpc_acfit_config* c, Plan* out);    // every check of bcmp
 int check_run(const int64_t* indices, const int32_t* batch_sizes, int32_t iterations, float lr, int64_t n_data,
               int64_t* total, int32_t* bmax);
 int check_filter(const float* mean, const float* std, int S);
+// the device image of a checked filter, [2][32]: mean then std, 0 / 1 beyond S
+void filter_image(const float* mean, const float* std, int S, float* out);
 
 }  // namespace bcmpc::acfit
 #pragma GCC visibility pop

@@ -21,21 +21,18 @@
 //
 // The trainer trains in place on its two fitters' d_w / d_wt and uses their activation buffers; the interleaved
 // BC step is the policy fitter's own acfit_step enqueued into the same chain (ac_fit_internal.h).
-//
-// The device helpers (rows_gemm and friends, adam_elem) are this unit's own copies of ac_fit.hip's: ac_fit.hip's
-// kernels stay as they are (profiles/ac_ppo_digest.txt).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "../../include/bcmpc.h"
 #include "ac_fit_internal.h"
 #include "ac_ppo_plan.h"
+#include "train_rows.h"
 
 namespace bcmpc::acppo {
 
@@ -44,11 +41,12 @@ using acfit::kTgtLd;
 using acfit::kWaves;
 using acfit::fail;
 
-typedef float f4v __attribute__((ext_vector_type(4)));
+using rows::adam_elem;                      // the row-tile GEMM and Adam: train_rows.h
+using rows::f4v;
+using rows::kPK;
+using rows::rows_gemm;
+static_assert(rows::kWaves == kWaves, "the plan's LDS layout and the row GEMM agree on the workgroup's waves");
 
-constexpr int kFK = 8;                      // k-steps (of 4) per weight chunk
-constexpr int kFRing = 4;                   // weight chunks in flight per wave
-constexpr int kPK = 32;                     // batch steps (of 4) per load batch of a weight-gradient tile
 constexpr int kLsLd = 16;                   // stride of the rows' logstd contributions (A <= 16)
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;        // f32(0.5 log 2 pi)
 constexpr float kHalfLog2PiE = 1.41893853320467274178f;       // f32(0.5 log(2 pi e))
@@ -78,98 +76,6 @@ struct Args {
     int32_t B, S, A, L, h, ld, mode;
     float b1, b2, eps;
 };
-
-// one chunk of kFK k-steps of the B operand through a buffer descriptor: one 32-bit lane offset (vo) for the
-// whole GEMM, the chunk position in the scalar offset; rows past the matrix and the masked columns (vo beyond
-// the range) read 0
-__device__ __forceinline__ void rows_load(float* b, __amdgpu_buffer_rsrc_t rsrc, int vo, int kb, int kstride) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s)
-        b[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, (kb + 4 * s) * kstride, 0));
-}
-
-__device__ __forceinline__ f4v rows_mma(f4v acc, const float* b, const float* X, int kb, int K, int r16, int k4,
-                                        int lds) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s) {
-        const int k = kb + 4 * s + k4;
-        const float x = k < K ? X[r16 * lds + k] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, b[s], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ void rows_drained() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-}
-
-__device__ __forceinline__ f4v rows_tile(f4v acc, const float* X, int k0, int k1, __amdgpu_buffer_rsrc_t rsrc,
-                                         int vo, int ldw, int r16, int k4, int lds) {
-    constexpr int CK = 4 * kFK;
-    float ring[kFRing][kFK];
-#pragma unroll
-    for (int j = 0; j < kFRing; ++j)
-        if (k0 + j * CK < k1) rows_load(ring[j], rsrc, vo, k0 + j * CK, 4 * ldw);
-    for (int kb = k0; kb < k1; kb += kFRing * CK) {
-#pragma unroll
-        for (int j = 0; j < kFRing; ++j) {
-            const int kc = kb + j * CK;
-            if (kc < k1) {
-                acc = rows_mma(acc, ring[j], X, kc, k1, r16, k4, lds);
-                if (kc + kFRing * CK < k1) rows_load(ring[j], rsrc, vo, kc + kFRing * CK, 4 * ldw);
-            }
-        }
-    }
-    return acc;
-}
-
-// C[r][n] = sum_k X[r][k] W[k*ldw + n] (+ bias[n]) for the 16 LDS rows X (stride lds), n < N, W row-major
-// [K][ldw].  16-column tiles over the 16 waves; with at most 8 tiles (N <= 128) the K range is split over the
-// idle waves and the partials (LDS, `kp`) are added in wave order.
-__device__ __forceinline__ void rows_gemm(const float* X, int K, const float* __restrict__ W, int ldw, int N,
-                                          const float* __restrict__ bias, float* C, int lds, float* kp) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r16 = lane & 15, k4 = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, K * ldw * 4, 0x00020000);
-    const int nt = (N + 15) / 16;
-    if (nt * 2 > kWaves) {
-        for (int n0 = 16 * wv; n0 < N; n0 += 16 * kWaves) {
-            const int n = n0 + r16;
-            const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-            const float bv = bias && n < N ? bias[n] : 0.f;          // requested before the weights
-            f4v acc = rows_tile((f4v){0.f, 0.f, 0.f, 0.f}, X, 0, K, rsrc, vo, ldw, r16, k4, lds);
-            rows_drained();
-            if (n < N)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) C[(4 * k4 + r) * lds + n] = bias ? acc[r] + bv : acc[r];
-        }
-        return;
-    }
-    // K split: wave wv takes tile wv % nt, K slice wv / nt of ks (whole 4-k-steps)
-    const int ks = kWaves / nt;
-    const int t = wv % nt, q = wv / nt;
-    const int n = 16 * t + r16;
-    if (q < ks) {
-        const int kq = ((K + 4 * ks - 1) / (4 * ks)) * 4;       // slice length, multiple of 4
-        const int k0 = min(K, q * kq), k1 = min(K, k0 + kq);
-        const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-        f4v acc = (f4v){0.f, 0.f, 0.f, 0.f};
-        if (k0 < k1) acc = rows_tile(acc, X, k0, k1, rsrc, vo, ldw, r16, k4, lds);
-        rows_drained();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) kp[(q * nt + t) * 256 + (4 * k4 + r) * 16 + r16] = acc[r];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 16 * nt * 16; i += 64 * kWaves) {
-        const int tt = i / 256, e = i % 256, r = e / 16, c = 16 * tt + e % 16;
-        if (c < N) {
-            float s = 0.f;
-            for (int qq = 0; qq < ks; ++qq) s += kp[(qq * nt + tt) * 256 + e];
-            C[r * lds + c] = bias ? s + bias[c] : s;
-        }
-    }
-}
 
 __global__ __launch_bounds__(1024) void acppo_rows_kernel(const Args a) {
     extern __shared__ float sm[];
@@ -371,18 +277,6 @@ __global__ __launch_bounds__(1024) void acppo_rows_kernel(const Args a) {
     }
 }
 
-__device__ __forceinline__ float adam_elem(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                           size_t i, float gi, float w0, float m0, float v0, float lr_t, float b1,
-                                           float b2, float eps) {
-    const float mi = m0 + (gi - m0) * (1.0f - b1);
-    const float vi = v0 + (gi * gi - v0) * (1.0f - b2);
-    const float wi = w0 - __fdiv_rn(mi * lr_t, __fsqrt_rn(vi) + eps);
-    m[i] = mi;
-    v[i] = vi;
-    w[i] = wi;
-    return wi;
-}
-
 // one workgroup per task; a weight tile's 4 waves take contiguous quarters of the batch and their partials are
 // added in wave order (deterministic)
 __global__ __launch_bounds__(256) void acppo_params_kernel(const Args a) {
@@ -481,6 +375,7 @@ __global__ __launch_bounds__(256) void acppo_params_kernel(const Args a) {
 }  // namespace bcmpc::acppo
 
 using namespace bcmpc::acppo;
+namespace train = bcmpc::train;
 using bcmpc::acfit::acfit_finish;
 using bcmpc::acfit::acfit_prepare;
 using bcmpc::acfit::acfit_reserve;
@@ -509,17 +404,10 @@ struct bcmpc_acppo {
     // one captured graph of a whole uniform run: a single chain of kernel nodes.  It is reused while everything
     // it holds by address or by value stands (the key); lr, eps, entcoeff and the filter are read from device
     // memory at fixed addresses.
-    hipGraphExec_t graph = nullptr;
-    intptr_t graph_key[16] = {};
-    int32_t captures = 0;
+    train::GraphRun graph;
     bool last_graph = false;
     bool has_logstd = false, has_old = false, has_data = false;
 };
-
-static void acppo_drop_graph(bcmpc_acppo* t) {
-    if (t->graph) (void)hipGraphExecDestroy(t->graph);
-    t->graph = nullptr;
-}
 
 static Args acppo_args(const bcmpc_acppo* t, const int64_t* d_idx, int stride, int B, int mode) {
     const Plan& p = t->plan;
@@ -569,7 +457,7 @@ static int acppo_snapshot(bcmpc_acppo* t) {
 
 extern "C" {
 
-int bcmpc_acppo_is_graph(const bcmpc_acppo* t) { return t && t->last_graph ? t->captures : 0; }
+int bcmpc_acppo_is_graph(const bcmpc_acppo* t) { return t && t->last_graph ? t->graph.captures : 0; }
 
 int bcmpc_acppo_create(const bcmpc_acppo_config* c, bcmpc_acfit* pol, bcmpc_acfit* val, bcmpc_acppo** out) {
     if (!c || !pol || !val || !out) return fail(BCMPC_ERR_ARG, "null argument");
@@ -606,7 +494,7 @@ int bcmpc_acppo_create(const bcmpc_acppo_config* c, bcmpc_acfit* pol, bcmpc_acfi
 int bcmpc_acppo_destroy(bcmpc_acppo* t) {
     if (!t) return BCMPC_OK;
     if (t->stream) (void)hipStreamSynchronize(t->stream);
-    acppo_drop_graph(t);
+    t->graph.drop();
     for (void* p : {(void*)t->d_m[0], (void*)t->d_m[1], (void*)t->d_v[0], (void*)t->d_v[1], (void*)t->d_ls,
                     (void*)t->d_old, (void*)t->d_oldf, (void*)t->d_state, (void*)t->d_iter, (void*)t->d_tasks,
                     (void*)t->d_obs, (void*)t->d_acs, (void*)t->d_atarg, (void*)t->d_ret, (void*)t->d_oldmean,
@@ -656,10 +544,7 @@ int bcmpc_acppo_set_old(bcmpc_acppo* t, const float* const* kernels, const float
     }
     if (const int rc = check_finite(hw.data(), (int64_t)hw.size(), "the old policy's weights")) return rc;
     float hf[80];
-    for (int i = 0; i < 32; ++i) {
-        hf[i] = i < fp.S ? ob_mean[i] : 0.f;
-        hf[32 + i] = i < fp.S ? ob_std[i] : 1.f;
-    }
+    bcmpc::acfit::filter_image(ob_mean, ob_std, fp.S, hf);
     for (int i = 0; i < 16; ++i) hf[64 + i] = i < fp.N ? oldlogstd[i] : 0.f;
     if (hipSetDevice(t->plan.device) != hipSuccess ||
         hipMemcpyAsync(t->d_old, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess ||
@@ -680,18 +565,13 @@ int bcmpc_acppo_set_data(bcmpc_acppo* t, const double* obs, const float* acs, co
     if (const int rc = check_finite(ret, n, "returns")) return rc;
     if (hipSetDevice(p.device) != hipSuccess) return fail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > t->data_cap) {
-        acppo_drop_graph(t);                              // the graph holds the data buffers' addresses
-        for (void** q : {(void**)&t->d_obs, (void**)&t->d_acs, (void**)&t->d_atarg, (void**)&t->d_ret,
-                         (void**)&t->d_oldmean})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        t->data_cap = 0;
+        t->graph.drop();                                  // the graph holds the data buffers' addresses
         t->n_data = 0;
         t->has_data = false;
-        if (hipMalloc(&t->d_obs, (size_t)n * p.S * 8) != hipSuccess || hipMalloc(&t->d_acs, (size_t)n * p.A * 4) != hipSuccess ||
-            hipMalloc(&t->d_atarg, (size_t)n * 4) != hipSuccess || hipMalloc(&t->d_ret, (size_t)n * 4) != hipSuccess ||
-            hipMalloc(&t->d_oldmean, (size_t)n * p.A * 4) != hipSuccess)
+        if (!train::grow(&t->data_cap, n, {{&t->d_obs, (size_t)n * p.S * 8}, {&t->d_acs, (size_t)n * p.A * 4},
+                                           {&t->d_atarg, (size_t)n * 4}, {&t->d_ret, (size_t)n * 4},
+                                           {&t->d_oldmean, (size_t)n * p.A * 4}}))
             return fail(BCMPC_ERR_HIP, "data buffer allocation failed");
-        t->data_cap = n;
     }
     if (hipMemcpyAsync(t->d_obs, obs, (size_t)n * p.S * 8, hipMemcpyHostToDevice, t->stream) != hipSuccess ||
         hipMemcpyAsync(t->d_acs, acs, (size_t)n * p.A * 4, hipMemcpyHostToDevice, t->stream) != hipSuccess ||
@@ -728,30 +608,13 @@ int bcmpc_acppo_run(bcmpc_acppo* t, const int64_t* indices, const int32_t* batch
     // no run of either fitter is in flight: their runs synchronise
     if (!acfit_reserve(pol, std::max(bmax, bc_bmax)) || !acfit_reserve(val, bmax))
         return fail(BCMPC_ERR_HIP, "activation buffer allocation failed");
-    if (bmax > t->rcap) {
-        for (float** q : {&t->d_rowls, &t->d_part})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        t->rcap = 0;
-        const size_t nblk = ((size_t)bmax + kRows - 1) / kRows;
-        if (hipMalloc(&t->d_rowls, (size_t)bmax * kLsLd * 4) != hipSuccess || hipMalloc(&t->d_part, nblk * 4 * 4) != hipSuccess)
-            return fail(BCMPC_ERR_HIP, "row buffer allocation failed");
-        t->rcap = bmax;
-    }
-    if (total > t->idx_cap) {
-        if (t->d_idx) (void)hipFree(t->d_idx);
-        t->d_idx = nullptr;
-        t->idx_cap = 0;
-        if (hipMalloc(&t->d_idx, (size_t)total * 8) != hipSuccess) return fail(BCMPC_ERR_HIP, "index buffer allocation failed");
-        t->idx_cap = total;
-    }
-    if (iterations > t->loss_cap) {
-        if (t->d_loss) (void)hipFree(t->d_loss);
-        t->d_loss = nullptr;
-        t->loss_cap = 0;
-        if (hipMalloc(&t->d_loss, (size_t)iterations * 6 * 4) != hipSuccess)
-            return fail(BCMPC_ERR_HIP, "loss buffer allocation failed");
-        t->loss_cap = iterations;
-    }
+    const size_t nblk = ((size_t)bmax + kRows - 1) / kRows;
+    if (!train::grow(&t->rcap, bmax, {{&t->d_rowls, (size_t)bmax * kLsLd * 4}, {&t->d_part, nblk * 4 * 4}}))
+        return fail(BCMPC_ERR_HIP, "row buffer allocation failed");
+    if (!train::grow(&t->idx_cap, total, {{&t->d_idx, (size_t)total * 8}}))
+        return fail(BCMPC_ERR_HIP, "index buffer allocation failed");
+    if (!train::grow(&t->loss_cap, iterations, {{&t->d_loss, (size_t)iterations * 6 * 4}}))
+        return fail(BCMPC_ERR_HIP, "loss buffer allocation failed");
     // device step state: counter 0, the host mirror's beta powers, this run's lr / eps / entcoeff
     t->h_state[2] = learning_rate;
     t->h_state[3] = eps;
@@ -770,34 +633,22 @@ int bcmpc_acppo_run(bcmpc_acppo* t, const int64_t* indices, const int32_t* batch
     const char* ge = std::getenv("BCMPC_ACPPO_GRAPH");
     const bool use_graph = uniform && !(ge && ge[0] == '0');
     if (use_graph) {
-        const intptr_t key[16] = {iterations, batch_sizes[0], bc ? bc_batch_sizes[0] : 0,
+        const intptr_t key[train::GraphRun::kKey] = {iterations, batch_sizes[0], bc ? bc_batch_sizes[0] : 0,
                                   (intptr_t)t->d_idx, (intptr_t)t->d_loss, (intptr_t)t->d_rowls, (intptr_t)t->d_obs,
                                   (intptr_t)pol->d_x0, (intptr_t)val->d_x0,
                                   bc ? (intptr_t)pol->d_idx : 0, bc ? (intptr_t)pol->d_loss : 0,
                                   bc ? (intptr_t)pol->d_obs : 0, bc ? (intptr_t)pol->d_tgt : 0,
                                   pol->bcap, val->bcap, (intptr_t)pol->d_act};
-        if (!(t->graph && std::memcmp(key, t->graph_key, sizeof(key)) == 0)) {
-            acppo_drop_graph(t);
-            if (hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
-                return fail(BCMPC_ERR_HIP, "graph capture failed to start");
-            int rc = BCMPC_OK;
-            for (int i = 0; i < iterations && rc == BCMPC_OK; ++i) {
-                rc = acppo_step(t, t->d_idx, batch_sizes[0], batch_sizes[0]);
-                if (bc && rc == BCMPC_OK) rc = acfit_step(pol, t->stream, pol->d_idx, bc_batch_sizes[0], bc_batch_sizes[0]);
+        const int rc = t->graph.run(t->stream, key, fail, [&] {
+            int rs = BCMPC_OK;
+            for (int i = 0; i < iterations && rs == BCMPC_OK; ++i) {
+                rs = acppo_step(t, t->d_idx, batch_sizes[0], batch_sizes[0]);
+                if (bc && rs == BCMPC_OK)
+                    rs = acfit_step(pol, t->stream, pol->d_idx, bc_batch_sizes[0], bc_batch_sizes[0]);
             }
-            hipGraph_t g = nullptr;
-            const hipError_t ec = hipStreamEndCapture(t->stream, &g);
-            if (rc != BCMPC_OK || ec != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                return rc != BCMPC_OK ? rc : fail(BCMPC_ERR_HIP, "graph capture failed");
-            }
-            const hipError_t ei = hipGraphInstantiate(&t->graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (ei != hipSuccess) { t->graph = nullptr; return fail(BCMPC_ERR_HIP, "graph instantiation failed"); }
-            std::memcpy(t->graph_key, key, sizeof(key));
-            ++t->captures;
-        }
-        if (hipGraphLaunch(t->graph, t->stream) != hipSuccess) return fail(BCMPC_ERR_HIP, "graph launch failed");
+            return rs;
+        });
+        if (rc != BCMPC_OK) return rc;
     } else {
         int64_t pos = 0, bpos = 0;
         for (int i = 0; i < iterations; ++i) {

@@ -32,6 +32,8 @@
 #include "../../include/bcmpc.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "train_rows.h"
+#include "train_run.h"
 
 namespace bcmpc {
 
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void gemm_f32(const float* __restrict__ A, con
 // v_mfma_f32_16x16x4_f32 tiles), operands straight from global memory (L1/L2-resident at
 // these sizes), K in steps of 4 with the next step's fragments in flight.  Fragment layouts:
 // A 16x4: lane l holds A[l&15][l>>4]; B 4x16: B[l>>4][l&15]; D 16x16: D[4(l>>4)+r][l&15].
-typedef float f4v __attribute__((ext_vector_type(4)));
+using rows::f4v;
 template <bool TA, bool TB>
 __global__ __launch_bounds__(64) void gemm_mfma(const float* __restrict__ A, const float* __restrict__ B,
                                                 float* __restrict__ C, const float* __restrict__ bias, int M, int N,
@@ -438,10 +440,10 @@ __global__ void fit_adam(float* __restrict__ w, float* __restrict__ m, float* __
 // Same row arithmetic as the per-op kernels above (fit_act_fwd / fit_act_bwd / fit_loss verbatim);
 // only the GEMM and batch-sum orders differ.
 constexpr int kFR = 16;                     // batch rows per row-block workgroup (one MFMA row tile)
-constexpr int kFW = 16;                     // waves of the row-block workgroup
-constexpr int kFK = 8;                      // k-steps (of 4) per weight chunk
-constexpr int kFRing = 4;                   // weight chunks in flight per wave
-constexpr int kPK = 32;                     // batch steps (of 4) per load batch of a weight-gradient tile
+using rows::kPK;                            // the row-tile GEMM and the wave sum: train_rows.h
+using rows::kWaves;
+using rows::rows_gemm;
+using rows::wave_sum_fast;
 
 struct FitTile {                            // fit_params_kernel work item (one workgroup)
     int32_t kind;                           // 0: weight tile (+ bias row), 1: LayerNorm columns, 3: loss
@@ -466,123 +468,7 @@ struct FusedArgs {
     float lr, b1, b2, eps;
 };
 
-// one chunk of kFK k-steps of the B operand through a buffer descriptor: one 32-bit lane offset
-// (vo) for the whole GEMM, the chunk position in the scalar offset; rows past the matrix and the
-// masked columns (vo beyond the range) read 0
-__device__ __forceinline__ void rows_load(float* b, __amdgpu_buffer_rsrc_t rsrc, int vo, int kb, int kstride) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s)
-        b[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, (kb + 4 * s) * kstride, 0));
-}
-
-__device__ __forceinline__ f4v rows_mma(f4v acc, const float* b, const float* X, int kb, int K, int r16, int k4,
-                                        int lds) {
-#pragma unroll
-    for (int s = 0; s < kFK; ++s) {
-        const int k = kb + 4 * s + k4;
-        const float x = k < K ? X[r16 * lds + k] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, b[s], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-// Every weight load of a GEMM has been consumed by its end, but the compiler's wait analysis cannot
-// see it through the conditional prefetches and keeps them "pending": the row phase after the GEMM
-// then gets vmcnt(0) waits at register reuse -- which also wait for that phase's own global stores,
-// a full HBM write trip (~2 us) per phase.  A real s_waitcnt vmcnt(0) here (nothing is in flight by
-// then) clears the analysis.
-__device__ __forceinline__ void rows_drained() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-}
-
-// acc += sum over k in [k0, k1) of X[r][k] W[k*ldw + n] for this lane's column n (a 16-wide tile),
-// kFRing chunks of weights in flight
-__device__ __forceinline__ f4v rows_tile(f4v acc, const float* X, int k0, int k1, __amdgpu_buffer_rsrc_t rsrc,
-                                         int vo, int ldw, int r16, int k4, int lds) {
-    constexpr int CK = 4 * kFK;
-    float ring[kFRing][kFK];
-#pragma unroll
-    for (int j = 0; j < kFRing; ++j)
-        if (k0 + j * CK < k1) rows_load(ring[j], rsrc, vo, k0 + j * CK, 4 * ldw);
-    for (int kb = k0; kb < k1; kb += kFRing * CK) {
-#pragma unroll
-        for (int j = 0; j < kFRing; ++j) {
-            const int kc = kb + j * CK;
-            if (kc < k1) {
-                acc = rows_mma(acc, ring[j], X, kc, k1, r16, k4, lds);
-                if (kc + kFRing * CK < k1) rows_load(ring[j], rsrc, vo, kc + kFRing * CK, 4 * ldw);
-            }
-        }
-    }
-    return acc;
-}
-
-// C[r][n] = sum_k X[r][k] W[k*ldw + n] (+ bias[n]) for the 16 LDS rows X (stride lds), n < N, W row-major
-// [K][ldw].  16-column tiles over the 16 waves; when there are fewer tiles than waves (the [h -> S]
-// output layer) the K range is split over the idle waves and the partials (LDS, `kp`) are added in
-// wave order.
-__device__ __forceinline__ void rows_gemm(const float* X, int K, const float* __restrict__ W, int ldw, int N,
-                          const float* __restrict__ bias, float* C, int lds, float* kp) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r16 = lane & 15, k4 = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, K * ldw * 4, 0x00020000);
-    const int nt = (N + 15) / 16;
-    if (nt * 2 > kFW) {
-        for (int n0 = 16 * wv; n0 < N; n0 += 16 * kFW) {
-            const int n = n0 + r16;
-            const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-            const float bv = bias && n < N ? bias[n] : 0.f;          // requested before the weights
-            f4v acc = rows_tile((f4v){0.f, 0.f, 0.f, 0.f}, X, 0, K, rsrc, vo, ldw, r16, k4, lds);
-            rows_drained();
-            if (n < N)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) C[(4 * k4 + r) * lds + n] = bias ? acc[r] + bv : acc[r];
-        }
-        return;
-    }
-    // K split: wave wv takes tile wv % nt, K slice wv / nt of ks (whole 4-k-steps)
-    const int ks = kFW / nt;
-    const int t = wv % nt, q = wv / nt;
-    const int n = 16 * t + r16;
-    if (q < ks) {
-        const int kq = ((K + 4 * ks - 1) / (4 * ks)) * 4;       // slice length, multiple of 4
-        const int k0 = min(K, q * kq), k1 = min(K, k0 + kq);
-        const int vo = n < N ? (k4 * ldw + n) * 4 : 0x40000000;
-        f4v acc = (f4v){0.f, 0.f, 0.f, 0.f};
-        if (k0 < k1) acc = rows_tile(acc, X, k0, k1, rsrc, vo, ldw, r16, k4, lds);
-        rows_drained();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) kp[(q * nt + t) * 256 + (4 * k4 + r) * 16 + r16] = acc[r];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 16 * nt * 16; i += 64 * kFW) {
-        const int tt = i / 256, e = i % 256, r = e / 16, c = 16 * tt + e % 16;
-        if (c < N) {
-            float s = 0.f;
-            for (int qq = 0; qq < ks; ++qq) s += kp[(qq * nt + tt) * 256 + e];
-            C[r * lds + c] = bias ? s + bias[c] : s;
-        }
-    }
-}
-
-// wave sum without the LDS crossbar: DPP butterflies inside each 16-lane row (quad_perm xor 1, xor 2,
-// row_ror 4, 8), then the four row totals in a fixed order (deterministic, wave-uniform)
-template <int CTRL>
-__device__ __forceinline__ float dpp_t(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float wave_sum_fast(float v) {
-    v += dpp_t<0xB1>(v);                    // quad_perm [1,0,3,2]
-    v += dpp_t<0x4E>(v);                    // quad_perm [2,3,0,1]
-    v += dpp_t<0x124>(v);                   // row_ror 4
-    v += dpp_t<0x128>(v);                   // row_ror 8
-    const int b = __builtin_bit_cast(int, v);
-    return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))) +
-           (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) +
-            __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48)));
-}
-
+// this unit's own copy: rows::adam_elem spells / and sqrtf as __fdiv_rn / __fsqrt_rn, which moves fit_params_kernel
 __device__ __forceinline__ float adam_elem(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                            size_t i, float gi, float w0, float m0, float v0, float lr_t, float b1,
                                            float b2, float eps) {
@@ -602,9 +488,9 @@ __global__ __launch_bounds__(1024) void fit_rows_kernel(const FusedArgs a) {
     float* bufB = bufA + kFR * ld;          // [16][ld]: GEMM output
     float* bufC = bufB + kFR * ld;          // [16][ld]: dH * xhat (LayerNorm backward)
     float* tsm = bufC + kFR * ld;           // [16][32] targets
-    float* red = tsm + kFR * 32;            // [kFW] loss partials per wave
-    float* kp = red + kFW;                  // [kFW][256] K-split partials
-    float* stat = kp + kFW * 256;           // [L][2][16] row mean / rs
+    float* red = tsm + kFR * 32;            // [kWaves] loss partials per wave
+    float* kp = red + kWaves;               // [kWaves][256] K-split partials
+    float* stat = kp + kWaves * 256;        // [L][2][16] row mean / rs
     float* prm = stat + L * 2 * kFR;        // [L][2][h] LayerNorm gamma, beta (LN nets)
                                             // (every pointer the row phases read is LDS: no flat
                                             //  loads, whose waits would include the pending stores)
@@ -628,12 +514,12 @@ __global__ __launch_bounds__(1024) void fit_rows_kernel(const FusedArgs a) {
     }
     // ---- gather (fit_gather), LayerNorm parameters into LDS ----
     if (a.ln)
-        for (int i = tid; i < 2 * L * h; i += 64 * kFW) {
+        for (int i = tid; i < 2 * L * h; i += 64 * kWaves) {
             const int l = i / (2 * h), j = i % (2 * h);
             prm[i] = j < h ? a.w[a.g_off[l] + j] : a.w[a.be_off[l] + j - h];
         }
     const double* nc = a.nc;
-    for (int i = tid; i < kFR * (IN + S); i += 64 * kFW) {
+    for (int i = tid; i < kFR * (IN + S); i += 64 * kWaves) {
         const int r = i / (IN + S), c = i % (IN + S);
         float val = 0.f;
         if (r < nr) {
@@ -710,7 +596,7 @@ __global__ __launch_bounds__(1024) void fit_rows_kernel(const FusedArgs a) {
     FIT_STAMP();
     const float inv = 1.0f / (float)(a.B * S);
     float sl = 0.f;
-    for (int i = tid; i < kFR * S; i += 64 * kFW) {
+    for (int i = tid; i < kFR * S; i += 64 * kWaves) {
         const int r = i / S, c = i % S;
         float g = 0.f;
         if (r < nr) {
@@ -729,7 +615,7 @@ __global__ __launch_bounds__(1024) void fit_rows_kernel(const FusedArgs a) {
     FIT_STAMP();
     if (tid == 0) {
         float t = 0.f;
-        for (int w = 0; w < kFW; ++w) t += red[w];
+        for (int w = 0; w < kWaves; ++w) t += red[w];
         a.loss_part[blockIdx.x] = t;
     }
     // ---- backward data gradients (fit_act_bwd per row), LayerNorm column partials ----
@@ -786,7 +672,7 @@ __global__ __launch_bounds__(1024) void fit_rows_kernel(const FusedArgs a) {
         __syncthreads();
         FIT_STAMP();
         if (a.ln) {                                       // this block's 16-row column sums, rows in order
-            for (int f = tid; f < h; f += 64 * kFW) {
+            for (int f = tid; f < h; f += 64 * kWaves) {
                 float sb = 0.f, sg = 0.f;
                 for (int r = 0; r < kFR; ++r) {
                     sb += bufB[r * ld + f];
@@ -943,11 +829,8 @@ struct bcmpc_fitter {
     float* d_cpart = nullptr;                     // column-sum chunk partials [kColChunks][2][max width]
     unsigned* d_tickets = nullptr;                // column-sum completion tickets (one per 64 columns)
     // one captured graph of a whole uniform-batch run, reused while its shape and buffers match (index and
-    // loss buffers: the reuse key; the data / reward buffers: fit_drop_graph where they are reallocated)
-    hipGraphExec_t graph = nullptr;
-    int32_t graph_iters = 0, graph_b = 0;
-    const void* graph_idx = nullptr;
-    const void* graph_loss = nullptr;
+    // loss buffers: the reuse key; the data / reward buffers: graph.drop() where they are reallocated)
+    train::GraphRun graph;
     int64_t step = 0;
     bool has_weights = false;
     // the fused two-launch iteration (fit_rows_kernel + fit_params_kernel)
@@ -966,14 +849,6 @@ struct bcmpc_fitter {
     bool has_rewards = false;
     int32_t last_iters = 0;                       // iterations of the last run (its reward losses in d_loss2)
 };
-
-// The captured graph holds the data buffers' addresses in its kernel arguments (fit_gather,
-// fit_gather_reward, FusedArgs.st/ac/de): a buffer that moves ends the graph's life.  (No run is in
-// flight here: bcmpc_fit_run synchronises the stream before it returns.)
-static void fit_drop_graph(bcmpc_fitter* f) {
-    if (f->graph) (void)hipGraphExecDestroy(f->graph);
-    f->graph = nullptr;
-}
 
 extern "C" {
 
@@ -1047,7 +922,7 @@ int bcmpc_fit_create(const bcmpc_fit_config* c, bcmpc_fitter** out) {
         // then (when it fits) LayerNorm parameters and every hidden layer's activation rows
         const int wmax = std::max(f->h, std::max(f->IN, f->S));
         f->rows_ld = (wmax + 3) / 4 * 4 + 4;
-        const size_t base = (size_t)3 * kFR * f->rows_ld + kFR * 32 + kFW + kFW * 256 + 2 * kFR * f->L;
+        const size_t base = (size_t)3 * kFR * f->rows_ld + kFR * 32 + kWaves + kWaves * 256 + 2 * kFR * f->L;
         const size_t cache = (size_t)2 * f->L * f->h + (size_t)f->L * kFR * f->rows_ld;
         constexpr size_t kLdsMax = 160 * 1024 / 4;
         f->rows_lds = (base + cache) * 4;
@@ -1088,7 +963,7 @@ int bcmpc_fit_create(const bcmpc_fit_config* c, bcmpc_fitter** out) {
 int bcmpc_fit_destroy(bcmpc_fitter* f) {
     if (!f) return BCMPC_OK;
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->graph) (void)hipGraphExecDestroy(f->graph);
+    f->graph.drop();
     for (void* p : {(void*)f->d_iter, (void*)f->d_bp, (void*)f->d_cpart, (void*)f->d_tickets, (void*)f->d_w, (void*)f->d_m, (void*)f->d_v, (void*)f->d_g, (void*)f->d_x0, (void*)f->d_t,
                     (void*)f->d_p, (void*)f->d_dp, (void*)f->d_act, (void*)f->d_hln, (void*)f->d_mean,
                     (void*)f->d_rs, (void*)f->d_dh, (void*)f->d_dz, (void*)f->d_loss, (void*)f->d_st,
@@ -1179,15 +1054,13 @@ int bcmpc_fit_set_data(bcmpc_fitter* f, const double* states, const double* acti
     if (!f || (n > 0 && (!states || !actions || !deltas)) || n < 0) return ffail(BCMPC_ERR_ARG, "bad argument");
     if (hipSetDevice(f->cfg.device) != hipSuccess) return ffail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > f->data_cap) {
-        fit_drop_graph(f);
-        for (double** p : {&f->d_st, &f->d_ac, &f->d_de})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        f->data_cap = 0;
-        if (hipMalloc(&f->d_st, (size_t)n * f->S * 8) != hipSuccess ||
-            hipMalloc(&f->d_ac, (size_t)n * f->A * 8) != hipSuccess ||
-            hipMalloc(&f->d_de, (size_t)n * f->S * 8) != hipSuccess)
+        // The captured graph holds the data buffers' addresses in its kernel arguments (fit_gather,
+        // fit_gather_reward, FusedArgs.st/ac/de): a buffer that moves ends the graph's life.  (No run is in
+        // flight here: bcmpc_fit_run synchronises the stream before it returns.)
+        f->graph.drop();
+        if (!train::grow(&f->data_cap, n, {{&f->d_st, (size_t)n * f->S * 8}, {&f->d_ac, (size_t)n * f->A * 8},
+                                           {&f->d_de, (size_t)n * f->S * 8}}))
             return ffail(BCMPC_ERR_HIP, "data buffer allocation failed");
-        f->data_cap = n;
     }
     if (n > 0 &&
         (hipMemcpyAsync(f->d_st, states, (size_t)n * f->S * 8, hipMemcpyHostToDevice, f->stream) != hipSuccess ||
@@ -1215,7 +1088,7 @@ static int fit_iteration_fused(bcmpc_fitter* f, const int64_t* d_idx, int stride
     a.B = B; a.Bmax = f->Bmax; a.S = f->S; a.A = f->A; a.IN = f->IN; a.L = f->L; a.h = f->h;
     a.act_kind = f->cfg.activation; a.ln = f->cfg.layer_norm ? 1 : 0; a.ldw = f->rows_ld;
     a.lr = f->cfg.learning_rate; a.b1 = f->cfg.beta1; a.b2 = f->cfg.beta2; a.eps = f->cfg.epsilon;
-    hipLaunchKernelGGL(fit_rows_kernel, dim3((B + kFR - 1) / kFR), dim3(64 * kFW), f->rows_lds, f->stream, a);
+    hipLaunchKernelGGL(fit_rows_kernel, dim3((B + kFR - 1) / kFR), dim3(64 * kWaves), f->rows_lds, f->stream, a);
     if (hipGetLastError() != hipSuccess) return ffail(BCMPC_ERR_HIP, "fit_rows_kernel launch failed");
     hipLaunchKernelGGL(fit_params_kernel, dim3(f->ntiles), dim3(256), 0, f->stream, a);
     if (hipGetLastError() != hipSuccess) return ffail(BCMPC_ERR_HIP, "fit_params_kernel launch failed");
@@ -1402,26 +1275,14 @@ int bcmpc_fit_run(bcmpc_fitter* f, const int64_t* indices, const int32_t* batch_
     }
     for (int64_t i = 0; i < total; ++i)
         if (indices[i] < 0 || indices[i] >= f->n_data) return ffail(BCMPC_ERR_ARG, "sample index out of range");
-    if (total > f->idx_cap) {
-        if (f->d_idx) (void)hipFree(f->d_idx);
-        f->d_idx = nullptr;
-        f->idx_cap = 0;
-        if (hipMalloc(&f->d_idx, (size_t)std::max<int64_t>(total, 1) * 8) != hipSuccess)
-            return ffail(BCMPC_ERR_HIP, "index buffer allocation failed");
-        f->idx_cap = total;
-    }
+    if (!train::grow(&f->idx_cap, total, {{&f->d_idx, (size_t)total * 8}}))
+        return ffail(BCMPC_ERR_HIP, "index buffer allocation failed");
     if (total > 0 &&
         hipMemcpyAsync(f->d_idx, indices, (size_t)total * 8, hipMemcpyHostToDevice, f->stream) != hipSuccess)
         return ffail(BCMPC_ERR_HIP, "index upload failed");
-    if (iterations > f->loss_cap) {
-        for (float** p : {&f->d_loss, &f->d_loss2})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        f->loss_cap = 0;
-        if (hipMalloc(&f->d_loss, (size_t)iterations * 4) != hipSuccess ||
-            (f->rw && hipMalloc(&f->d_loss2, (size_t)iterations * 4) != hipSuccess))
-            return ffail(BCMPC_ERR_HIP, "loss buffer allocation failed");
-        f->loss_cap = iterations;
-    }
+    if (!train::grow(&f->loss_cap, iterations, {{&f->d_loss, (size_t)iterations * 4},
+                                                {&f->d_loss2, f->rw ? (size_t)iterations * 4 : 0}}))
+        return ffail(BCMPC_ERR_HIP, "loss buffer allocation failed");
     // device iteration state: counter 0, the host mirror's beta powers
     const float bp[2] = {f->beta1_power, f->beta2_power};
     if (hipMemsetAsync(f->d_iter, 0, 4, f->stream) != hipSuccess ||
@@ -1433,30 +1294,15 @@ int bcmpc_fit_run(bcmpc_fitter* f, const int64_t* indices, const int32_t* batch_
     const bool use_graph = uniform && !(ge && ge[0] == '0');
     if (use_graph) {
         // the whole run as one graph (~20 launches per iteration otherwise dominate a 512-row step)
-        if (!(f->graph && f->graph_iters == iterations && f->graph_b == batch_sizes[0] && f->graph_idx == f->d_idx &&
-              f->graph_loss == f->d_loss)) {
-            if (f->graph) (void)hipGraphExecDestroy(f->graph);
-            f->graph = nullptr;
-            if (hipStreamBeginCapture(f->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
-                return ffail(BCMPC_ERR_HIP, "graph capture failed to start");
-            int rc = BCMPC_OK;
-            for (int i = 0; i < iterations && rc == BCMPC_OK; ++i)
-                rc = fit_iteration(f, f->d_idx, batch_sizes[0], batch_sizes[0], f->d_loss);
-            hipGraph_t g = nullptr;
-            const hipError_t ec = hipStreamEndCapture(f->stream, &g);
-            if (rc != BCMPC_OK || ec != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                return rc != BCMPC_OK ? rc : ffail(BCMPC_ERR_HIP, "graph capture failed");
-            }
-            const hipError_t ei = hipGraphInstantiate(&f->graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (ei != hipSuccess) { f->graph = nullptr; return ffail(BCMPC_ERR_HIP, "graph instantiation failed"); }
-            f->graph_iters = iterations;
-            f->graph_b = batch_sizes[0];
-            f->graph_idx = f->d_idx;
-            f->graph_loss = f->d_loss;
-        }
-        if (hipGraphLaunch(f->graph, f->stream) != hipSuccess) return ffail(BCMPC_ERR_HIP, "graph launch failed");
+        const intptr_t key[train::GraphRun::kKey] = {iterations, batch_sizes[0], (intptr_t)f->d_idx,
+                                                     (intptr_t)f->d_loss};
+        const int rc = f->graph.run(f->stream, key, ffail, [&] {
+            int rs = BCMPC_OK;
+            for (int i = 0; i < iterations && rs == BCMPC_OK; ++i)
+                rs = fit_iteration(f, f->d_idx, batch_sizes[0], batch_sizes[0], f->d_loss);
+            return rs;
+        });
+        if (rc != BCMPC_OK) return rc;
     } else {
         int64_t pos = 0;
         for (int i = 0; i < iterations; ++i) {
@@ -1484,13 +1330,9 @@ int bcmpc_fit_set_rewards(bcmpc_fitter* f, const double* rewards, int64_t n) {
     if (n != f->n_data) return ffail(BCMPC_ERR_ARG, "rewards: one per row of bcmpc_fit_set_data");
     if (hipSetDevice(f->cfg.device) != hipSuccess) return ffail(BCMPC_ERR_HIP, "hipSetDevice failed");
     if (n > f->rw_cap) {
-        fit_drop_graph(f);
-        if (f->d_rwd) (void)hipFree(f->d_rwd);
-        f->d_rwd = nullptr;
-        f->rw_cap = 0;
-        if (hipMalloc(&f->d_rwd, (size_t)std::max<int64_t>(n, 1) * 8) != hipSuccess)
+        f->graph.drop();                                  // (as bcmpc_fit_set_data)
+        if (!train::grow(&f->rw_cap, n, {{&f->d_rwd, (size_t)n * 8}}))
             return ffail(BCMPC_ERR_HIP, "reward buffer allocation failed");
-        f->rw_cap = n;
     }
     if (n > 0 && (hipMemcpyAsync(f->d_rwd, rewards, (size_t)n * 8, hipMemcpyHostToDevice, f->stream) != hipSuccess ||
                   hipStreamSynchronize(f->stream) != hipSuccess))

@@ -83,6 +83,20 @@ int main() {
     const float f[3] = {0.f, 1.f, INFINITY};
     EXPECT(acppo::check_finite(f, 2, "x") == BCMPC_OK && acppo::check_finite(f, 3, "x") == BCMPC_ERR_ARG);
     EXPECT(std::strstr(bcmpc_acppo_last_error(), "x must be finite") != nullptr);
+    // the filter's device image [2][32] at the smallest and the largest state: mean / std up to S, 0 / 1 beyond
+    // (the sources hold exactly S floats: a read past them is the sanitizer's to catch)
+    for (int S : {1, 32}) {
+        std::vector<float> mean(S), sd(S);
+        for (int i = 0; i < S; ++i) { mean[i] = 0.5f + (float)i; sd[i] = 2.0f + (float)i; }
+        EXPECT(acfit::check_filter(mean.data(), sd.data(), S) == BCMPC_OK);
+        float img[64];
+        for (float& x : img) x = NAN;
+        acfit::filter_image(mean.data(), sd.data(), S, img);
+        for (int i = 0; i < 32; ++i) {
+            EXPECT(img[i] == (i < S ? mean[i] : 0.f));
+            EXPECT(img[32 + i] == (i < S ? sd[i] : 1.f));
+        }
+    }
     std::printf(failures ? "%d failures\n" : "ac_ppo_plan_check ok\n", failures);
     return failures ? 1 : 0;
 }
